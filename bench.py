@@ -11,10 +11,15 @@ of per-node statistics (two packed RCCL all-reduces of 160 KB each), outside the
 A "step" is one transient time step of every instance of a rank (companion update -> Newton{device eval, MNA gather,
 multifrontal LU, triangular solves, convergence test}).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-One JSON line on rank 0.  value = instance-steps per second over all GPUs.
+One JSON line on rank 0.  value = instance-steps per second over all GPUs; ms_per_step = wall time of one timed step.
+A plain run sets up, warms up, times the K steps, reduces the per-node statistics and prints the line.  --full adds the extras
+that take runs of their own: the measured HBM copy ceiling, the single-circuit, other-config and shard-rate figures and the CPU
+baselines.  --dump-outputs DIR writes what the timed path computed at its last step as DIR/<name>.npy (float64): a fixed, seeded
+sample of rank 0's instance solutions, their global instance indices, the reduced per-node statistics, and the Newton iterations
+and simulated time of every rank-0 instance.
 """
 import argparse
 import json
@@ -90,6 +95,28 @@ def select_traffic(profiles_dir, build_id, B, nonlinear, W, kernel, algorithmic_
                    "traffic_source": f"none for build_id {build_id}: the newest summary for this configuration, profiles/{tp}, is of build "
                                      f"{tj.get('build_id', 'unknown (before round 4)')} ({tj['hbm_bytes_per_launch']:.4g} B per launch there)"}
     return out
+
+
+DUMP_BYTES = 48 << 20  # what --dump-outputs writes in all (the limit is 64 MB)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, eng, stats, first_instance):
+    """--dump-outputs: what the timed path computed at its last step, float64 only.  The solutions of this rank's instances when
+    they fit in DUMP_BYTES next to the other arrays, else a fixed, seeded sample of them (the same instances from run to run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, rows = eng.batch, eng.rows
+    n = min(B, max(1, (DUMP_BYTES - 8 * np.size(stats) - 16 * B) // (8 * rows)))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    x = np.stack([eng.solution(int(i), 1)[0] for i in idx])
+    st = eng.state()
+    out = {"solution_sample": x,                                           # [n][rows] node voltages / branch currents at t_end
+           "solution_sample_instances": (first_instance + idx).astype(np.float64),  # global instance index (seed - 1) of each row
+           "node_statistics": np.asarray(stats, dtype=np.float64),         # [4][rows] sum, sum of squares, min, max over all instances
+           "newton_iters": st["iters"].astype(np.float64),                 # Newton iterations of every instance of this rank since reset
+           "t_end": st["t"].astype(np.float64)}                            # simulated time of every instance of this rank
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def shard(total, world, rank):
@@ -265,8 +292,10 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="override: instances PER GPU (weak scaling); 0 = shard --instances (strong scaling)")
     ap.add_argument("--mesh", type=int, default=100)
     ap.add_argument("--linear", action="store_true", help="VDC-driven linear variant (no diodes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the extra single-circuit measurement")
+    ap.add_argument("--full", action="store_true", help="also measure the extras (HBM copy ceiling, single circuit, other configs, shard rates, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed at its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-single", action="store_true", help="with --full: skip the single-circuit, other-config and shard-rate measurements")
     ap.add_argument("--cpu-steps", type=int, default=60)
     args = ap.parse_args()
 
@@ -356,6 +385,8 @@ def main():
     t3 = time.perf_counter()
     reduce_ms = (t3 - t1) * 1e3
     allreduce_ms = (t3 - t2) * 1e3 if ranks_seen > 1 else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, stats, lo)
 
     if rank == 0:
         bpi = bytes_per_iteration(info)
@@ -433,7 +464,7 @@ def main():
                            stored_over_structural=info["nnz_lu_stored"] / max(1, info["nnz_lu"]), n_wave_fronts=info.get("n_wave_fronts"),
                            n_quad_fronts=info.get("n_quad_fronts")),
         }
-        ceiling = measured_hbm_ceiling(eng) if world == 1 else None
+        ceiling = measured_hbm_ceiling(eng) if world == 1 and args.full else None
         if isinstance(ceiling, float):
             line["roofline"]["measured_ceiling"] = {"GBps": ceiling, "frac_of_measured": achieved / ceiling,
                                                     "guide_copy_GBps": HBM_GUIDE_COPY_GBS, "frac_of_guide_copy": achieved / HBM_GUIDE_COPY_GBS,
@@ -446,7 +477,7 @@ def main():
         # this line) -- two separate --pmc passes of this same command, corrected with the factors calibrated on this engine's
         # access shapes (scripts/hbm_calib.hip); copied from the committed summary only when it was measured for this configuration
         line["roofline"].update(select_traffic(os.path.join(ROOT, "profiles"), line["build_id"], B, nonlinear, W, kernel, dom_bytes / dom_launches))
-        if world == 1 and not args.no_single:
+        if world == 1 and args.full and not args.no_single:
             # extra (outside the timed region): ONE M10k circuit on the GPU -- the latency-bound case of config C3
             try:
                 line["single_circuit"] = single_circuit_numbers(pe, W, dt, device_index)
@@ -459,7 +490,7 @@ def main():
                 r128 = sr.get("128", {}).get("instance_steps_per_s")
                 if r128:
                     line["shard_rates"]["projected_8gpu_over_1gpu"] = 8.0 * r128 / line["value"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(deck, dt, nonlinear, args.cpu_steps)
                 line["speedup_vs_cpu_1core"] = line["value"] / line["cpu_baseline"]["value"]

@@ -64,3 +64,33 @@ def test_bench_copies_pmc_traffic_only_from_the_same_library_build(tmp_path):
     assert stale["traffic"] is None and stale["traffic_stale"] is True and "aaaa" in stale["traffic_source"] and "cccc" in stale["traffic_source"]
     assert bench.select_traffic(str(tmp_path), "aaaa", 256, True, 100, args[3], 1.0) == {}                # nothing measured for that configuration
     assert bench.select_traffic(str(tmp_path / "missing"), "aaaa", *args) == {}
+
+
+def test_bench_dump_samples_large_sweeps_with_a_fixed_seed(tmp_path):
+    """--dump-outputs on a sweep whose solutions exceed the dump budget: a fixed, seeded sample of the instances (the same one every run),
+    each row the solution of the instance it names, within 64 MB in all."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Eng:
+        batch, rows = 4096, 3000
+
+        def solution(self, first, count):
+            return np.full((count, self.rows), float(first))
+
+        def state(self):
+            return {"iters": np.arange(self.batch, dtype=np.int64), "t": np.full(self.batch, 2e-9)}
+
+    stats = np.ones((4, Eng.rows))
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"d{k}"
+        bench.dump_outputs(str(d), Eng(), stats, 100)
+        outs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = outs
+    assert all(np.array_equal(a[f], b[f]) and a[f].dtype == np.float64 for f in a)
+    idx = a["solution_sample_instances.npy"] - 100
+    assert 1 < len(idx) < Eng.batch and np.all(np.diff(idx) > 0) and idx[-1] < Eng.batch
+    assert np.array_equal(a["solution_sample.npy"][:, 0], idx) and a["solution_sample.npy"].shape == (len(idx), Eng.rows)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20

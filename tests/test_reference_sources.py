@@ -37,13 +37,21 @@ OUT = os.path.join(ROOT, "tests", "cpp", "_build_ref")
 EXPECTED = {"0005.models/cutthrough.cpp": 255}
 
 
-def _programs():
-    if not os.path.isdir(REF_TESTS):
-        return []
-    pats = ["0001.module/*.cpp", "0002.net_list/*.cpp", "0003.circuits/*.cpp", "0004.solver/*.cpp", "0005.models/*.cpp", "0006.digital/*.cpp",
+PATTERNS = ["0001.module/*.cpp", "0002.net_list/*.cpp", "0003.circuits/*.cpp", "0004.solver/*.cpp", "0005.models/*.cpp", "0006.digital/*.cpp",
             "0008.numerical_methods/*.cpp", "0011.nonlinear/*.cpp", "0012.ac/*.cpp"]
+# The names of the programs (names only, in PATTERNS order) are a committed fixture, so that the test ids are the same whether or not
+# the reference tree is present; test_reference_program_list_is_complete checks the list against the tree where it exists.
+PROGRAM_LIST = os.path.join(ROOT, "tests", "golden", "reference_test_programs.txt")
+
+
+def _programs():
+    with open(PROGRAM_LIST) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def _programs_in_tree():
     out = []
-    for p in pats:
+    for p in PATTERNS:
         out += sorted(os.path.relpath(f, REF_TESTS) for f in glob.glob(os.path.join(REF_TESTS, p)))
     return out
 
@@ -87,6 +95,7 @@ def test_reference_program_compiles_unchanged_and_passes(built, rel):
 
 def test_reference_program_list_is_complete():
     names = _programs()
+    assert names == _programs_in_tree(), "tests/golden/reference_test_programs.txt is out of date with the reference's test programs"
     assert len(names) >= 140 and "0001.module/concept.cpp" in names and "0002.net_list/operation.cpp" in names
     assert sum("bsim3v32" in n for n in names) == len(glob.glob(os.path.join(REF_TESTS, "0004.solver", "bsim3v32_*.cpp"))) + len(glob.glob(os.path.join(REF_TESTS, "0012.ac", "bsim3v32_*.cpp")))
     assert sum(n.startswith("0005.models/") for n in names) == len(glob.glob(os.path.join(REF_TESTS, "0005.models", "*.cpp")))

@@ -84,3 +84,31 @@ def test_bench_world2_gloo_statistics_equal_world1(emu):
     assert l2["config"]["instances_total"] == 6 and l2["config"]["instances_rank0"] == 3
     assert l1["newton_iters_per_step"] == pytest.approx(l2["newton_iters_per_step"])
     assert l2["stats_checksum"] == pytest.approx(l1["stats_checksum"], rel=1e-12)
+
+
+def test_bench_plain_run_dumps_the_same_outputs_every_run(emu, tmp_path):
+    """A plain bench.py run measures the headline only (the extras are behind --full), and --dump-outputs writes what the timed path
+    computed at its last step as float .npy files: the same arrays, bit for bit, from two runs with the same arguments."""
+    env = dict(os.environ, PE_HIP_LIB=emu)
+    args = ["--gpus", "1", "--mesh", "16", "--instances", "6", "--steps", "3", "--warmup", "1"]
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)], env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append({f[:-len(".npy")]: np.load(d / f) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "instance-steps/s" and line["dtype"] == "f64"
+    assert not {"single_circuit", "other_configs", "shard_rates", "cpu_baseline", "cpu_baseline_all_cores"} & set(line)
+    assert "measured_ceiling" not in line["roofline"]
+    a, b = dumps
+    assert sorted(a) == ["newton_iters", "node_statistics", "solution_sample", "solution_sample_instances", "t_end"]
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], b[f]), f
+    x = a["solution_sample"]
+    assert x.shape == (6, line["config"]["rows"]) and list(a["solution_sample_instances"]) == list(range(6))   # all six fit: no sampling
+    assert np.allclose(a["node_statistics"], [x.sum(axis=0), (x * x).sum(axis=0), x.min(axis=0), x.max(axis=0)], rtol=1e-12, atol=1e-300)
+    assert np.allclose(a["t_end"], 4 * 1e-10) and np.all(a["newton_iters"] >= 4)
+    assert float(np.sum(a["node_statistics"][0])) == pytest.approx(line["stats_checksum"], rel=1e-12)
