@@ -288,6 +288,52 @@ int pe_hip_sweep_statistics(pe_hip_engine* h, double* out);
 
 int pe_hip_get_instance_state(pe_hip_engine* h, int first_instance, int count, int* status, long long* steps, long long* iters, double* t);
 
+/* ---- Transient probes and measurements (.probe / .measure tran), recorded ON THE DEVICE at every accepted transient step of every
+ * instance; the host reads back only what was asked for.
+ *   pe_hip_set_probes  rows[n_probes]: indices into x as pe_hip_get_solution returns it (node voltages, then branch currents; duplicates
+ *                      allowed); room for `capacity` samples per instance; a sample every `stride`-th accepted step; n_measures streaming
+ *                      measurements m[] over those probes.  Needs a loaded circuit (pe_hip_load_circuit drops the configuration);
+ *                      n_probes = n_measures = 0 removes it.  PE_HIP_ERR_ARG, engine unchanged and usable, for: a row out of range;
+ *                      capacity < 1 or stride < 1; an unknown kind; a measure's probe out of range; CROSS with occurrence < 1 or an edge
+ *                      outside {-1, 0, 1}; batch x capacity x (n_probes + 1) overflowing 64 bits.
+ *   pe_hip_arm_probes  opens a window at every instance's current point: sample 0 = (t_now, x[rows]), every measure initialised there.
+ *                      Every accepted TR step of pe_hip_analyze_tr then updates the measures, and every stride-th one since arming appends
+ *                      a sample (t, x[rows]); samples past `capacity` are only counted (n_dropped) -- the measures still see them.  A
+ *                      rejected or rolled-back step records nothing.  Anything else that moves x or t (pe_hip_analyze_dc, _reset,
+ *                      _set_solution, _set_time, _checkpoint_load, _load_circuit) disarms the window; what it recorded stays readable
+ *                      until the next arm.  No AC.
+ *   pe_hip_get_probe_samples  t [count][capacity], v [count][capacity][n_probes] (slots past n_recorded[b] are NaN), n_recorded [count],
+ *                      n_dropped [count]; any pointer may be NULL.
+ *   pe_hip_get_measures  out [count][n_measures][2], with (t0,v0) -> (t1,v1) consecutive accepted points of the window, T = t_last - t_arm:
+ *                      MIN / MAX  extreme value (strict compare), time of its first occurrence
+ *                      INTEG      sum (t1 - t0)(v0 + v1) / 2, T
+ *                      AVG        INTEG / T (NaN if T = 0), T
+ *                      RMS        sqrt(sum (t1 - t0)(v0^2 + v1^2) / 2 / T) (NaN if T = 0), T
+ *                      CROSS      time of the occurrence-th selected crossing (rise: v0 < level <= v1, fall: v0 > level >= v1, at
+ *                                 t0 + (level - v0)(t1 - t0)/(v1 - v0); NaN if not reached), number of selected crossings seen
+ *                      An instance that was never armed since the configuration reads NaN. */
+enum pe_hip_measure_kind
+{
+    PE_HIP_MEAS_MIN = 1,
+    PE_HIP_MEAS_MAX = 2,
+    PE_HIP_MEAS_AVG = 3,
+    PE_HIP_MEAS_RMS = 4,
+    PE_HIP_MEAS_INTEG = 5,
+    PE_HIP_MEAS_CROSS = 6
+};
+typedef struct pe_hip_measure
+{
+    int kind;       /* pe_hip_measure_kind */
+    int probe;      /* index into the probe list */
+    int edge;       /* CROSS: +1 rise, -1 fall, 0 either */
+    int occurrence; /* CROSS: k >= 1 */
+    double level;   /* CROSS */
+} pe_hip_measure;
+int pe_hip_set_probes(pe_hip_engine* h, int n_probes, const int* rows, int capacity, int stride, int n_measures, const pe_hip_measure* m);
+int pe_hip_arm_probes(pe_hip_engine* h);
+int pe_hip_get_probe_samples(pe_hip_engine* h, int first_instance, int count, double* t, double* v, int* n_recorded, long long* n_dropped);
+int pe_hip_get_measures(pe_hip_engine* h, int first_instance, int count, double* out);
+
 /* ---- Monte-Carlo / parameter sweep over several GPUs of one node (csrc/pe_sweep.cpp).
  * Independent instances of ONE topology are the natural shard of this path: the symbolic analysis is replicated per device, the
  * instances are dealt out in contiguous blocks of ceil(batch / G) per device -- the chunk rule of the reference's only
@@ -311,6 +357,12 @@ int pe_hip_sweep_run(pe_hip_sweep* s, double dt, int nsteps, pe_hip_run_stats* s
 int pe_hip_sweep_reduce(pe_hip_sweep* s, double* out); /* [4][rows]: sum, sum of squares, min, max of the current solution over all instances */
 int pe_hip_sweep_get_solution(pe_hip_sweep* s, int first_instance, int count, double* x);
 int pe_hip_sweep_get_instance_state(pe_hip_sweep* s, int first_instance, int count, int* status, long long* steps, long long* iters, double* t);
+/* transient probes of every instance of the sweep: the same meaning as pe_hip_set_probes / _arm_probes / _get_probe_samples / _get_measures,
+ * forwarded to each device's engine; read-back in global instance order */
+int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int capacity, int stride, int n_measures, const pe_hip_measure* m);
+int pe_hip_sweep_arm_probes(pe_hip_sweep* s);
+int pe_hip_sweep_get_probe_samples(pe_hip_sweep* s, int first_instance, int count, double* t, double* v, int* n_recorded, long long* n_dropped);
+int pe_hip_sweep_get_measures(pe_hip_sweep* s, int first_instance, int count, double* out);
 /* iteration count of every step of instance 0 since the last reset (parity with the reference's Newton counts) */
 int pe_hip_get_newton_trace(pe_hip_engine* h, int capacity, int* iters, int* n_out);
 /* last stamped MNA system of one instance (CSR, sorted columns; vals/rhs may be NULL) */

@@ -1,5 +1,6 @@
 // pe_device.hpp -- plain-data views shared by the host engine and the HIP kernels.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "pe_symbolic.hpp"  // pe_ld
@@ -36,6 +37,33 @@ namespace pe
         DP_TT,      // transit time used by step_changed_tr
         DP_TT_STAMP,  // 1: iterate_tr stamps the diffusion-cap companion, 0: DC stamp only (FBR)
         DP_NCOL
+    };
+
+    // Transient probes (pe_probe.hpp, pe_hip_set_probes): selected rows of x recorded and streaming measurements updated at every accepted
+    // TR step of an armed window.  Lives in the engine; only the launches that record get it, as a ProbedView (below).
+    enum : int
+    {
+        MEAS_MIN = 1,
+        MEAS_MAX,
+        MEAS_AVG,
+        MEAS_RMS,
+        MEAS_INTEG,
+        MEAS_CROSS
+    };
+    struct ProbeView
+    {
+        int n_probes, n_meas, capacity, stride;
+        int const* rows;            // [n_probes] rows of x
+        int const* m_desc;          // [n_meas][4] kind, probe, edge, occurrence
+        double const* m_level;      // [n_meas] CROSS level
+        double* t;                  // [batch][capacity] sample times
+        double* v;                  // [batch][capacity][n_probes] sample values
+        int* n_rec;                 // [batch] samples stored (the cursor: slot of the next sample)
+        long long* n_drop;          // [batch] samples past capacity
+        long long* n_acc;           // [batch] accepted steps since arming
+        double* last;               // [batch][n_probes + 2] t_arm, t of the last accepted point, its probe values
+        double* ms;                 // [batch][n_meas][2] measure state (pe_probe.hpp measure_update)
+        int const* accept;          // [batch] split schedule (k_probe_record): 1 = the step just solved was accepted for this instance
     };
 
     struct DevView
@@ -172,6 +200,8 @@ namespace pe
         int q_lds_stride{};            // doubles between the LDS stacks of two instances of a quad (0: no LDS stack); a launch needs 4 x 8 x this bytes
         int const* q_list{};           // [n_quads][4] instances of a quad (-1: none), ascending; all within one 32-bit byte-offset window of [0]
         int n_quads{};
+        int probe_armed{};             // 1: this view is the DevView part of a ProbedView with an armed window (tr_steps dispatches on it); 0 in the
+                                       // engine's own view.  (It sits in the padding before v_abstol: size and layout of the view are unchanged.)
         // ---- Newton
         double v_abstol, v_reltol, i_abstol, i_reltol;
         int max_newton;
@@ -182,5 +212,14 @@ namespace pe
         double* rres;     // [.][rows]  residual b - A x (right-hand side of the correction solve)
         double* eta_acc;  // [.][4]     max |r_i|, max_i sum_j |a_ij|, max |x_i|, max |b_i| of the last solve (split schedule: atomic max)
         double residual_tol;  // <= 0: check disabled
+    };
+    // (the kernel argument of the probe-less kernels must keep its size: a larger DevView changes the register allocation of k_tr_steps)
+    static_assert(offsetof(DevView, v_abstol) == offsetof(DevView, probe_armed) + sizeof(int), "probe_armed must fill the padding before v_abstol");
+
+    // The view of the launches that record into an armed probe window (k_tr_steps<MINW, true>, k_probe_arm, k_probe_record): the engine's
+    // view + the window.  The engine's own view, which captured launch sequences are keyed by, never carries it.
+    struct ProbedView : DevView
+    {
+        ProbeView pr{};
     };
 }  // namespace pe

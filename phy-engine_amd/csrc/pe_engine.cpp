@@ -233,6 +233,48 @@ int finish_load(pe_hip_engine* h)
     }
     return PE_HIP_OK;
 }
+
+// ---------------- transient probes (pe_probe.hpp)
+pe::ProbedView probe_view(pe_hip_engine const* h)
+{
+    pe::ProbedView V;
+    static_cast<pe::DevView&>(V) = h->V;
+    V.probe_armed = 1;
+    V.pr = h->probe.pv;
+    return V;
+}
+void probe_disarm(pe_hip_engine* h) { h->probe.armed = false; }
+void probe_drop(pe_hip_engine* h)
+{
+    auto& P = h->probe;
+    if(P.configured) (void)hipStreamSynchronize(h->stream);  // (a recording launch may still read the buffers)
+    P.pool.release();
+    P.configured = P.armed = false;
+    P.n_probes = P.n_meas = P.capacity = P.stride = P.batch = 0;
+    P.kind.clear();
+    P.pv = pe::ProbeView{};
+}
+int probe_record_step(pe_hip_engine* h, std::vector<int> const& accepted, double t)
+{
+    auto& P = h->probe;
+    if(!P.armed || std::find(accepted.begin(), accepted.end(), 1) == accepted.end()) return PE_HIP_OK;
+    size_t const B = accepted.size();
+    if(P.pin_cap < B)
+    {
+        if(P.pin_accept) (void)hipHostFree(P.pin_accept);
+        P.pin_accept = nullptr;
+        P.pin_cap = 0;
+        HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&P.pin_accept), B * sizeof(int), hipHostMallocDefault));
+        P.pin_cap = B;
+    }
+    // the staging buffer of the previous step may still be in flight (its copy is stream-ordered); a private device array keeps
+    // upload_active's cache of the `active` mask and the quad list behind it intact
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::copy(accepted.begin(), accepted.end(), P.pin_accept);
+    HIPCHK(h, hipMemcpyAsync(const_cast<int*>(P.pv.accept), P.pin_accept, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, pe::launch_probe_record(h->stream, probe_view(h), t));
+    return PE_HIP_OK;
+}
 }  // namespace pe_eng
 
 extern "C" {
@@ -289,6 +331,7 @@ void pe_hip_destroy(pe_hip_engine* h)
     if(h->ac.eng) pe_hip_destroy(h->ac.eng);
     (void)hipStreamSynchronize(h->stream);
     if(h->graphs) pe::m2_graphs_destroy(h->graphs);  // (captured launch sequences: before the memory they point into and their stream go)
+    h->probe.pool.release();
     h->circ_pool.release();
     h->sym_pool.release();
     h->csr.pool.release();
@@ -301,6 +344,7 @@ void pe_hip_destroy(pe_hip_engine* h)
     if(h->pin_flags) (void)hipHostFree(h->pin_flags);
     if(h->pub_host) (void)hipHostFree(h->pub_host);
     if(h->stats_pinned) (void)hipHostFree(h->stats_pinned);
+    if(h->probe.pin_accept) (void)hipHostFree(h->probe.pin_accept);
     delete h;
 }
 
@@ -419,6 +463,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     h->fact_valid = false;
     h->a_static.clear();
     pe::m2_graphs_clear(h->graphs);  // (captured launch sequences point into the circuit being replaced)
+    probe_drop(h);                   // (a probe configuration belongs to the circuit: rows, batch)
     h->circ_pool.release();
     h->stats_scratch = nullptr;
     h->stats_doubles = 0;
@@ -492,6 +537,7 @@ int pe_hip_set_time(pe_hip_engine* h, double t, double last_step)
 {
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
+    probe_disarm(h);
     std::vector<double> a(h->hc.batch, t), b(h->hc.batch, last_step);
     HIPCHK(h, hipMemcpy(h->V.t_now, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->V.last_step, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -502,6 +548,7 @@ int pe_hip_reset(pe_hip_engine* h)
 {
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
+    probe_disarm(h);
     auto const& hc = h->hc;
     size_t const B = static_cast<size_t>(hc.batch);
     auto& V = h->V;
@@ -538,6 +585,7 @@ int pe_hip_set_solution(pe_hip_engine* h, int first, int count, const double* x)
 {
     if(!h || !h->loaded || !x || first < 0 || count < 0 || first + count > h->hc.batch) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
+    probe_disarm(h);
     HIPCHK(h, hipMemcpy(h->V.x + static_cast<size_t>(first) * h->hc.rows, x, static_cast<size_t>(count) * h->hc.rows * sizeof(double),
                         hipMemcpyHostToDevice));
     return PE_HIP_OK;
@@ -889,6 +937,155 @@ int pe_hip_get_phase_clocks_ex(pe_hip_engine* h, int instance, int capacity, lon
     int const n = std::min(capacity, static_cast<int>(pe::PE_PROF));
     HIPCHK(h, hipMemcpy(ticks, h->V.prof + static_cast<size_t>(instance) * pe::PE_PROF, n * sizeof(long long), hipMemcpyDeviceToHost));
     if(n_out) *n_out = n;
+    return PE_HIP_OK;
+}
+
+
+// ---------------- transient probes and measurements (pe_probe.hpp; include/pe_hip.h)
+int pe_hip_set_probes(pe_hip_engine* h, int n_probes, const int* rows, int capacity, int stride, int n_measures, const pe_hip_measure* m)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(!h->loaded) return fail(h, PE_HIP_ERR_ARG, "set_probes: no circuit loaded");
+    if(n_probes < 0 || n_measures < 0) return fail(h, PE_HIP_ERR_ARG, "set_probes: negative count");
+    HIPCHK(h, hipSetDevice(h->device));
+    if(n_probes == 0 && n_measures == 0)
+    {
+        probe_drop(h);
+        return PE_HIP_OK;
+    }
+    // everything is checked before anything changes: a refused configuration leaves the current one as it was
+    if((n_probes > 0 && !rows) || (n_measures > 0 && !m)) return fail(h, PE_HIP_ERR_ARG, "set_probes: null array");
+    if(capacity < 1 || stride < 1) return fail(h, PE_HIP_ERR_ARG, "set_probes: capacity and stride must be >= 1");
+    long long const B = h->hc.batch;
+    long long n_samples{}, n_doubles{}, n_bytes{};
+    if(__builtin_mul_overflow(B, static_cast<long long>(capacity), &n_samples) || __builtin_mul_overflow(n_samples, static_cast<long long>(n_probes) + 1, &n_doubles) ||
+       __builtin_mul_overflow(n_doubles, static_cast<long long>(sizeof(double)), &n_bytes))
+        return fail(h, PE_HIP_ERR_ARG, "set_probes: batch x capacity x (n_probes + 1) overflows");
+    for(int p = 0; p < n_probes; ++p)
+        if(rows[p] < 0 || rows[p] >= h->hc.rows) return fail(h, PE_HIP_ERR_ARG, "set_probes: row " + std::to_string(rows[p]) + " out of range");
+    for(int k = 0; k < n_measures; ++k)
+    {
+        if(m[k].kind < PE_HIP_MEAS_MIN || m[k].kind > PE_HIP_MEAS_CROSS) return fail(h, PE_HIP_ERR_ARG, "set_probes: unknown measure kind");
+        if(m[k].probe < 0 || m[k].probe >= n_probes) return fail(h, PE_HIP_ERR_ARG, "set_probes: measure of a probe out of range");
+        if(m[k].kind == PE_HIP_MEAS_CROSS && (m[k].occurrence < 1 || m[k].edge < -1 || m[k].edge > 1))
+            return fail(h, PE_HIP_ERR_ARG, "set_probes: CROSS needs occurrence >= 1 and edge in {-1, 0, 1}");
+    }
+    probe_drop(h);
+    auto& P = h->probe;
+    std::vector<int> desc(static_cast<size_t>(n_measures) * 4);
+    std::vector<double> level(static_cast<size_t>(n_measures));
+    for(int k = 0; k < n_measures; ++k)
+    {
+        desc[4 * k] = m[k].kind;
+        desc[4 * k + 1] = m[k].probe;
+        desc[4 * k + 2] = m[k].edge;
+        desc[4 * k + 3] = m[k].occurrence;
+        level[k] = m[k].level;
+        P.kind.push_back(m[k].kind);
+    }
+    pe::ProbeView& pv = P.pv;
+    pv.n_probes = n_probes;
+    pv.n_meas = n_measures;
+    pv.capacity = capacity;
+    pv.stride = stride;
+    int* d_acc{};
+    HIPCHK(h, P.pool.upload(pv.rows, std::vector<int>(rows, rows + n_probes)));
+    HIPCHK(h, P.pool.upload(pv.m_desc, desc));
+    HIPCHK(h, P.pool.upload(pv.m_level, level));
+    HIPCHK(h, P.pool.alloc(pv.t, static_cast<size_t>(n_samples), false));
+    HIPCHK(h, P.pool.alloc(pv.v, static_cast<size_t>(n_samples) * n_probes, false));
+    HIPCHK(h, P.pool.alloc(pv.n_rec, static_cast<size_t>(B)));  // (0: nothing recorded yet)
+    HIPCHK(h, P.pool.alloc(pv.n_drop, static_cast<size_t>(B)));
+    HIPCHK(h, P.pool.alloc(pv.n_acc, static_cast<size_t>(B)));
+    HIPCHK(h, P.pool.alloc(pv.last, static_cast<size_t>(B) * (n_probes + 2)));
+    HIPCHK(h, P.pool.alloc(pv.ms, static_cast<size_t>(B) * n_measures * 2));
+    HIPCHK(h, P.pool.alloc(d_acc, static_cast<size_t>(B)));
+    pv.accept = d_acc;
+    P.n_probes = n_probes;
+    P.n_meas = n_measures;
+    P.capacity = capacity;
+    P.stride = stride;
+    P.batch = static_cast<int>(B);
+    P.configured = true;
+    return PE_HIP_OK;
+}
+
+int pe_hip_arm_probes(pe_hip_engine* h)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(!h->loaded || !h->probe.configured) return fail(h, PE_HIP_ERR_ARG, "arm_probes: no probe configuration (pe_hip_set_probes)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, pe::launch_probe_arm(h->stream, probe_view(h)));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->probe.armed = true;
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_probe_samples(pe_hip_engine* h, int first, int count, double* t, double* v, int* n_recorded, long long* n_dropped)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    auto const& P = h->probe;
+    if(!h->loaded || !P.configured) return fail(h, PE_HIP_ERR_ARG, "get_probe_samples: no probe configuration");
+    if(first < 0 || count < 0 || first + count > P.batch) return fail(h, PE_HIP_ERR_ARG, "get_probe_samples: instance range");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    size_t const cap = static_cast<size_t>(P.capacity), np = static_cast<size_t>(P.n_probes), f = static_cast<size_t>(first), n = static_cast<size_t>(count);
+    std::vector<int> rec(n);
+    if(n == 0) return PE_HIP_OK;
+    HIPCHK(h, hipMemcpy(rec.data(), P.pv.n_rec + f, n * sizeof(int), hipMemcpyDeviceToHost));
+    if(n_recorded) std::copy(rec.begin(), rec.end(), n_recorded);
+    if(n_dropped) HIPCHK(h, hipMemcpy(n_dropped, P.pv.n_drop + f, n * sizeof(long long), hipMemcpyDeviceToHost));
+    double const nan = std::nan("");
+    if(t)
+    {
+        HIPCHK(h, hipMemcpy(t, P.pv.t + f * cap, n * cap * sizeof(double), hipMemcpyDeviceToHost));
+        for(size_t b = 0; b < n; ++b) std::fill(t + b * cap + rec[b], t + (b + 1) * cap, nan);
+    }
+    if(v && np > 0)
+    {
+        HIPCHK(h, hipMemcpy(v, P.pv.v + f * cap * np, n * cap * np * sizeof(double), hipMemcpyDeviceToHost));
+        for(size_t b = 0; b < n; ++b) std::fill(v + (b * cap + rec[b]) * np, v + (b + 1) * cap * np, nan);
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_measures(pe_hip_engine* h, int first, int count, double* out)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    auto const& P = h->probe;
+    if(!h->loaded || !P.configured) return fail(h, PE_HIP_ERR_ARG, "get_measures: no probe configuration");
+    if(first < 0 || count < 0 || first + count > P.batch || (!out && count > 0 && P.n_meas > 0)) return fail(h, PE_HIP_ERR_ARG, "get_measures: instance range");
+    if(count == 0 || P.n_meas == 0) return PE_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    size_t const M = static_cast<size_t>(P.n_meas), L = static_cast<size_t>(P.n_probes) + 2, f = static_cast<size_t>(first), n = static_cast<size_t>(count);
+    std::vector<int> rec(n);
+    std::vector<double> last(n * L);
+    HIPCHK(h, hipMemcpy(rec.data(), P.pv.n_rec + f, n * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(last.data(), P.pv.last + f * L, n * L * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out, P.pv.ms + f * M * 2, n * M * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    double const nan = std::nan("");
+    for(size_t b = 0; b < n; ++b)
+    {
+        double const T = last[b * L + 1] - last[b * L];  // t of the last accepted point - t_arm
+        for(size_t k = 0; k < M; ++k)
+        {
+            double* o = out + (b * M + k) * 2;
+            if(rec[b] == 0)  // never armed since the configuration
+            {
+                o[0] = o[1] = nan;
+                continue;
+            }
+            int const kind = P.kind[k];
+            if(kind == PE_HIP_MEAS_INTEG || kind == PE_HIP_MEAS_AVG || kind == PE_HIP_MEAS_RMS)
+            {
+                if(kind == PE_HIP_MEAS_AVG) o[0] = T == 0.0 ? nan : o[0] / T;
+                else if(kind == PE_HIP_MEAS_RMS)
+                    o[0] = T == 0.0 ? nan : std::sqrt(o[0] / T);
+                o[1] = T;
+            }
+        }
+    }
     return PE_HIP_OK;
 }
 

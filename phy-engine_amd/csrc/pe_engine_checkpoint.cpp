@@ -113,6 +113,7 @@ int pe_hip_checkpoint_load(pe_hip_engine* h, const void* buffer, size_t size)
        hd.dv_len != hc.dv_len || hd.fingerprint != structure_fingerprint(hc))
         return fail(h, PE_HIP_ERR_ARG, "checkpoint_load: the checkpoint belongs to a different circuit (sizes or structure fingerprint: another topology, or the same one built in another order)");
     HIPCHK(h, hipSetDevice(h->device));
+    probe_disarm(h);  // (probe windows are not part of a checkpoint)
     char const* i = static_cast<char const*>(buffer) + sizeof(hd);
     auto const parts = ck_parts(h);
     for(size_t k = 0; k + 1 < parts.size(); ++k)

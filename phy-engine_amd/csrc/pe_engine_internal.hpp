@@ -123,6 +123,18 @@ struct pe_hip_engine
     size_t stats_doubles{};
     double* stats_pinned{};       // pinned host landing buffer of its result (owned by the engine)
     size_t stats_pinned_bytes{};
+    // transient probes (pe_hip_set_probes / pe_hip_arm_probes, pe_probe.hpp): configuration and device buffers (dropped by a circuit
+    // load) and the armed window.  The engine's view V never carries them; the launches that record get probe_view(h).
+    struct Probes
+    {
+        Pool pool;
+        bool configured{}, armed{};
+        int n_probes{}, n_meas{}, capacity{}, stride{}, batch{};
+        std::vector<int> kind;     // per measure (the host finishes AVG / RMS)
+        pe::ProbeView pv{};        // device buffers
+        int* pin_accept{};         // pinned staging of the split schedule's accepted set
+        size_t pin_cap{};
+    } probe;
     Pool circ_pool;  // topology, params, state
     Pool sym_pool;   // symbolic arrays + factor storage
     pe::Symbolic sym;
@@ -229,6 +241,11 @@ namespace pe_eng PE_ENG_HIDDEN
     int analyze_fitting(pe_hip_engine* h, int batch, int geometry_rows, int n, int const* rp, int const* ci, double const* vals, pe::Symbolic& S,
                         pe::SymbolicOptions& so);
     int ensure_symbolic(pe_hip_engine* h, bool tr, double dt);
+    // pe_engine.cpp: transient probes
+    pe::ProbedView probe_view(pe_hip_engine const* h);  // the engine's view + its armed window (probe_armed set)
+    void probe_disarm(pe_hip_engine* h);             // whatever moves x or t other than pe_hip_analyze_tr ends the window (samples stay)
+    void probe_drop(pe_hip_engine* h);               // configuration and buffers gone (pe_hip_load_circuit)
+    int probe_record_step(pe_hip_engine* h, std::vector<int> const& accepted, double t);  // split schedule: one solved step
     // pe_engine_newton.cpp
     bool has_overlay(pe_hip_engine const* h);
     int overlay_call(pe_hip_engine* h, int event, int mode, double t, double dt, int b = 0);

@@ -425,7 +425,7 @@ namespace pe_eng PE_ENG_HIDDEN
         }
         bool const skip_first = only && retry;
         bool const may_reuse = !h->hc.nonlinear && !h->opt.refactor_every_solve && !has_overlay(h);  // (overlay values may change every solve)
-        std::vector<int> res;
+        std::vector<int> res, accepted;
         for(int s = 0; s < nsteps; ++s)
         {
             int alive = 0;
@@ -482,6 +482,7 @@ namespace pe_eng PE_ENG_HIDDEN
                 h->fact_valid = true;
                 h->fact_dt = dt;
             }
+            if(h->probe.armed) accepted.assign(B, 0);
             for(int b = 0; b < B; ++b)
             {
                 if(S.status[b] != PE_HIP_OK || res[b] == 0) continue;
@@ -492,8 +493,12 @@ namespace pe_eng PE_ENG_HIDDEN
                     S.t[b] = t;
                     ++S.steps[b];
                     S.iters[b] += res[b];
+                    if(h->probe.armed) accepted[b] = 1;
                 }
             }
+            // transient probes: only the host knows which instances' steps were accepted (residual check, overlay veto)
+            if(h->probe.armed)
+                if(int const prc = probe_record_step(h, accepted, t); prc != PE_HIP_OK) return prc;
         }
         for(int b = 0; b < B; ++b)
             if(S.status[b] == -1000) S.status[b] = PE_HIP_OK;
@@ -590,6 +595,35 @@ namespace pe_eng PE_ENG_HIDDEN
     }
 }  // namespace pe_eng
 
+#if !defined(__HIPCC__)
+// Builds without HIP (the emulation library of tests/emu, which compiles the engine's translation units with a host compiler): the probe
+// launchers as serial loops over the instances, with a one-thread team
+    #include "pe_probe.hpp"
+namespace pe
+{
+    namespace
+    {
+        struct ProbeHostTeam
+        {
+            int tid() const { return 0; }
+            int size() const { return 1; }
+            void sync() const {}
+        };
+    }  // namespace
+    hipError_t launch_probe_arm(hipStream_t, ProbedView const& V)
+    {
+        for(int b = 0; b < V.batch; ++b) probe_arm(ProbeHostTeam{}, V, b);
+        return hipSuccess;
+    }
+    hipError_t launch_probe_record(hipStream_t, ProbedView const& V, double t)
+    {
+        for(int b = 0; b < V.batch; ++b)
+            if(V.pr.accept[b]) probe_record(ProbeHostTeam{}, V, b, t);
+        return hipSuccess;
+    }
+}  // namespace pe
+#endif
+
 extern "C" {
 
 int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats* st)
@@ -624,7 +658,13 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     {
         bool const reuse = may_reuse && h->fact_valid && h->fact_dt == dt;
         int const n = reuse || !may_reuse ? std::min(chunk, nsteps - done) : 1;  // first step factors, the rest may reuse
-        HIPCHK(h, pe::launch_tr_steps(h->stream, h->V, dt, n, reuse));
+        if(h->probe.armed)
+        {
+            pe::ProbedView const pv = probe_view(h);
+            HIPCHK(h, pe::launch_tr_steps(h->stream, pv, dt, n, reuse));  // (probe_armed set: the kernel that records)
+        }
+        else
+            HIPCHK(h, pe::launch_tr_steps(h->stream, h->V, dt, n, reuse));
         ++launches;
         done += n;
         if(may_reuse)
@@ -668,6 +708,7 @@ int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;
     if(mode != PE_HIP_MODE_OP && mode != PE_HIP_MODE_DC && mode != PE_HIP_MODE_TROP) return fail(h, PE_HIP_ERR_ARG, "analyze_dc: mode must be OP, DC or TROP");
     HIPCHK(h, hipSetDevice(h->device));
+    probe_disarm(h);  // (moves x: ends a probe window)
     if(st) std::memset(st, 0, sizeof(*st));
     h->dominant_ms = 0.0;
     h->dominant_launches = 0;

@@ -30,6 +30,7 @@
 #else
     #define PE_MARK(name) ((void)0)
 #endif
+#include "pe_probe.hpp"  // (after PE_DEV)
 
 namespace pe
 {
@@ -1668,9 +1669,11 @@ namespace pe
         return ST_NO_CONVERGENCE;
     }
 
-    // TR loop of circult::analyze (circuit.h:242-254) for `nsteps` steps of one instance
-    template <class Team>
-    PE_DEV void tr_steps(Team const& tm, DevView const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
+    // TR loop of circult::analyze (circuit.h:242-254) for `nsteps` steps of one instance.  PROBES (View = ProbedView): every accepted step
+    // is recorded into the armed probe window V.pr (pe_probe.hpp) -- a separate instantiation, so that the probe-less resident kernel stays
+    // as it was.
+    template <class Team, bool PROBES, class View>
+    PE_DEV void tr_steps_run(Team const& tm, View const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
     {
         if(V.status[b] != ST_OK) return;
         double t = V.t_now[b];
@@ -1697,6 +1700,7 @@ namespace pe
             }
             ++steps;
             iters += it;
+            if constexpr(PROBES) probe_record(tm, V, b, t);
         }
         tm.sync();
         if(tm.tid() == 0)
@@ -1707,6 +1711,15 @@ namespace pe
             V.n_steps[b] += steps;
             V.n_iters[b] += iters;
         }
+    }
+
+    // the same, dispatched on the armed state of the view (a view with probe_armed set is a ProbedView)
+    template <class Team>
+    PE_DEV void tr_steps(Team const& tm, DevView const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
+    {
+        if(V.probe_armed) tr_steps_run<Team, true>(tm, static_cast<ProbedView const&>(V), b, dt, nsteps, reuse_factor, lds);
+        else
+            tr_steps_run<Team, false>(tm, V, b, dt, nsteps, reuse_factor, lds);
     }
 
     // OP / DC / TROP point of circult::analyze (circuit.h:183-191, 257-266)

@@ -7,7 +7,7 @@
 // independent instances (256 CUs x k workgroups); symbolic data is shared read-only and stays in L2/MALL.
 //
 // Two launch schemes share the front code of pe_front.hpp:
-//   * resident kernels k_tr_steps<MINW> / k_dc_point<MINW> / k_factor_solve: one workgroup per instance does everything
+//   * resident kernels k_tr_steps<MINW, PROBES> / k_dc_point<MINW> / k_factor_solve: one workgroup per instance does everything
 //     (MINW = 2: <= 256 VGPRs, one 512-thread workgroup per CU; MINW = 4: 128 VGPRs, 256-thread workgroups, 4 per CU);
 //   * multi-workgroup schedule k_m2_*: one launch per phase and per top level of the assembly tree, an instance spread over
 //     n_parts workgroups + one workgroup per top front; the host drives the Newton loop from one flag word per instance
@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -564,13 +565,15 @@ namespace pe
     // Two register budgets of the same code: MINW = 2 -> up to 256 VGPRs (one 512-thread workgroup per CU: few
     // instances, lowest latency, no spills); MINW = 4 -> 128 VGPRs (2-4 workgroups per CU: a sweep that oversubscribes
     // the chip hides each workgroup's dependent-latency chains behind the others).
-    template <int MINW>
-    __global__ void __launch_bounds__(PE_THREADS, MINW) k_tr_steps(DevView V, double dt, int nsteps, int reuse_factor)
+    // PROBES: the instantiation that records into an armed probe window (pe_probe.hpp); launched only while one is armed, so that the
+    // probe-less kernel keeps its registers
+    template <int MINW, bool PROBES>
+    __global__ void __launch_bounds__(PE_THREADS, MINW) k_tr_steps(std::conditional_t<PROBES, ProbedView, DevView> V, double dt, int nsteps, int reuse_factor)
     {
         int const b = static_cast<int>(blockIdx.x);
         if(b >= V.batch) return;
         HipTeam tm;
-        tr_steps(tm, V, b, dt, nsteps, reuse_factor != 0, pe_lds);
+        tr_steps_run<HipTeam, PROBES>(tm, V, b, dt, nsteps, reuse_factor != 0, pe_lds);
     }
 
     template <int MINW>
@@ -1071,7 +1074,15 @@ namespace pe
     hipError_t launch_tr_steps(hipStream_t st, DevView const& V, double dt, int nsteps, bool reuse)
     {
         size_t const lds = static_cast<size_t>(V.lds_doubles) * sizeof(double);
-        auto const fn = V.high_occupancy ? &k_tr_steps<4> : &k_tr_steps<2>;
+        if(V.probe_armed)  // (the view is the DevView part of a ProbedView: pe_engine.cpp probe_view)
+        {
+            auto const fn = V.high_occupancy ? &k_tr_steps<4, true> : &k_tr_steps<2, true>;
+            hipError_t e = set_lds(reinterpret_cast<void const*>(fn), lds);
+            if(e != hipSuccess) return e;
+            hipLaunchKernelGGL(fn, dim3(V.batch), dim3(V.n_waves * 64), lds, st, static_cast<ProbedView const&>(V), dt, nsteps, reuse ? 1 : 0);
+            return hipGetLastError();
+        }
+        auto const fn = V.high_occupancy ? &k_tr_steps<4, false> : &k_tr_steps<2, false>;
         hipError_t e = set_lds(reinterpret_cast<void const*>(fn), lds);
         if(e != hipSuccess) return e;
         hipLaunchKernelGGL(fn, dim3(V.batch), dim3(V.n_waves * 64), lds, st, V, dt, nsteps, reuse ? 1 : 0);
@@ -1455,6 +1466,31 @@ namespace pe
         dim3 const grid((V.rows + 255) / 256, n_chunks);
         hipLaunchKernelGGL(k_sweep_stats_partial, grid, dim3(256), 0, st, V.x, V.rows, V.batch, chunk_len, partial);
         hipLaunchKernelGGL(k_sweep_stats_final, dim3(grid.x), dim3(256), 0, st, partial, V.rows, n_chunks, out);
+        return hipGetLastError();
+    }
+
+    // ---- transient probes (pe_probe.hpp): one 64-thread workgroup per instance, lanes over probes and measures
+    __global__ void __launch_bounds__(64) k_probe_arm(ProbedView V)
+    {
+        probe_arm(HipTeam{}, V, static_cast<int>(blockIdx.x));
+    }
+    // the split schedule's step at time t has been solved: the instances the host accepted (V.pr.accept) record it
+    __global__ void __launch_bounds__(64) k_probe_record(ProbedView V, double t)
+    {
+        int const b = static_cast<int>(blockIdx.x);
+        if(!V.pr.accept[b]) return;
+        probe_record(HipTeam{}, V, b, t);
+    }
+    hipError_t launch_probe_arm(hipStream_t st, ProbedView const& V)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_probe_arm, dim3(V.batch), dim3(64), 0, st, V);
+        return hipGetLastError();
+    }
+    hipError_t launch_probe_record(hipStream_t st, ProbedView const& V, double t)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_probe_record, dim3(V.batch), dim3(64), 0, st, V, t);
         return hipGetLastError();
     }
 

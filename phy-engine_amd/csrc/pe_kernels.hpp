@@ -48,4 +48,9 @@ namespace pe
     // per-row {sum v, sum v^2, min, max} of x over the instances (the payload of the sweep's one exchange step):
     // `partial` holds n_chunks x 4 x rows doubles, `out` 4 x rows (both device memory); deterministic (fixed chunk order)
     hipError_t launch_sweep_statistics(hipStream_t st, DevView const& V, int n_chunks, double* partial, double* out);
+    // transient probes (pe_probe.hpp): open the window of every instance at its current point / record the split schedule's step at time t
+    // for the instances with V.pr.accept[b] != 0.  (launch_tr_steps records when its view has probe_armed set: then it is a ProbedView.)
+    // The engine's translation unit pe_engine_newton.cpp holds a serial host definition of both for builds without HIP (the emulation library).
+    hipError_t launch_probe_arm(hipStream_t st, ProbedView const& V);
+    hipError_t launch_probe_record(hipStream_t st, ProbedView const& V, double t);
 }  // namespace pe

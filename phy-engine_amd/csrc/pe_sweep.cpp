@@ -23,6 +23,8 @@ struct pe_hip_sweep
     std::vector<int> lo, hi;  // instances [lo, hi) of the whole sweep on engine g
     int batch{}, rows{};
     bool loaded{};
+    int n_probes{}, n_meas{}, capacity{};  // transient probes: the configuration every engine holds (read-back sizes)
+    bool probes{};
     std::string err;
 };
 
@@ -145,6 +147,7 @@ int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int 
     s->batch = batch;
     s->rows = n_nodes + n_branches;
     s->loaded = false;
+    s->probes = false;  // (a circuit load drops every engine's probe configuration)
     int const rc = for_each_engine(s,
                                    [&](int g)
                                    {
@@ -262,6 +265,85 @@ int pe_hip_sweep_get_instance_state(pe_hip_sweep* s, int first_instance, int cou
         if(int const rc = pe_hip_get_instance_state(s->eng[g], a - s->lo[g], b - a, status ? status + o : nullptr, steps ? steps + o : nullptr, iters ? iters + o : nullptr,
                                                     t ? t + o : nullptr);
            rc != PE_HIP_OK)
+        {
+            s->err = pe_hip_last_error(s->eng[g]);
+            return rc;
+        }
+    }
+    return PE_HIP_OK;
+}
+
+// transient probes: every engine holds the same configuration over its block of instances
+int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int capacity, int stride, int n_measures, const pe_hip_measure* m)
+{
+    if(!s || !s->loaded) return PE_HIP_ERR_ARG;
+    // the whole sweep's buffers: batch x capacity x (n_probes + 1) must not overflow (each engine checks its own block)
+    long long prod{};
+    if((n_probes > 0 || n_measures > 0) && capacity > 0 && n_probes >= 0 &&
+       (__builtin_mul_overflow(static_cast<long long>(s->batch), static_cast<long long>(capacity), &prod) || __builtin_mul_overflow(prod, static_cast<long long>(n_probes) + 1, &prod) ||
+        __builtin_mul_overflow(prod, static_cast<long long>(sizeof(double)), &prod)))
+    {
+        s->err = "set_probes: batch x capacity x (n_probes + 1) overflows";
+        return PE_HIP_ERR_ARG;
+    }
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_probes(s->eng[g], n_probes, rows, capacity, stride, n_measures, m); });
+    if(rc != PE_HIP_OK)
+    {
+        // an argument error is refused by every engine alike (nothing changed); anything else leaves the engines unequal: drop them all
+        if(rc != PE_HIP_ERR_ARG)
+        {
+            for(size_t g = 0; g < s->eng.size(); ++g)
+                if(s->hi[g] > s->lo[g]) (void)pe_hip_set_probes(s->eng[g], 0, nullptr, 0, 0, 0, nullptr);
+            s->probes = false;
+        }
+        return rc;
+    }
+    s->probes = n_probes > 0 || n_measures > 0;
+    s->n_probes = s->probes ? n_probes : 0;
+    s->n_meas = s->probes ? n_measures : 0;
+    s->capacity = s->probes ? capacity : 0;
+    return PE_HIP_OK;
+}
+
+int pe_hip_sweep_arm_probes(pe_hip_sweep* s)
+{
+    if(!s || !s->loaded || !s->probes)
+    {
+        if(s) s->err = "arm_probes: no probe configuration";
+        return PE_HIP_ERR_ARG;
+    }
+    return for_each_engine(s, [&](int g) { return pe_hip_arm_probes(s->eng[g]); });
+}
+
+int pe_hip_sweep_get_probe_samples(pe_hip_sweep* s, int first_instance, int count, double* t, double* v, int* n_recorded, long long* n_dropped)
+{
+    if(!s || !s->loaded || !s->probes || first_instance < 0 || count < 0 || first_instance + count > s->batch) return PE_HIP_ERR_ARG;
+    size_t const cap = static_cast<size_t>(s->capacity), np = static_cast<size_t>(s->n_probes);
+    for(size_t g = 0; g < s->eng.size(); ++g)
+    {
+        int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
+        if(b <= a) continue;
+        size_t const o = static_cast<size_t>(a - first_instance);
+        if(int const rc = pe_hip_get_probe_samples(s->eng[g], a - s->lo[g], b - a, t ? t + o * cap : nullptr, v ? v + o * cap * np : nullptr,
+                                                   n_recorded ? n_recorded + o : nullptr, n_dropped ? n_dropped + o : nullptr);
+           rc != PE_HIP_OK)
+        {
+            s->err = pe_hip_last_error(s->eng[g]);
+            return rc;
+        }
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_sweep_get_measures(pe_hip_sweep* s, int first_instance, int count, double* out)
+{
+    if(!s || !s->loaded || !s->probes || first_instance < 0 || count < 0 || first_instance + count > s->batch) return PE_HIP_ERR_ARG;
+    size_t const M = static_cast<size_t>(s->n_meas);
+    for(size_t g = 0; g < s->eng.size(); ++g)
+    {
+        int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
+        if(b <= a) continue;
+        if(int const rc = pe_hip_get_measures(s->eng[g], a - s->lo[g], b - a, out ? out + static_cast<size_t>(a - first_instance) * M * 2 : nullptr); rc != PE_HIP_OK)
         {
             s->err = pe_hip_last_error(s->eng[g]);
             return rc;

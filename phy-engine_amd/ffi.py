@@ -29,8 +29,12 @@ EXPORTS = [
     "pe_hip_analyze_pattern_fronts", "pe_hip_get_phase_clocks", "pe_hip_get_phase_clocks_ex", "pe_hip_analyze_ac", "pe_hip_get_solution_ac", "pe_hip_checkpoint_size", "pe_hip_checkpoint_save", "pe_hip_checkpoint_load", "pe_hip_set_time",
     "pe_hip_sweep_create", "pe_hip_sweep_destroy", "pe_hip_sweep_last_error", "pe_hip_sweep_devices", "pe_hip_sweep_shard", "pe_hip_sweep_set_options",
     "pe_hip_sweep_load_circuit", "pe_hip_sweep_reset", "pe_hip_sweep_operating_point", "pe_hip_sweep_run", "pe_hip_sweep_reduce", "pe_hip_sweep_get_solution",
-    "pe_hip_sweep_get_instance_state",
+    "pe_hip_sweep_get_instance_state", "pe_hip_set_probes", "pe_hip_arm_probes", "pe_hip_get_probe_samples", "pe_hip_get_measures",
+    "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
 ]
+# pe_hip_measure_kind
+MEAS_MIN, MEAS_MAX, MEAS_AVG, MEAS_RMS, MEAS_INTEG, MEAS_CROSS = 1, 2, 3, 4, 5, 6
+_MEAS_NAMES = {"min": MEAS_MIN, "max": MEAS_MAX, "avg": MEAS_AVG, "rms": MEAS_RMS, "integ": MEAS_INTEG, "cross": MEAS_CROSS}
 
 
 class DeviceTable(C.Structure):
@@ -59,6 +63,72 @@ class Info(C.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Measure(C.Structure):
+    _fields_ = [("kind", C.c_int), ("probe", C.c_int), ("edge", C.c_int), ("occurrence", C.c_int), ("level", C.c_double)]
+
+
+def _measures(measures):
+    """measures: (kind, probe[, level, edge, occurrence]) tuples or dicts with those keys; kind a MEAS_* value or its name ('min', 'cross', ...)."""
+    ms = list(measures)
+    arr = (Measure * max(1, len(ms)))()
+    for i, m in enumerate(ms):
+        if isinstance(m, dict):
+            kind, probe = m["kind"], m["probe"]
+            level, edge, occ = m.get("level", 0.0), m.get("edge", 0), m.get("occurrence", 1)
+        else:
+            kind, probe = m[0], m[1]
+            level = m[2] if len(m) > 2 else 0.0
+            edge = m[3] if len(m) > 3 else 0
+            occ = m[4] if len(m) > 4 else 1
+        kind = _MEAS_NAMES.get(kind, kind) if isinstance(kind, str) else kind
+        arr[i] = Measure(int(kind), int(probe), int(edge), int(occ), float(level))
+    return len(ms), arr
+
+
+def _probe_argtypes(l, prefix):
+    getattr(l, prefix + "set_probes").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(Measure)]
+    getattr(l, prefix + "arm_probes").argtypes = [C.c_void_p]
+    getattr(l, prefix + "get_probe_samples").argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                                C.POINTER(C.c_longlong)]
+    getattr(l, prefix + "get_measures").argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+
+
+class _Probes:
+    """set_probes / arm_probes / probe_samples / measures, shared by Engine and Sweep (prefix pe_hip_ / pe_hip_sweep_)."""
+    _prefix = "pe_hip_"
+    _probe_cfg = (0, 0, 0)  # n_probes, capacity, n_measures
+
+    def set_probes(self, rows, capacity, stride=1, measures=()):
+        """record x[rows] of every instance at every stride-th accepted transient step of an armed window (room for `capacity` samples)
+        and update `measures` on the device; rows=[] with measures=() removes the configuration"""
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        n_m, arr = _measures(measures)
+        self._chk(getattr(lib(), self._prefix + "set_probes")(self._h, len(r), _ip(r), int(capacity), int(stride), n_m, arr))
+        self._probe_cfg = (len(r), int(capacity), n_m) if (len(r) or n_m) else (0, 0, 0)
+
+    def arm_probes(self):
+        self._chk(getattr(lib(), self._prefix + "arm_probes")(self._h))
+
+    def probe_samples(self, first=0, count=None):
+        """(t [count][capacity], v [count][capacity][n_probes], n_recorded [count], n_dropped [count]); slots past n_recorded are NaN"""
+        count = self.batch - first if count is None else count
+        n_p, cap, _ = self._probe_cfg
+        t = np.empty((count, cap))
+        v = np.empty((count, cap, n_p))
+        n_rec = np.empty(count, dtype=np.int32)
+        n_drop = np.empty(count, dtype=np.int64)
+        self._chk(getattr(lib(), self._prefix + "get_probe_samples")(self._h, int(first), int(count), _dp(t), _dp(v), _ip(n_rec),
+                                                            n_drop.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return t, v, n_rec, n_drop
+
+    def measures(self, first=0, count=None):
+        """[count][n_measures][2] (include/pe_hip.h: value, then time / T / crossings seen)"""
+        count = self.batch - first if count is None else count
+        out = np.empty((count, self._probe_cfg[2], 2))
+        self._chk(getattr(lib(), self._prefix + "get_measures")(self._h, int(first), int(count), _dp(out)))
+        return out
 
 
 class RunStats(C.Structure):
@@ -108,6 +178,8 @@ def lib():
         l.pe_hip_build_id.restype = C.c_char_p
         l.pe_hip_build_id.argtypes = []
         l.pe_hip_analyze_pattern.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(Info)]
+        _probe_argtypes(l, "pe_hip_")
+        _probe_argtypes(l, "pe_hip_sweep_")
         _lib = l
     return _lib
 
@@ -211,7 +283,7 @@ def analyze_pattern_fronts(n, row_ptr, col_ind, values=None):
     return p[:k].copy(), u[:k].copy(), par[:k].copy()
 
 
-class Engine:
+class Engine(_Probes):
     """One resident circuit (optionally a batch of parameter instances) on one GPU."""
 
     def __init__(self, device=0):
@@ -265,6 +337,7 @@ class Engine:
         self._chk(lib().pe_hip_load_circuit(self._h, int(n_nodes), int(n_branches), int(batch), len(tables), arr))
         self.rows = n_nodes + n_branches
         self.batch = batch
+        self._probe_cfg = (0, 0, 0)  # (a load drops the probe configuration)
 
     def load_deck(self, deck, batch=1, overrides=None, n_drives=0):
         n_nodes, n_br, tables = deck_tables(deck, batch, overrides, n_drives)
@@ -437,8 +510,9 @@ def build_id():
     return lib().pe_hip_build_id().decode()
 
 
-class Sweep:
+class Sweep(_Probes):
     """Monte-Carlo sweep over the devices of `device_mask` (pe_hip_sweep_*): contiguous instance blocks per device, one engine each."""
+    _prefix = "pe_hip_sweep_"
 
     def __init__(self, device_mask=1):
         l = lib()
@@ -482,6 +556,7 @@ class Sweep:
             arr[i] = DeviceTable(kind, len(nodes), _ip(nodes), None if branch is None else _ip(branch), _dp(par), batched)
         self._chk(lib().pe_hip_sweep_load_circuit(self._h, int(n_nodes), int(n_br), int(batch), len(tables), arr))
         self.rows, self.batch = n_nodes + n_br, batch
+        self._probe_cfg = (0, 0, 0)
 
     def shards(self):
         out = []
