@@ -268,6 +268,54 @@ int pe_hip_checkpoint_load(pe_hip_engine* h, const void* buffer, size_t size);
 int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* stats);
 int pe_hip_get_solution_ac(pe_hip_engine* h, int first_instance, int count, double* re, double* im);
 
+/* A whole frequency sweep as one call.  The points become extra instances of the real-equivalent system on a third engine (batch =
+ * instances of the circuit x points per pass), the value vectors are made on the device (every AC value is constant or omega x a
+ * per-instance constant: one base vector per circuit instance is uploaded per sweep, not one vector per point), iterative refinement is
+ * decided per instance, and only the kept rows come back, in one copy.
+ *   Bands.  The static pivot order is matched on representative values at one frequency, exactly as pe_hip_analyze_ac does it: the
+ *   points are sorted ascending, omega == 0 points form a band of their own, a band starts at its first omega w0, is analysed on instance
+ *   0's values at w0 and takes every point with omega <= 10 w0.  A band is solved in ceil(points / P) passes.
+ *   Points per pass P.  Knob AC_SWEEP_POINTS (pe_hip_set_knob / PHY_ENGINE_HIP_AC_SWEEP_POINTS, read at every sweep); 0 = automatic: what
+ *   fits half of the device's free memory, at most 4 GiB (a fixed 256 MiB in builds without HIP), by pe_hip_info.bytes_per_instance of
+ *   the AC system, never more than the largest band holds or than 65535 instances in all.  Sizing the first automatic sweep of a circuit costs one
+ *   symbolic analysis on the single-point engine if pe_hip_analyze_ac has not run on it yet (not part of n_analyses).  The third engine is
+ *   rebuilt only when P changes.
+ *   Memory outside that budget: the result, 2 x n_points x instances x kept rows doubles, once on the device and once on the host
+ *   (200 points x 8 instances x 10 002 rows: 256 MB each) -- select rows (pe_hip_set_ac_sweep_rows) where that matters.
+ *   A band whose values cannot be analysed (singular at its w0, e.g. a node held by capacitors only at omega = 0) launches nothing: its
+ *   points take the fallback below.  gpu_ms is the HIP-event time around the passes on the engine's stream -- fill, solves, refinement
+ *   with its host round trips, gather --; the bands' symbolic analyses run on the host before them and are not in it.
+ *   Fallback.  A point with an instance at PE_HIP_ERR_SINGULAR / _INACCURATE in its batch, or whose refined solution is not finite, is
+ *   solved again by pe_hip_analyze_ac (which analyses on that point's own values) and counted in n_fallback_points; if that fails too its
+ *   status is the point's status.  A circuit with a host-stamp overlay (pe_hip_set_overlay: the values come from callbacks per omega)
+ *   takes that path for every point.  A HIP error ends the call.
+ * pe_hip_analyze_ac / pe_hip_get_solution_ac are unchanged; after a sweep pe_hip_get_solution_ac holds the last fallback point, if any.
+ * pe_hip_analyze_dc, _analyze_tr, _reset, _set_solution, _checkpoint_load, _update_param and _load_circuit make the stored sweep
+ * unreadable (PE_HIP_ERR_ARG, "no AC sweep yet").  There is no sweep twin on the multi-device pe_hip_sweep_* handle (it has no AC at all). */
+typedef struct pe_hip_ac_sweep_stats {
+    int n_points;            /* as passed */
+    int n_passes;            /* batched factor+solve passes */
+    int points_per_pass;     /* largest number of points put into one pass */
+    int n_analyses;          /* symbolic analyses (one per frequency band) */
+    int n_refine_rounds;     /* correction solves, summed over passes */
+    int n_fallback_points;   /* points that were (re)solved by the single-point path */
+    double gpu_ms;           /* HIP-event time of the passes */
+} pe_hip_ac_sweep_stats;
+
+/* rows of x = [node voltages ; branch currents] kept for every point of the following sweeps; n_rows = 0 / rows = NULL: all rows.
+ * Needs a loaded circuit; dropped by pe_hip_load_circuit.  PE_HIP_ERR_ARG (engine unchanged) for a row out of range.  A stored sweep
+ * becomes unreadable (its layout is that of the rows it was made with). */
+int pe_hip_set_ac_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows);
+
+/* Small-signal AC at omegas[0..n_points) [rad/s], any order, duplicates and 0 allowed, every instance of the batch.  Same meaning per
+ * point as pe_hip_analyze_ac (non-linear devices at their last linearisation: run the OP first).  point_status (may be NULL) receives a
+ * pe_hip_status per point (worst over the instances).  Returns PE_HIP_OK when every point solved, else the first failing point's status;
+ * the points that solved stay readable.  PE_HIP_ERR_ARG for n_points < 1, a negative or non-finite omega, omegas == NULL. */
+int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas, int* point_status, pe_hip_ac_sweep_stats* stats);
+
+/* phasors of the last sweep, in the CALLER's point order: re / im [n_points][count][n_kept_rows]; a failed point reads NaN */
+int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* re, double* im);
+
 /* x = [node voltages ; branch currents], instance-major [count][rows] */
 int pe_hip_get_solution(pe_hip_engine* h, int first_instance, int count, double* x);
 int pe_hip_set_solution(pe_hip_engine* h, int first_instance, int count, const double* x);

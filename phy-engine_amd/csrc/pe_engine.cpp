@@ -325,6 +325,7 @@ void pe_hip_destroy(pe_hip_engine* h)
 {
     if(!h) return;
     (void)hipSetDevice(h->device);
+    ac_sweep_drop(h);
     if(h->ac.d_xacc) (void)hipFree(h->ac.d_xacc);
     if(h->ac.d_b0) (void)hipFree(h->ac.d_b0);
     if(h->ac.d_worst) (void)hipFree(h->ac.d_worst);
@@ -473,6 +474,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     h->careful = false;  // (a false alarm on the previous circuit must not pin this one to the host-driven schedule)
     h->n_refined = h->n_rematched = 0;
     h->sym_pool.release();
+    ac_sweep_drop(h);
     if(h->ac.eng)
     {
         if(h->ac.d_xacc) (void)hipFree(h->ac.d_xacc);
@@ -549,6 +551,7 @@ int pe_hip_reset(pe_hip_engine* h)
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     probe_disarm(h);
+    ac_sweep_invalidate(h);
     auto const& hc = h->hc;
     size_t const B = static_cast<size_t>(hc.batch);
     auto& V = h->V;
@@ -586,6 +589,7 @@ int pe_hip_set_solution(pe_hip_engine* h, int first, int count, const double* x)
     if(!h || !h->loaded || !x || first < 0 || count < 0 || first + count > h->hc.batch) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     probe_disarm(h);
+    ac_sweep_invalidate(h);
     HIPCHK(h, hipMemcpy(h->V.x + static_cast<size_t>(first) * h->hc.rows, x, static_cast<size_t>(count) * h->hc.rows * sizeof(double),
                         hipMemcpyHostToDevice));
     return PE_HIP_OK;
@@ -689,6 +693,7 @@ int pe_hip_update_param(pe_hip_engine* h, int kind, int index, int column, const
 {
     if(!h || !h->loaded || !values || index < 0 || column < 0) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
+    ac_sweep_invalidate(h);
     auto& hc = h->hc;
     int const B = hc.batch;
     auto val = [&](int b) { return batched ? values[b] : values[0]; };

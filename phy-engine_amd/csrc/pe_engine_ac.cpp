@@ -1,24 +1,18 @@
 // pe_engine_ac.cpp -- small-signal AC on the device: pe_hip_analyze_ac / pe_hip_get_solution_ac (the real-equivalent system of pe_ac.hpp
-// solved by a second engine, iterative refinement on the device).
+// solved by a second engine, iterative refinement on the device) and pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep (a whole frequency
+// sweep as batches of that system on a third engine, pe_ac_sweep.hpp).
 #include "pe_engine_internal.hpp"
 
 using namespace pe_eng;
 
-extern "C" {
-
-/* Small-signal AC at angular frequency omega (circult::solve_once with iterate_ac, run once per sweep point by
- * run_ac_analysis, circuit.h:389-431): complex MNA system of the devices' AC stamps, non-linear devices at their LAST
- * linearisation (run pe_hip_analyze_dc(OP) first, as circuit.h:196-209 / the ACOP case do), solved in real-equivalent form. */
-int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
+namespace
 {
-    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if(st) std::memset(st, 0, sizeof(*st));
-    auto& hc = h->hc;
-    if(hc.rows == 0) return PE_HIP_OK;
-    auto& A = h->ac;
-    if(!A.built)
+    // the real-equivalent AC system of the resident circuit and the second engine that solves it, built on first use
+    int ensure_ac_built(pe_hip_engine* h)
     {
+        auto& hc = h->hc;
+        auto& A = h->ac;
+        if(A.built) return PE_HIP_OK;
         if(!pe::build_ac_circuit(hc, A.circ, has_overlay(h) ? &h->overlay : nullptr)) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_ac: could not build the AC system");
         if(pe_hip_create(h->device, &A.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_ac: " + std::string(pe_hip_last_error(nullptr)));
         A.eng->knobs = h->knobs;  // (the real-equivalent system is analysed under the same tuning knobs)
@@ -41,7 +35,89 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
         if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac: " + A.eng->err);
         A.built = true;
         A.sym_omega = -1.0;
+        return PE_HIP_OK;
     }
+
+    // ---- frequency-batched sweep (pe_hip_analyze_ac_sweep)
+    void sweep_engine_drop(pe_hip_engine* h)
+    {
+        auto& W = h->ac.sweep;
+        if(W.eng) pe_hip_destroy(W.eng);  // (synchronises its stream first: nothing reads the buffers below any more)
+        W.eng = nullptr;
+        W.P = 0;
+        W.pass_pool.release();
+    }
+
+    // the third engine: the AC system with batch (circuit batch) x P, constructed like h->ac.eng, and the buffers sized by that batch
+    int sweep_engine_build(pe_hip_engine* h, int P)
+    {
+        auto& A = h->ac;
+        auto& W = A.sweep;
+        sweep_engine_drop(h);
+        if(pe_hip_create(h->device, &W.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_ac_sweep: " + std::string(pe_hip_last_error(nullptr)));
+        W.eng->knobs = h->knobs;
+        W.eng->opt = h->opt;
+        W.eng->hc = A.circ.hc;
+        W.eng->hc.batch = h->hc.batch * P;
+        int const rc = finish_load(W.eng);
+        if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac_sweep: " + W.eng->err);
+        size_t const Q = static_cast<size_t>(h->hc.batch) * P, R2 = static_cast<size_t>(A.circ.hc.rows);
+        double* omega{};
+        int* point{};
+        HIPCHK(h, W.pass_pool.alloc(W.V.xacc, Q * R2));
+        HIPCHK(h, W.pass_pool.alloc(W.V.b0, Q * R2));
+        HIPCHK(h, W.pass_pool.alloc(W.V.worst, Q));
+        HIPCHK(h, W.pass_pool.alloc(W.V.n_above, 1));
+        HIPCHK(h, W.pass_pool.alloc(omega, static_cast<size_t>(P)));
+        HIPCHK(h, W.pass_pool.alloc(point, static_cast<size_t>(P)));
+        W.V.omega = omega;
+        W.V.point = point;
+        W.V.P = P;
+        W.P = P;
+        return PE_HIP_OK;
+    }
+
+    // budget of the automatic pass size: half of the device's free memory, at most 4 GiB -- every band's symbolic analysis allocates the
+    // factor storage of the whole batch again, and past a few hundred instances of a large circuit a pass gains nothing (the band's
+    // host-side analysis dominates it; measured: DESIGN.md).  Builds without HIP have no such query and take a fixed budget.
+    long long sweep_memory_budget()
+    {
+#if defined(__HIPCC__)
+        size_t free_b = 0, total_b = 0;
+        if(hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) return std::min<long long>(static_cast<long long>(free_b / 2), 4ll << 30);
+#endif
+        return 256ll << 20;
+    }
+    constexpr long long SWEEP_MAX_INSTANCES = 65535;  // instances of one engine: the y extent of a launch grid
+}  // namespace
+
+namespace pe_eng
+{
+    void ac_sweep_drop(pe_hip_engine* h)
+    {
+        sweep_engine_drop(h);
+        auto& W = h->ac.sweep;
+        W.circ_pool.release();
+        W.res_pool.release();
+        if(W.d_keep) (void)hipFree(W.d_keep);
+        W = pe_hip_engine::Ac::Sweep{};
+    }
+}  // namespace pe_eng
+
+extern "C" {
+
+/* Small-signal AC at angular frequency omega (circult::solve_once with iterate_ac, run once per sweep point by
+ * run_ac_analysis, circuit.h:389-431): complex MNA system of the devices' AC stamps, non-linear devices at their LAST
+ * linearisation (run pe_hip_analyze_dc(OP) first, as circuit.h:196-209 / the ACOP case do), solved in real-equivalent form. */
+int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if(st) std::memset(st, 0, sizeof(*st));
+    auto& hc = h->hc;
+    if(hc.rows == 0) return PE_HIP_OK;
+    auto& A = h->ac;
+    if(int const brc = ensure_ac_built(h); brc != PE_HIP_OK) return brc;
     int const B = hc.batch;
     // the linearisation the small-signal stamps refer to
     pe::AcOperatingPoint op;
@@ -174,4 +250,404 @@ int pe_hip_get_solution_ac(pe_hip_engine* h, int first, int count, double* re, d
     return PE_HIP_OK;
 }
 
+int pe_hip_set_ac_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows)
+{
+    if(!h || !h->loaded || n_rows < 0 || (n_rows > 0 && !rows)) return h ? fail(h, PE_HIP_ERR_ARG, "set_ac_sweep_rows: bad arguments or no circuit") : PE_HIP_ERR_ARG;
+    for(int k = 0; k < n_rows; ++k)
+        if(rows[k] < 0 || rows[k] >= h->hc.rows) return fail(h, PE_HIP_ERR_ARG, "set_ac_sweep_rows: row out of range");
+    auto& W = h->ac.sweep;
+    W.rows.assign(rows, rows + n_rows);
+    W.rows_on_device = false;
+    W.valid = false;  // (the stored result has the layout of the rows it was made with)
+    return PE_HIP_OK;
+}
+
+/* A whole frequency sweep as batches of the real-equivalent system: the points of a pass are extra instances of a third engine
+ * (h->ac.sweep.eng), the value vectors are made on the device from one base vector per circuit instance (k_ac_sweep_fill), refinement runs
+ * per instance, the kept rows are gathered on the device and copied back once.  Bands, passes and the fallback: include/pe_hip.h. */
+int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas, int* point_status, pe_hip_ac_sweep_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(n_points < 1 || !omegas) return fail(h, PE_HIP_ERR_ARG, "analyze_ac_sweep: n_points < 1 or no omegas");
+    for(int i = 0; i < n_points; ++i)
+        if(!std::isfinite(omegas[i]) || omegas[i] < 0.0) return fail(h, PE_HIP_ERR_ARG, "analyze_ac_sweep: negative or non-finite omega");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto& hc = h->hc;
+    auto& A = h->ac;
+    auto& W = A.sweep;
+    W.valid = false;
+    int const B = hc.batch, N = hc.rows;
+    int const K = W.rows.empty() ? N : static_cast<int>(W.rows.size());
+    pe_hip_ac_sweep_stats S{};
+    S.n_points = n_points;
+    std::vector<int> pst(static_cast<size_t>(n_points), PE_HIP_OK);
+    size_t const plane = static_cast<size_t>(n_points) * B * K;  // doubles of the real (and of the imaginary) parts
+    W.res.assign(2 * plane, std::nan(""));
+    auto finish = [&]() -> int
+    {
+        W.n_points = n_points;
+        W.n_keep = K;
+        W.batch = B;
+        W.valid = true;
+        if(point_status) std::copy(pst.begin(), pst.end(), point_status);
+        if(stats) *stats = S;
+        for(int i = 0; i < n_points; ++i)
+            if(pst[i] != PE_HIP_OK) return fail(h, pst[i], "analyze_ac_sweep: point " + std::to_string(i) + ": " + h->err);
+        return PE_HIP_OK;
+    };
+    if(N == 0) return finish();
+    // the single-point path for point i (the fallback): pe_hip_analyze_ac analyses on that point's own values.  A numerical status is the
+    // point's status; anything else (a HIP error) ends the call.
+    auto single = [&](int i) -> int
+    {
+        ++S.n_fallback_points;
+        int const rc = pe_hip_analyze_ac(h, omegas[i], nullptr);
+        pst[i] = rc;
+        double* re = &W.res[static_cast<size_t>(i) * B * K];
+        double* im = re + plane;
+        if(rc == PE_HIP_OK)
+        {
+            for(int b = 0; b < B; ++b)
+                for(int k = 0; k < K; ++k)
+                {
+                    double const* x2 = &A.x[static_cast<size_t>(b) * 2 * N];
+                    int const r = W.rows.empty() ? k : W.rows[k];
+                    re[static_cast<size_t>(b) * K + k] = x2[r];
+                    im[static_cast<size_t>(b) * K + k] = x2[N + r];
+                }
+            return PE_HIP_OK;
+        }
+        std::fill(re, re + static_cast<size_t>(B) * K, std::nan(""));
+        std::fill(im, im + static_cast<size_t>(B) * K, std::nan(""));
+        return (rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE) ? PE_HIP_OK : rc;
+    };
+    auto numerical = [](int rc) { return rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE; };
+    if(has_overlay(h))
+    {
+        // host-stamped models: their values come from callbacks per omega -- every point takes the single-point path
+        for(int i = 0; i < n_points; ++i)
+            if(int const rc = single(i); rc != PE_HIP_OK) return rc;
+        return finish();
+    }
+    if(int const brc = ensure_ac_built(h); brc != PE_HIP_OK) return brc;
+    auto const& ah = A.circ.hc;
+    int const R2 = ah.rows, rhs0 = A.rhs0;
+    if(rhs0 < pe::DV_FIXED + static_cast<int>(A.circ.slots.size())) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_ac_sweep: value vector shorter than its slots");
+
+    // ---- one base vector per circuit instance (the values at omega = 1) + how every value follows omega: uploaded once per sweep
+    std::vector<double> base(static_cast<size_t>(B) * rhs0, 0.0);
+    std::vector<int> scale(static_cast<size_t>(rhs0), pe::AC_CONST);
+    {
+        pe::AcOperatingPoint op;
+        op.d_geq.resize(static_cast<size_t>(B) * hc.nD());
+        op.dv.resize(static_cast<size_t>(B) * hc.dv_len);
+        op.rl_engaged.resize(static_cast<size_t>(B) * hc.nRl());
+        if(!op.d_geq.empty()) HIPCHK(h, hipMemcpy(op.d_geq.data(), h->V.d_geq, op.d_geq.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if(!op.dv.empty()) HIPCHK(h, hipMemcpy(op.dv.data(), h->V.dv, op.dv.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
+        std::vector<double> one(static_cast<size_t>(ah.dv_len), 0.0);
+        for(int b = 0; b < B; ++b)
+        {
+            pe::fill_ac_values(hc, A.circ, op, b, 1.0, h->opt.g_min, r_open_of(h), one.data());
+            std::copy(one.begin(), one.begin() + rhs0, base.begin() + static_cast<size_t>(b) * rhs0);
+        }
+        for(size_t i = 0; i < A.circ.slots.size(); ++i)
+            switch(A.circ.slots[i].kind)
+            {
+                case pe::AcSlot::C_W:
+                case pe::AcSlot::KL_W11:
+                case pe::AcSlot::KL_W12:
+                case pe::AcSlot::KL_W22: scale[pe::DV_FIXED + i] = pe::AC_OMEGA; break;
+                case pe::AcSlot::L_W:
+                case pe::AcSlot::D_WC: scale[pe::DV_FIXED + i] = pe::AC_OMEGA_ZERO; break;
+                default: break;
+            }
+    }
+    if(!W.V.base)
+    {
+        double* d_base{};
+        int* d_scale{};
+        HIPCHK(h, W.circ_pool.alloc(d_base, base.size(), false));
+        HIPCHK(h, W.circ_pool.alloc(d_scale, scale.size(), false));
+        HIPCHK(h, W.circ_pool.upload(W.V.b_ptr0, A.b_ptr0));
+        HIPCHK(h, W.circ_pool.upload(W.V.b_src0, A.b_src0));
+        W.V.scale = d_scale;
+        W.V.base = d_base;
+        W.V.rhs0 = rhs0;
+        W.V.n_inst = B;
+        W.V.n_half = N;
+    }
+    HIPCHK(h, hipMemcpy(const_cast<double*>(W.V.base), base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.scale), scale.data(), scale.size() * sizeof(int), hipMemcpyHostToDevice));
+
+    // ---- frequency bands: the static pivot order is matched on representative values at one frequency and holds for a decade above it
+    // (the rule of pe_hip_analyze_ac).  Points ascending; omega == 0 a band of its own; a band starts at its first omega w0 and takes every
+    // point with omega <= 10 w0.
+    std::vector<int> order(static_cast<size_t>(n_points));
+    for(int i = 0; i < n_points; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return omegas[a] < omegas[b]; });
+    std::vector<std::pair<int, int>> bands;  // [first, last) in `order`
+    for(int i = 0; i < n_points;)
+    {
+        double const w0 = omegas[order[i]];
+        int j = i + 1;
+        while(j < n_points && (w0 == 0.0 ? omegas[order[j]] == 0.0 : omegas[order[j]] <= 10.0 * w0)) ++j;
+        bands.emplace_back(i, j);
+        i = j;
+    }
+    int largest_band = 0;
+    for(auto const& bd: bands) largest_band = std::max(largest_band, bd.second - bd.first);
+
+    // instance 0's matrix values at omega: what a band's symbolic analysis is matched on (analyse_here of the single-point path)
+    auto representative = [&](double omega, std::vector<double>& out)
+    {
+        int const nnz = static_cast<int>(ah.ci.size());
+        out.assign(static_cast<size_t>(nnz), 0.0);
+        for(int s = 0; s < nnz; ++s)
+        {
+            double acc = 0.0;
+            for(int e = ah.a_ptr[s]; e < ah.a_ptr[s + 1]; ++e)
+            {
+                int const i = ah.a_src[e] >> 1;
+                double const v = pe::ac_sweep_value(base[i], scale[i], omega);
+                acc = (ah.a_src[e] & 1) ? acc - v : acc + v;
+            }
+            out[s] = acc;
+        }
+    };
+
+    // ---- points per pass: the knob, else what fits the memory budget; never more than the largest band needs
+    int const knob_p = knob(h, "AC_SWEEP_POINTS", 0);
+    long long cap = knob_p > 0 ? knob_p : 0;
+    if(cap == 0)
+    {
+        if(W.bytes_per_instance == 0)
+        {
+            // bytes of one instance of the AC system incl. its factor storage, from the single-point engine.  When that has no symbolic
+            // analysis yet one is made on a band's values and forgotten again: pe_hip_analyze_ac then analyses as it always did.  A band
+            // whose values cannot be analysed (a singular system at its omega) says nothing about the others: the next band is tried, and
+            // when none can be analysed the sweep runs one point per pass -- its bands then fail one by one into the single-point path.
+            bool const had = A.eng->sym_class >= 0;
+            int src = had ? PE_HIP_OK : PE_HIP_ERR_SINGULAR;
+            for(size_t k = 0; !had && k < bands.size() && src != PE_HIP_OK; ++k)
+            {
+                representative(omegas[order[bands[k].first]], A.eng->sym_values_override);
+                A.eng->sym_class = -1;
+                src = ensure_symbolic(A.eng, false, 0.0);
+                if(src != PE_HIP_OK && !numerical(src))
+                {
+                    A.eng->sym_class = -1;
+                    A.sym_omega = -1.0;
+                    return fail(h, src, "analyze_ac_sweep (sizing): " + A.eng->err);
+                }
+            }
+            pe_hip_info info{};
+            int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng, &info) : PE_HIP_OK;
+            if(!had)
+            {
+                A.eng->sym_class = -1;
+                A.sym_omega = -1.0;
+            }
+            if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac_sweep (sizing): " + A.eng->err);
+            if(src == PE_HIP_OK) W.bytes_per_instance = std::max<long long>(1, info.bytes_per_instance);
+        }
+        cap = W.bytes_per_instance > 0 ? sweep_memory_budget() / (W.bytes_per_instance * static_cast<long long>(B)) : 1;
+    }
+    cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
+    int const P = static_cast<int>(std::min<long long>(cap, largest_band));
+    if(!W.eng || W.P != P)
+        if(int const rc = sweep_engine_build(h, P); rc != PE_HIP_OK) return rc;
+    S.points_per_pass = 0;
+
+    // ---- result buffer and kept rows on the device
+    if(W.res_len != plane || !W.V.res_re)
+    {
+        W.res_pool.release();
+        W.V.res_re = W.V.res_im = nullptr;
+        W.res_len = 0;
+        HIPCHK(h, W.res_pool.alloc(W.V.res_re, plane, false));
+        HIPCHK(h, W.res_pool.alloc(W.V.res_im, plane, false));
+        W.res_len = plane;
+    }
+    if(!W.rows_on_device)
+    {
+        // (a buffer of its own, reused while it is large enough: a caller alternating row selections allocates nothing)
+        W.V.keep = nullptr;
+        if(W.rows.size() > W.keep_cap)
+        {
+            if(W.d_keep) (void)hipFree(W.d_keep);
+            W.d_keep = nullptr;
+            W.keep_cap = 0;
+            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&W.d_keep), W.rows.size() * sizeof(int)));
+            W.keep_cap = W.rows.size();
+        }
+        if(!W.rows.empty())
+        {
+            HIPCHK(h, hipMemcpy(W.d_keep, W.rows.data(), W.rows.size() * sizeof(int), hipMemcpyHostToDevice));
+            W.V.keep = W.d_keep;
+        }
+        W.rows_on_device = true;
+    }
+    W.V.n_keep = K;
+
+    pe_hip_engine* const E = W.eng;
+    hipStream_t const es = E->stream;
+    int const Q = B * P;
+    std::vector<char> failed(static_cast<size_t>(n_points), 0);
+    std::vector<int> inst_status(static_cast<size_t>(Q)), now(static_cast<size_t>(Q));
+    std::vector<double> omega_h(static_cast<size_t>(P)), worst_h;
+    std::vector<int> point_h(static_cast<size_t>(P));
+    // one batched factor + solve of all Q instances from the device's value vectors; a numerical failure of some instances is theirs alone
+    auto solve = [&]() -> int
+    {
+        HIPCHK(h, hipMemset(E->V.status, 0, static_cast<size_t>(Q) * sizeof(int)));
+        int const rc = pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
+        if(rc != PE_HIP_OK && !numerical(rc)) return fail(h, rc, "analyze_ac_sweep: " + E->err);
+        if(rc != PE_HIP_OK)
+        {
+            // (a status that no instance carries was raised before anything was launched: nothing of this solve is usable)
+            HIPCHK(h, hipMemcpy(now.data(), E->V.status, static_cast<size_t>(Q) * sizeof(int), hipMemcpyDeviceToHost));
+            bool const none = std::all_of(now.begin(), now.end(), [](int s) { return s == 0; });
+            for(int q = 0; q < Q; ++q)
+                if(inst_status[q] == 0) inst_status[q] = none ? rc : now[q];
+        }
+        return PE_HIP_OK;
+    };
+    for(auto const& bd: bands)
+    {
+        // the band's symbolic analysis, on the host, before its passes (so that gpu_ms is theirs alone).  Values that cannot be analysed
+        // (a structurally or numerically singular system at w0, e.g. a node held by capacitors only at omega = 0) fail the BAND, not the
+        // sweep: nothing is launched for it and each of its points goes to the single-point path, which reports that point's own status.
+        representative(omegas[order[bd.first]], E->sym_values_override);
+        E->sym_class = -1;
+        ++S.n_analyses;
+        if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK)
+        {
+            if(!numerical(rc)) return fail(h, rc, "analyze_ac_sweep: " + E->err);
+            for(int k = bd.first; k < bd.second; ++k) failed[order[k]] = 1;
+            continue;
+        }
+        for(int first = bd.first; first < bd.second; first += P)
+        {
+            int const n = std::min(P, bd.second - first);
+            for(int p = 0; p < P; ++p)
+            {
+                point_h[p] = p < n ? order[first + p] : -1;
+                omega_h[p] = omegas[order[first + std::min(p, n - 1)]];
+            }
+            ++S.n_passes;
+            S.points_per_pass = std::max(S.points_per_pass, n);
+            HIPCHK(h, hipMemcpy(const_cast<double*>(W.V.omega), omega_h.data(), static_cast<size_t>(P) * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.point), point_h.data(), static_cast<size_t>(P) * sizeof(int), hipMemcpyHostToDevice));
+            std::fill(inst_status.begin(), inst_status.end(), 0);
+            HIPCHK(h, hipEventRecord(h->ev0, es));
+            HIPCHK(h, pe::launch_ac_sweep_fill(es, E->V, W.V));
+            if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+            HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
+            // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds), decided per instance: the host reads one int per round
+            int above = 0;
+            for(int round = 0; round < 3; ++round)
+            {
+                HIPCHK(h, pe::launch_ac_residual_each(es, E->V, W.V));
+                HIPCHK(h, hipMemcpyAsync(&above, W.V.n_above, sizeof(int), hipMemcpyDeviceToHost, es));
+                HIPCHK(h, hipStreamSynchronize(es));
+                if(above == 0) break;
+                if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+                HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, false));
+                ++S.n_refine_rounds;
+            }
+            HIPCHK(h, pe::launch_ac_sweep_gather(es, E->V, W.V));
+            HIPCHK(h, hipEventRecord(h->ev1, es));
+            HIPCHK(h, hipStreamSynchronize(es));
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            S.gpu_ms += ms;
+            if(above != 0)
+            {
+                // the rounds ran out with instances still above the threshold: fine when their error is merely not at rounding level yet (the
+                // single-point path stops there too), a failure when it is not a number
+                worst_h.resize(static_cast<size_t>(Q));
+                HIPCHK(h, hipMemcpy(worst_h.data(), W.V.worst, static_cast<size_t>(Q) * sizeof(double), hipMemcpyDeviceToHost));
+                for(int q = 0; q < Q; ++q)
+                    if(!std::isfinite(worst_h[q]) && inst_status[q] == 0) inst_status[q] = PE_HIP_ERR_INACCURATE;
+            }
+            for(int p = 0; p < n; ++p)
+                for(int b = 0; b < B; ++b)
+                    if(inst_status[static_cast<size_t>(b) * P + p] != 0) failed[point_h[p]] = 1;
+        }
+    }
+    // ---- one copy of the kept rows of every point, then the single-point path for the points that failed in their batch
+    HIPCHK(h, hipMemcpy(W.res.data(), W.V.res_re, plane * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(W.res.data() + plane, W.V.res_im, plane * sizeof(double), hipMemcpyDeviceToHost));
+    size_t const per_point = static_cast<size_t>(B) * K;
+    for(int i = 0; i < n_points; ++i)
+    {
+        for(size_t k = 0; k < per_point && !failed[i]; ++k)
+            if(!std::isfinite(W.res[i * per_point + k]) || !std::isfinite(W.res[plane + i * per_point + k])) failed[i] = 1;
+        if(failed[i])
+            if(int const rc = single(i); rc != PE_HIP_OK) return rc;
+    }
+    return finish();
+}
+
+int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* re, double* im)
+{
+    if(!h || !h->loaded || !re || !im) return PE_HIP_ERR_ARG;
+    auto const& W = h->ac.sweep;
+    if(!W.valid || W.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_ac_sweep: no AC sweep yet");
+    if(first_point < 0 || n_points < 0 || first_point > W.n_points - n_points || first_instance < 0 || count < 0 || first_instance > W.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_ac_sweep: points or instances out of range");
+    size_t const K = static_cast<size_t>(W.n_keep), plane = static_cast<size_t>(W.n_points) * W.batch * K;
+    for(int i = 0; i < n_points; ++i)
+    {
+        size_t const src = (static_cast<size_t>(first_point + i) * W.batch + first_instance) * K, dst = static_cast<size_t>(i) * count * K;
+        if(count * K == 0) continue;
+        std::memcpy(re + dst, &W.res[src], static_cast<size_t>(count) * K * sizeof(double));
+        std::memcpy(im + dst, &W.res[plane + src], static_cast<size_t>(count) * K * sizeof(double));
+    }
+    return PE_HIP_OK;
+}
+
 }  // extern "C"
+
+#if !defined(__HIPCC__)
+// Builds without HIP (the emulation library of tests/emu): the sweep's launchers as serial loops over the instances, with a one-thread
+// team running the text of pe_ac_sweep.hpp
+namespace pe
+{
+    namespace
+    {
+        struct SweepHostTeam
+        {
+            int tid() const { return 0; }
+            int size() const { return 1; }
+        };
+    }  // namespace
+    hipError_t launch_ac_sweep_fill(hipStream_t, DevView const& V, AcSweepView const& S)
+    {
+        for(int q = 0; q < V.batch; ++q) ac_sweep_fill(SweepHostTeam{}, V, S, q);
+        return hipSuccess;
+    }
+    hipError_t launch_ac_residual_each(hipStream_t, DevView const& V, AcSweepView const& S)
+    {
+        *S.n_above = 0;
+        for(int q = 0; q < V.batch; ++q)
+        {
+            S.worst[q] = ac_residual_each(SweepHostTeam{}, V, S, q);
+            if(ac_needs_refinement(S.worst[q])) ++*S.n_above;
+        }
+        return hipSuccess;
+    }
+    hipError_t launch_ac_accumulate_each(hipStream_t, DevView const& V, AcSweepView const& S, bool first)
+    {
+        for(int q = 0; q < V.batch; ++q) ac_accumulate_each(SweepHostTeam{}, V, S, q, first);
+        return hipSuccess;
+    }
+    hipError_t launch_ac_sweep_gather(hipStream_t, DevView const& V, AcSweepView const& S)
+    {
+        for(int q = 0; q < V.batch; ++q) ac_sweep_gather(SweepHostTeam{}, V, S, q);
+        return hipSuccess;
+    }
+}  // namespace pe
+#endif

@@ -106,6 +106,7 @@ int pe_hip_checkpoint_load(pe_hip_engine* h, const void* buffer, size_t size)
 {
     size_t need = 0;
     if(!buffer || pe_hip_checkpoint_size(h, &need) != PE_HIP_OK || size != need) return h ? fail(h, PE_HIP_ERR_ARG, "checkpoint_load: size does not match the loaded circuit") : PE_HIP_ERR_ARG;
+    ac_sweep_invalidate(h);
     auto const& hc = h->hc;
     CkHeader hd{};
     std::memcpy(&hd, buffer, sizeof(hd));

@@ -5,7 +5,7 @@
 //   pe_engine_policy.cpp      launch geometry by batch size, symbolic analysis + its upload (the PHY_ENGINE_HIP_* knobs live here)
 //   pe_engine_newton.cpp      host-driven Newton / transient loops of the split schedule, residual safety net, pe_hip_analyze_tr / _dc
 //   pe_engine_checkpoint.cpp  pe_hip_checkpoint_*
-//   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac
+//   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep
 //   pe_engine_seam.cpp        pe_hip_solve_csr_complex (the complex twin of the solver seam)
 #pragma once
 // (the helpers below are shared between the engine's translation units only: not exported from libpe_hip.so)
@@ -24,6 +24,7 @@
 
 #include "../../include/pe_hip.h"
 #include "pe_ac.hpp"
+#include "pe_ac_sweep.hpp"
 #include "pe_circuit.hpp"
 #include "pe_device.hpp"
 #include "pe_kernels.hpp"
@@ -161,6 +162,26 @@ struct pe_hip_engine
         std::vector<double> x;            // refined solution [batch][2N]
         double *d_xacc{}, *d_b0{}, *d_worst{};  // device: accumulated solution, the point's right-hand side, worst backward error (refinement)
         size_t d_len{};
+        // frequency-batched sweep (pe_hip_analyze_ac_sweep): a third engine holding the same system with batch (circuit batch) x P -- the
+        // points of one pass are extra instances --, the buffers of its kernels (pe_ac_sweep.hpp) and the stored result
+        struct Sweep
+        {
+            pe_hip_engine* eng{};
+            int P{};                          // points per pass the engine was built for
+            Pool pass_pool;                   // sized by batch x P: xacc, b0, worst, omega, point, n_above
+            Pool circ_pool;                   // sized by the circuit: base vectors, scale flags, right-hand-side lists
+            Pool res_pool;                    // sized by the sweep: the result planes
+            size_t res_len{};                 // doubles in each of res_re / res_im
+            bool rows_on_device{};            // V.keep holds `rows`
+            int* d_keep{};                    // device copy of `rows` (own allocation, reused while large enough)
+            size_t keep_cap{};
+            pe::AcSweepView V{};
+            long long bytes_per_instance{};   // of the AC system (pe_hip_info), measured once per circuit for the automatic P
+            std::vector<int> rows;            // pe_hip_set_ac_sweep_rows; empty: all rows
+            bool valid{};                     // `res` is the sweep of the current circuit at its current operating point
+            int n_points{}, n_keep{}, batch{};
+            std::vector<double> res;          // [2][n_points][batch][n_keep]: real parts, then imaginary parts
+        } sweep;
     } ac;
     std::vector<double> sym_values_override;  // representative |A| values for the row matching (AC engine)
 
@@ -246,6 +267,9 @@ namespace pe_eng PE_ENG_HIDDEN
     void probe_disarm(pe_hip_engine* h);             // whatever moves x or t other than pe_hip_analyze_tr ends the window (samples stay)
     void probe_drop(pe_hip_engine* h);               // configuration and buffers gone (pe_hip_load_circuit)
     int probe_record_step(pe_hip_engine* h, std::vector<int> const& accepted, double t);  // split schedule: one solved step
+    // pe_engine_ac.cpp: the stored AC sweep
+    void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy)
+    inline void ac_sweep_invalidate(pe_hip_engine* h) { h->ac.sweep.valid = false; }  // whatever moves the operating point or the circuit
     // pe_engine_newton.cpp
     bool has_overlay(pe_hip_engine const* h);
     int overlay_call(pe_hip_engine* h, int event, int mode, double t, double dt, int b = 0);

@@ -630,6 +630,7 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
 {
     if(!h || !h->loaded || nsteps < 0 || !(dt > 0.0)) return h ? fail(h, PE_HIP_ERR_ARG, "analyze_tr: bad arguments or no circuit") : PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
+    ac_sweep_invalidate(h);
     if(st) std::memset(st, 0, sizeof(*st));
     h->dominant_ms = 0.0;
     h->dominant_launches = 0;
@@ -709,6 +710,7 @@ int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
     if(mode != PE_HIP_MODE_OP && mode != PE_HIP_MODE_DC && mode != PE_HIP_MODE_TROP) return fail(h, PE_HIP_ERR_ARG, "analyze_dc: mode must be OP, DC or TROP");
     HIPCHK(h, hipSetDevice(h->device));
     probe_disarm(h);  // (moves x: ends a probe window)
+    ac_sweep_invalidate(h);
     if(st) std::memset(st, 0, sizeof(*st));
     h->dominant_ms = 0.0;
     h->dominant_launches = 0;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "pe_front.hpp"
+#include "pe_ac_sweep.hpp"
 #include "pe_kernels.hpp"
 #include "pe_quad.hpp"
 #include "pe_top_plan.hpp"
@@ -1528,6 +1529,70 @@ namespace pe
         size_t const n = static_cast<size_t>(V.batch) * V.rows;
         int const g = static_cast<int>(std::min<size_t>(1024, (n + 255) / 256));
         hipLaunchKernelGGL(k_ac_accumulate, dim3(g > 0 ? g : 1), dim3(256), 0, st, V, xacc, b0, first ? 1 : 0);
+        return hipGetLastError();
+    }
+
+    // ---- frequency-batched AC sweep (pe_ac_sweep.hpp, pe_engine_ac.cpp pe_hip_analyze_ac_sweep): AC-engine instance blockIdx.y = b * P + p
+    // is circuit instance b at point p of the pass; the workgroups of one instance share its slot / row loops (streaming kernels, no LDS)
+    __global__ void __launch_bounds__(256) k_ac_sweep_fill(DevView V, AcSweepView S)
+    {
+        ac_sweep_fill(GridTeam{}, V, S, static_cast<int>(blockIdx.y));
+    }
+    // per-instance refinement: worst[q] instead of one global maximum, so that a point gets its own rounds, not those of the worst one
+    __global__ void __launch_bounds__(256) k_ac_residual_each(DevView V, AcSweepView S)
+    {
+        int const q = static_cast<int>(blockIdx.y);
+        // (non-negative doubles order like their bit patterns and a NaN has the largest pattern: reduced as integers, nothing drops it)
+        unsigned long long u = static_cast<unsigned long long>(__double_as_longlong(fabs(ac_residual_each(GridTeam{}, V, S, q))));
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1)
+        {
+            unsigned long long const t = __shfl_xor(u, o);
+            u = t > u ? t : u;
+        }
+        if((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(S.worst + q), u);
+    }
+    __global__ void __launch_bounds__(256) k_ac_count_above(AcSweepView S, int n)
+    {
+        int const q = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+        if(q < n && ac_needs_refinement(S.worst[q])) atomicAdd(S.n_above, 1);
+    }
+    __global__ void __launch_bounds__(256) k_ac_accumulate_each(DevView V, AcSweepView S, int first)
+    {
+        ac_accumulate_each(GridTeam{}, V, S, static_cast<int>(blockIdx.y), first != 0);
+    }
+    __global__ void __launch_bounds__(256) k_ac_sweep_gather(DevView V, AcSweepView S)
+    {
+        ac_sweep_gather(GridTeam{}, V, S, static_cast<int>(blockIdx.y));
+    }
+    // workgroups per instance of the sweep's streaming kernels: 256 elements each, at most 64 (an instance is one of many)
+    static int sweep_grid(int n) { return std::max(1, std::min(64, (n + 255) / 256)); }
+    hipError_t launch_ac_sweep_fill(hipStream_t st, DevView const& V, AcSweepView const& S)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_ac_sweep_fill, dim3(sweep_grid(V.dv_len), V.batch), dim3(256), 0, st, V, S);
+        return hipGetLastError();
+    }
+    hipError_t launch_ac_residual_each(hipStream_t st, DevView const& V, AcSweepView const& S)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipError_t e = hipMemsetAsync(S.worst, 0, static_cast<size_t>(V.batch) * sizeof(double), st);
+        if(e == hipSuccess) e = hipMemsetAsync(S.n_above, 0, sizeof(int), st);
+        if(e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ac_residual_each, dim3(sweep_grid(V.rows), V.batch), dim3(256), 0, st, V, S);
+        hipLaunchKernelGGL(k_ac_count_above, dim3((V.batch + 255) / 256), dim3(256), 0, st, S, V.batch);
+        return hipGetLastError();
+    }
+    hipError_t launch_ac_accumulate_each(hipStream_t st, DevView const& V, AcSweepView const& S, bool first)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_ac_accumulate_each, dim3(sweep_grid(V.rows), V.batch), dim3(256), 0, st, V, S, first ? 1 : 0);
+        return hipGetLastError();
+    }
+    hipError_t launch_ac_sweep_gather(hipStream_t st, DevView const& V, AcSweepView const& S)
+    {
+        if(V.batch <= 0 || S.n_keep <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_ac_sweep_gather, dim3(sweep_grid(S.n_keep), V.batch), dim3(256), 0, st, V, S);
         return hipGetLastError();
     }
 

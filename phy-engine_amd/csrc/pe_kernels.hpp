@@ -53,4 +53,14 @@ namespace pe
     // The engine's translation unit pe_engine_newton.cpp holds a serial host definition of both for builds without HIP (the emulation library).
     hipError_t launch_probe_arm(hipStream_t st, ProbedView const& V);
     hipError_t launch_probe_record(hipStream_t st, ProbedView const& V, double t);
+    // frequency-batched AC sweep (pe_ac_sweep.hpp): V is the view of the sweep's AC engine, whose instance b * S.P + p is circuit instance b at
+    // point p of the pass.  fill: the value vector of every instance from the base vectors and S.omega.  residual_each: r = b0 - A xacc into
+    // the right-hand-side slots, S.worst[q] per instance and *S.n_above = instances above the refinement threshold (NaN counts).
+    // accumulate_each: xacc (+)= x, after the first time only for the instances above the threshold.  gather: the kept rows of xacc into
+    // S.res_re / S.res_im at the caller's index of each point.  Builds without HIP: serial host definitions in pe_engine_ac.cpp.
+    struct AcSweepView;
+    hipError_t launch_ac_sweep_fill(hipStream_t st, DevView const& V, AcSweepView const& S);
+    hipError_t launch_ac_residual_each(hipStream_t st, DevView const& V, AcSweepView const& S);
+    hipError_t launch_ac_accumulate_each(hipStream_t st, DevView const& V, AcSweepView const& S, bool first);
+    hipError_t launch_ac_sweep_gather(hipStream_t st, DevView const& V, AcSweepView const& S);
 }  // namespace pe

@@ -26,7 +26,7 @@ EXPORTS = [
     "pe_hip_load_circuit", "pe_hip_set_options", "pe_hip_get_info", "pe_hip_set_digital_drives", "pe_hip_set_overlay", "pe_hip_set_knob", "pe_hip_get_knob", "pe_hip_update_param",
     "pe_hip_reset", "pe_hip_analyze_dc", "pe_hip_analyze_tr", "pe_hip_get_solution", "pe_hip_set_solution",
     "pe_hip_get_instance_state", "pe_hip_sweep_statistics", "pe_hip_measure_hbm_ceiling", "pe_hip_get_safety_net_counters", "pe_hip_get_newton_trace", "pe_hip_get_matrix", "pe_hip_analyze_pattern",
-    "pe_hip_analyze_pattern_fronts", "pe_hip_get_phase_clocks", "pe_hip_get_phase_clocks_ex", "pe_hip_analyze_ac", "pe_hip_get_solution_ac", "pe_hip_checkpoint_size", "pe_hip_checkpoint_save", "pe_hip_checkpoint_load", "pe_hip_set_time",
+    "pe_hip_analyze_pattern_fronts", "pe_hip_get_phase_clocks", "pe_hip_get_phase_clocks_ex", "pe_hip_analyze_ac", "pe_hip_get_solution_ac", "pe_hip_set_ac_sweep_rows", "pe_hip_analyze_ac_sweep", "pe_hip_get_ac_sweep", "pe_hip_checkpoint_size", "pe_hip_checkpoint_save", "pe_hip_checkpoint_load", "pe_hip_set_time",
     "pe_hip_sweep_create", "pe_hip_sweep_destroy", "pe_hip_sweep_last_error", "pe_hip_sweep_devices", "pe_hip_sweep_shard", "pe_hip_sweep_set_options",
     "pe_hip_sweep_load_circuit", "pe_hip_sweep_reset", "pe_hip_sweep_operating_point", "pe_hip_sweep_run", "pe_hip_sweep_reduce", "pe_hip_sweep_get_solution",
     "pe_hip_sweep_get_instance_state", "pe_hip_set_probes", "pe_hip_arm_probes", "pe_hip_get_probe_samples", "pe_hip_get_measures",
@@ -139,6 +139,14 @@ class RunStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AcSweepStats(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_passes", C.c_int), ("points_per_pass", C.c_int), ("n_analyses", C.c_int), ("n_refine_rounds", C.c_int),
+                ("n_fallback_points", C.c_int), ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -180,6 +188,9 @@ def lib():
         l.pe_hip_analyze_pattern.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(Info)]
         _probe_argtypes(l, "pe_hip_")
         _probe_argtypes(l, "pe_hip_sweep_")
+        l.pe_hip_set_ac_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.pe_hip_analyze_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(AcSweepStats)]
+        l.pe_hip_get_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = l
     return _lib
 
@@ -338,6 +349,7 @@ class Engine(_Probes):
         self.rows = n_nodes + n_branches
         self.batch = batch
         self._probe_cfg = (0, 0, 0)  # (a load drops the probe configuration)
+        self._ac_rows = None         # (... and the row selection of AC sweeps)
 
     def load_deck(self, deck, batch=1, overrides=None, n_drives=0):
         n_nodes, n_br, tables = deck_tables(deck, batch, overrides, n_drives)
@@ -459,6 +471,32 @@ class Engine(_Probes):
             g.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
             self._chk(g(self._h, 0, self.batch, _dp(re), _dp(im)))
         return re + 1j * im, rc
+
+    def set_ac_sweep_rows(self, rows=None):
+        """rows of x kept for every point of the following analyze_ac_sweep calls; None / empty: all rows"""
+        r = np.ascontiguousarray([] if rows is None else rows, dtype=np.int32).reshape(-1)
+        self._chk(lib().pe_hip_set_ac_sweep_rows(self._h, len(r), _ip(r) if len(r) else None))
+        self._ac_rows = len(r) if len(r) else None
+
+    def analyze_ac_sweep(self, omegas, check=True):
+        """Small-signal AC at every omega of `omegas` (rad/s, any order) in batched passes on the device (pe_hip_analyze_ac_sweep).
+        Returns (x [n_points][batch][n_kept] complex in the caller's order -- NaN where a point failed --, status [n_points], stats dict
+        with the return code under 'rc')."""
+        w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        n = len(w)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        st = AcSweepStats()
+        rc = lib().pe_hip_analyze_ac_sweep(self._h, n, _dp(w), _ip(status), C.byref(st))
+        if check:
+            self._chk(rc)
+        kept = self._ac_rows if getattr(self, "_ac_rows", None) else self.rows
+        re = np.full((n, self.batch, kept), np.nan)
+        im = np.full((n, self.batch, kept), np.nan)
+        if rc not in (ERR_ARG, ERR_NO_DEVICE, ERR_INTERNAL) and n:
+            self._chk(lib().pe_hip_get_ac_sweep(self._h, 0, n, 0, self.batch, _dp(re), _dp(im)))
+        d = st.asdict()
+        d["rc"] = rc
+        return re + 1j * im, status[:n], d
 
     def phase_clocks_coop(self, instance=0):
         """Per-layout breakdown of the cooperative fronts (see pe_hip_get_phase_clocks_ex), microseconds / counts."""

@@ -1269,7 +1269,8 @@ namespace phy_engine
             return x;
         }
 
-        // circuit.h:389-431: single point, linear or logarithmic sweep of omega; every point is one AC solve on the device
+        // circuit.h:389-431: single point, linear or logarithmic sweep of omega.  A sweep is ONE call of pe_hip_analyze_ac_sweep: its points
+        // are solved as batches of instances on the device (include/pe_hip.h); the omega list is formed with the reference's arithmetic.
         [[nodiscard]] bool run_ac_analysis() noexcept
         {
             auto& ac = analyzer_setting.ac;
@@ -1279,30 +1280,76 @@ namespace phy_engine
             if(ac.sweep == sweep_t::linear)
             {
                 double const step = (ac.omega_stop - ac.omega_start) / static_cast<double>(ac.points - 1);
-                for(::std::size_t i = 0; i < ac.points; ++i)
-                {
-                    ac.omega = ac.omega_start + step * static_cast<double>(i);
-                    if(!solve_ac_point(ac.omega)) return false;
-                    ac_sweep_results.push_back({ac.omega, capture_solution_vector()});
-                }
-                return true;
+                ::std::vector<double> omegas(ac.points);
+                for(::std::size_t i = 0; i < ac.points; ++i) omegas[i] = ac.omega_start + step * static_cast<double>(i);
+                return solve_ac_sweep(omegas);
             }
             if(ac.sweep == sweep_t::log)
             {
                 if(ac.omega_start <= 0.0 || ac.omega_stop <= 0.0) return false;
                 double const ratio = ::std::pow(ac.omega_stop / ac.omega_start, 1.0 / static_cast<double>(ac.points - 1));
+                ::std::vector<double> omegas(ac.points);
                 double omega = ac.omega_start;
                 for(::std::size_t i = 0; i < ac.points; ++i)
                 {
-                    ac.omega = omega;
-                    if(!solve_ac_point(ac.omega)) return false;
-                    ac_sweep_results.push_back({ac.omega, capture_solution_vector()});
+                    omegas[i] = omega;
                     omega *= ratio;
                 }
-                return true;
+                return solve_ac_sweep(omegas);
             }
             return solve_ac_point(ac.omega);
         }
+
+        // every point of a sweep in one batched call; ac_sweep_results receives the points up to the first one that failed (the loop of
+        // the reference stops there), nodes and branches hold the phasors of the last point solved, ac.omega its frequency
+        // last_stats (per point in the single-point loop) describes the sweep: gpu_ms of its passes, their number as n_launches, the failed
+        // points as n_failed; last_ac_sweep_stats has the rest.  The sweep keeps ALL rows: a row selection the application made on the same
+        // handle (gpu_engine() + pe_hip_set_ac_sweep_rows) is replaced and has to be made again afterwards.
+        bool solve_ac_sweep(::std::vector<double> const& omegas) noexcept
+        {
+            if(!gpu_ || !loaded_) return false;
+            auto& ac = analyzer_setting.ac;
+            ::std::size_t const rows = node_counter + branch_counter;
+            if(!rows)
+            {
+                for(double const w: omegas) ac_sweep_results.push_back({ac.omega = w, capture_solution_vector()});
+                return true;
+            }
+            int const n = static_cast<int>(omegas.size());
+            ::std::vector<int> status(omegas.size(), PE_HIP_OK);
+            (void)pe_hip_set_ac_sweep_rows(gpu_, 0, nullptr);
+            int const rc = pe_hip_analyze_ac_sweep(gpu_, n, omegas.data(), status.data(), &last_ac_sweep_stats);
+            if(rc == PE_HIP_ERR_ARG || rc == PE_HIP_ERR_NO_DEVICE || rc == PE_HIP_ERR_INTERNAL) return gpu_fail();
+            int n_ok = 0;
+            while(n_ok < n && status[n_ok] == PE_HIP_OK) ++n_ok;
+            last_stats = pe_hip_run_stats{};
+            last_stats.gpu_ms = last_stats.dominant_ms = last_ac_sweep_stats.gpu_ms;
+            last_stats.n_launches = last_stats.dominant_launches = last_ac_sweep_stats.n_passes;
+            for(int const s: status) last_stats.n_failed += s != PE_HIP_OK;
+            ::std::vector<double> re(rows * static_cast<::std::size_t>(n_ok)), im(re.size());
+            if(n_ok && pe_hip_get_ac_sweep(gpu_, 0, n_ok, 0, 1, re.data(), im.data()) != PE_HIP_OK) return gpu_fail();
+            for(int i = 0; i < n_ok; ++i)
+            {
+                ac_sweep_point pt{omegas[i], ::std::vector<::std::complex<double>>(rows)};
+                for(::std::size_t r = 0; r < rows; ++r) pt.x[r] = {re[i * rows + r], im[i * rows + r]};
+                ac_sweep_results.push_back(::std::move(pt));
+            }
+            if(n_ok)
+            {
+                auto const& x = ac_sweep_results.back().x;
+                ac.omega = omegas[n_ok - 1];
+                for(auto* nd: size_t_to_node_p) nd->node_information.an.voltage = x[nd->node_index];
+                nl.ground_node.node_information.an.voltage = {};
+                for(auto* b: size_t_to_branch_p) b->current = x[node_counter + b->index];
+            }
+            if(n_ok < n)
+            {
+                ac.omega = omegas[n_ok];
+                return gpu_fail();
+            }
+            return true;
+        }
+        pe_hip_ac_sweep_stats last_ac_sweep_stats{};  // of the last linear / logarithmic sweep
 
         // one AC solve (solve_once with iterate_ac): phasors scattered into the nodes / branches as complex values
         bool solve_ac_point(double omega) noexcept
