@@ -251,8 +251,56 @@ int pe_hip_reset(pe_hip_engine* h); /* circult::reset(), circuit.h:446-465: t = 
 
 /* one OP / DC / TROP solve (Newton inside), every instance */
 int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* stats);
-/* `nsteps` fixed-dt transient steps, every instance: update_tr_step -> t += dt -> Newton(solve_once) */
+/* `nsteps` fixed-dt transient steps, every instance: update_tr_step -> t += dt -> Newton(solve_once)  (a step chosen by the engine:
+ * pe_hip_analyze_tr_adaptive below) */
 int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats* stats);
+
+/* ---- Variable-step transient: from the current time to the ABSOLUTE time t_stop (> t_now) with a step chosen from the local truncation
+ * error (LTE) of the trapezoidal rule and cut when Newton fails.  One decision per attempted step, taken on the host from ONE small
+ * read-back; the state of a step is snapshotted, rolled back and tested on the device.
+ *   Lockstep.  The batch advances with ONE step sequence (the split schedule solves every instance at one time point per launch sequence):
+ *   the step is decided by the worst instance, so every instance meets its tolerance, and an instance's result depends -- within that
+ *   tolerance -- on its batch-mates.  All instances must sit at the same t (else PE_HIP_ERR_ARG).
+ *   An attempted step of size h = min(dt, dt_max, t_bp - t_now), t_bp the next breakpoint or t_stop, is the ordinary step of
+ *   pe_hip_analyze_tr(h, 1) (companion update, Newton, residual safety net with its retries); the new time is t_now + h as that step
+ *   forms it, and a breakpoint counts as reached when |t - t_bp| <= 4 eps |t_bp|.
+ *     - an instance fails, or its candidate is not finite: roll back, dt = h / 8 (outcome 2).  At h <= dt_min the call ends as
+ *       pe_hip_analyze_tr does: the step rolled back, the failed instances' status kept, their status returned.
+ *     - LTE test, once three accepted points are in the history: err_r = h^3 / 2 |DD3_r| (third divided difference over those points and
+ *       the candidate x*), tol_r = trtol (lte_reltol max(|x*_r|, |x_n,r|) + abstol), q = max err_r / tol_r over all rows of all instances.
+ *       q > 1 (or not a number) and h > dt_min: roll back, dt = h max(0.1, 0.9 q^(-1/3)) (outcome 1); at dt_min the step is accepted and
+ *       counted in n_at_dt_min.
+ *     - accepted (outcome 0): dt = h min(2, 0.9 q^(-1/3)) if the step was tested, else dt = h.  A step that reached a breakpoint other
+ *       than t_stop restarts the history at that point and continues with dt = dt_init.
+ *   The history (three previous solutions per instance, device memory of the engine) is empty at the first adaptive call and after
+ *   everything that ends a probe window (pe_hip_analyze_dc, _reset, _set_solution, _set_time, _checkpoint_load, _load_circuit) and after
+ *   pe_hip_analyze_tr; a call that finds it empty does not count its starting point (it need not lie on the trajectory): its first three
+ *   steps are untested.  A second adaptive call continues the history of the first.  The history is not part of a checkpoint.
+ *   Probes armed before the call record ACCEPTED steps only; pe_hip_get_newton_trace likewise.
+ *   PE_HIP_ERR_ARG, engine unchanged: no circuit, c == NULL, dt_init <= 0, dt_min > dt_max, t_stop <= t_now, a non-finite value, instances at
+ *   different t, a host-stamp overlay (its models keep host state that cannot be rolled back).  There is no twin on the multi-device
+ *   pe_hip_sweep_* handle (each device would choose its own step sequence). */
+typedef struct pe_hip_tr_control {
+    double dt_init;        /* first step, and the step after every breakpoint; > 0 */
+    double dt_min, dt_max; /* <= 0: dt_init * 1e-9 and (t_stop - t_now) / 50 */
+    double lte_reltol, lte_abstol_v, lte_abstol_i; /* <= 0: 1e-3, 1e-6, 1e-9; a NEGATIVE lte_reltol switches the LTE test off */
+    double trtol;          /* <= 0: 7 (SPICE's over-estimate factor of the divided-difference LTE) */
+    long long max_steps;   /* cap on ATTEMPTED steps of this call; <= 0: none.  Reaching it ends the call with PE_HIP_OK and t_end < t_stop */
+    int source_breakpoints;/* 1: corners of SQR / PULSE / SAW / TRI generators whose parameters are shared by the batch are breakpoints
+                              (a generator with more than 100 000 periods before t_stop is left to the LTE test) */
+    int n_breakpoints; const double* breakpoints; /* further absolute times, any order; may be NULL */
+} pe_hip_tr_control;
+typedef struct pe_hip_tr_adaptive_stats {
+    long long n_accepted, n_rejected_lte, n_rejected_newton, n_at_dt_min; /* steps of the batch (one sequence per call) */
+    long long newton_iters_rejected;  /* solve_once-equivalents spent in rejected steps, summed over instances */
+    int n_analyses;                   /* symbolic (re-)analyses the dt range caused */
+    double dt_smallest, dt_largest, t_end; /* over the attempted steps */
+    pe_hip_run_stats run;             /* as pe_hip_analyze_tr fills it: accepted steps / their Newton iterations only */
+} pe_hip_tr_adaptive_stats;
+int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_control* c, pe_hip_tr_adaptive_stats* stats);
+/* every attempted step of the last adaptive call, from entry `first`: dt, and 0 accepted / 1 rejected by LTE / 2 rejected by Newton;
+ * *n_total = entries of the log; dt / outcome may be NULL */
+int pe_hip_get_tr_step_log(pe_hip_engine* h, long long first, int capacity, double* dt, int* outcome, long long* n_total);
 
 /* Checkpoint / resume of the device-resident simulation state of every instance (solution, time, companion histories,
  * junction and relay state, counters, device values): a transient continued from a loaded checkpoint is bit-identical to an
@@ -290,7 +338,7 @@ int pe_hip_get_solution_ac(pe_hip_engine* h, int first_instance, int count, doub
  *   status is the point's status.  A circuit with a host-stamp overlay (pe_hip_set_overlay: the values come from callbacks per omega)
  *   takes that path for every point.  A HIP error ends the call.
  * pe_hip_analyze_ac / pe_hip_get_solution_ac are unchanged; after a sweep pe_hip_get_solution_ac holds the last fallback point, if any.
- * pe_hip_analyze_dc, _analyze_tr, _reset, _set_solution, _checkpoint_load, _update_param and _load_circuit make the stored sweep
+ * pe_hip_analyze_dc, _analyze_tr, _analyze_tr_adaptive, _reset, _set_solution, _checkpoint_load, _update_param and _load_circuit make the stored sweep
  * unreadable (PE_HIP_ERR_ARG, "no AC sweep yet").  There is no sweep twin on the multi-device pe_hip_sweep_* handle (it has no AC at all). */
 typedef struct pe_hip_ac_sweep_stats {
     int n_points;            /* as passed */

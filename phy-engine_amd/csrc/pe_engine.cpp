@@ -243,7 +243,11 @@ pe::ProbedView probe_view(pe_hip_engine const* h)
     V.pr = h->probe.pv;
     return V;
 }
-void probe_disarm(pe_hip_engine* h) { h->probe.armed = false; }
+void probe_disarm(pe_hip_engine* h)
+{
+    h->probe.armed = false;
+    h->tra.n_pts = 0;  // (whatever ends a probe window also restarts the history of the variable-step transient: x or t moved)
+}
 void probe_drop(pe_hip_engine* h)
 {
     auto& P = h->probe;
@@ -465,6 +469,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     h->a_static.clear();
     pe::m2_graphs_clear(h->graphs);  // (captured launch sequences point into the circuit being replaced)
     probe_drop(h);                   // (a probe configuration belongs to the circuit: rows, batch)
+    tr_adaptive_drop(h);             // (... and so do the shadow state and the history of the variable-step transient)
     h->circ_pool.release();
     h->stats_scratch = nullptr;
     h->stats_doubles = 0;

@@ -46,11 +46,9 @@ namespace
         vec(hc.b_src);
         return f;
     }
-    struct CkPart
-    {
-        void* ptr;
-        size_t bytes;
-    };
+}  // namespace
+namespace pe_eng PE_ENG_HIDDEN
+{
     std::vector<CkPart> ck_parts(pe_hip_engine* h)
     {
         auto const& hc = h->hc;
@@ -71,7 +69,7 @@ namespace
                 {V.rl_engaged, B * hc.nRl() * sizeof(int)},
                 {V.dv, B * hc.dv_len * sizeof(double)}};
     }
-}  // namespace
+}  // namespace pe_eng
 }  // extern "C++"
 
 int pe_hip_checkpoint_size(pe_hip_engine* h, size_t* bytes)

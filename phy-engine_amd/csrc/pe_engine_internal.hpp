@@ -28,6 +28,7 @@
 #include "pe_circuit.hpp"
 #include "pe_device.hpp"
 #include "pe_kernels.hpp"
+#include "pe_lte.hpp"
 #include "pe_symbolic.hpp"
 
 #include <map>
@@ -136,6 +137,24 @@ struct pe_hip_engine
         int* pin_accept{};         // pinned staging of the split schedule's accepted set
         size_t pin_cap{};
     } probe;
+    // variable-step transient (pe_hip_analyze_tr_adaptive, pe_lte.hpp): the shadow copy of the state of a step, the history ring and the
+    // result slots (allocated at the first adaptive call, dropped by a circuit load), the history's host side, and the step log of the last call
+    struct TrAdaptive
+    {
+        Pool pool;
+        bool allocated{};
+        pe::StateCopy save{}, restore{};   // state -> shadow, shadow -> state (the arrays of tr_state_parts + the trace cursor)
+        long long* shadow_iters{};         // the shadow of n_iters (what a rejected step spent is read against it)
+        double* hist{};                    // [3][batch][rows]
+        unsigned long long* q_each{};      // [batch]
+        pe::LteResult* result{};
+        int n_pts{};                       // accepted points in the history (0: restarted; the ring holds the last three)
+        int head{};                        // ring slot of the newest point
+        double t_pts[3]{};                 // time of the point in each ring slot
+        std::vector<double> log_dt;
+        std::vector<int> log_outcome;
+    } tra;
+    long long n_symbolic{};  // symbolic analyses of the resident circuit so far (ensure_symbolic)
     Pool circ_pool;  // topology, params, state
     Pool sym_pool;   // symbolic arrays + factor storage
     pe::Symbolic sym;
@@ -267,6 +286,16 @@ namespace pe_eng PE_ENG_HIDDEN
     void probe_disarm(pe_hip_engine* h);             // whatever moves x or t other than pe_hip_analyze_tr ends the window (samples stay)
     void probe_drop(pe_hip_engine* h);               // configuration and buffers gone (pe_hip_load_circuit)
     int probe_record_step(pe_hip_engine* h, std::vector<int> const& accepted, double t);  // split schedule: one solved step
+    // pe_engine_checkpoint.cpp: every array that makes up the state of an instance, in the order of the checkpoint blob -- shared with the
+    // variable-step transient's device-side snapshot so that the two cannot drift
+    struct CkPart
+    {
+        void* ptr;
+        size_t bytes;
+    };
+    std::vector<CkPart> ck_parts(pe_hip_engine* h);
+    // pe_engine_newton.cpp: variable-step transient
+    void tr_adaptive_drop(pe_hip_engine* h);  // shadow state, history ring and step log gone (pe_hip_load_circuit)
     // pe_engine_ac.cpp: the stored AC sweep
     void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy)
     inline void ac_sweep_invalidate(pe_hip_engine* h) { h->ac.sweep.valid = false; }  // whatever moves the operating point or the circuit

@@ -621,8 +621,175 @@ namespace pe
             if(V.pr.accept[b]) probe_record(ProbeHostTeam{}, V, b, t);
         return hipSuccess;
     }
+    // ... and those of the variable-step transient (pe_lte.hpp)
+    hipError_t launch_tr_lte(hipStream_t, DevView const& V, LteView const& L)
+    {
+        *L.result = LteResult{};
+        for(int b = 0; b < V.batch; ++b)
+        {
+            int nonfinite = 0;
+            unsigned long long const u = lte_partial(ProbeHostTeam{}, V, L, b, nonfinite);
+            if(L.test)
+            {
+                L.q_each[b] = u;
+                if(u > L.result->q) L.result->q = u;
+            }
+            L.result->n_nonfinite += nonfinite;
+            if(V.status[b] != 0) ++L.result->n_failed;
+            L.result->iters_spent += L.iters_now[b] - L.iters_before[b];
+        }
+        return hipSuccess;
+    }
+    hipError_t launch_tr_history_push(hipStream_t, DevView const& V, double* hist, int slot)
+    {
+        lte_history_push(ProbeHostTeam{}, V, hist, slot);
+        return hipSuccess;
+    }
+    hipError_t launch_tr_state_copy(hipStream_t, StateCopy const& S)
+    {
+        for(int p = 0; p < S.n; ++p)
+            if(S.bytes[p]) std::memcpy(S.dst[p], S.src[p], S.bytes[p]);
+        return hipSuccess;
+    }
 }  // namespace pe
 #endif
+
+namespace pe_eng PE_ENG_HIDDEN
+{
+    // The stepping part of pe_hip_analyze_tr: `nsteps` steps of dt on the schedule in effect, then the residual safety net's retries of
+    // the instances whose solve stayed inaccurate.  The caller has run ensure_symbolic and cleared the status; s0 = n_steps before the
+    // steps.  Leaves the stream synchronised.  pe_hip_analyze_tr_adaptive takes its single steps through here too.
+    int tr_run_steps(pe_hip_engine* h, double dt, int nsteps, std::vector<long long> const& s0, int& launches)
+    {
+        int rc = PE_HIP_OK;
+        bool const may_reuse = !h->hc.nonlinear && !h->opt.refactor_every_solve && !has_overlay(h);
+        int const chunk = h->hc.rows > 2000 ? 32 : (h->hc.rows > 200 ? 256 : 2048);
+        int done = 0;
+        if(split_launch(h))
+        {
+            rc = run_m2_tr(h, dt, nsteps, launches);
+            if(rc != PE_HIP_OK) return rc;
+            done = nsteps;
+        }
+        if(done < nsteps) h->a_static.clear();  // (the resident kernel stamps the matrix itself: what the split schedule knew about it is void)
+        while(done < nsteps)
+        {
+            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == dt;
+            int const n = reuse || !may_reuse ? std::min(chunk, nsteps - done) : 1;  // first step factors, the rest may reuse
+            if(h->probe.armed)
+            {
+                pe::ProbedView const pv = probe_view(h);
+                HIPCHK(h, pe::launch_tr_steps(h->stream, pv, dt, n, reuse));  // (probe_armed set: the kernel that records)
+            }
+            else
+                HIPCHK(h, pe::launch_tr_steps(h->stream, h->V, dt, n, reuse));
+            ++launches;
+            done += n;
+            if(may_reuse)
+            {
+                h->fact_valid = true;
+                h->fact_dt = dt;
+            }
+        }
+        for(int attempt = 0; attempt < 2; ++attempt)
+        {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            std::vector<std::pair<int, std::vector<int>>> groups;
+            rc = prepare_inaccurate_retry(h, true, dt, attempt, s0, nsteps, groups);
+            if(rc != PE_HIP_OK) return rc;
+            if(groups.empty()) break;
+            for(auto const& g: groups)
+            {
+                rc = run_m2_tr(h, dt, g.first, launches, &g.second);
+                if(rc != PE_HIP_OK) return rc;
+            }
+        }
+        return PE_HIP_OK;
+    }
+}  // namespace pe_eng
+
+namespace pe_eng PE_ENG_HIDDEN
+{
+    void tr_adaptive_drop(pe_hip_engine* h)
+    {
+        auto& A = h->tra;
+        if(A.allocated) (void)hipStreamSynchronize(h->stream);
+        A.pool.release();
+        A = pe_hip_engine::TrAdaptive{};
+    }
+
+    // shadow set of the state of a step (tr_state_parts = the arrays of a checkpoint, + the cursor of the Newton trace so that the trace
+    // keeps accepted steps only), history ring and result slots: allocated once per resident circuit
+    int tr_adaptive_alloc(pe_hip_engine* h)
+    {
+        auto& A = h->tra;
+        if(A.allocated) return PE_HIP_OK;
+        auto parts = ck_parts(h);
+        parts.push_back({h->V.trace_len, sizeof(int)});
+        if(parts.size() > 16) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_tr_adaptive: the state of an instance has more arrays than the snapshot table holds");
+        A.save = A.restore = pe::StateCopy{};
+        for(auto const& p: parts)
+        {
+            if(p.bytes == 0) continue;
+            char* shadow{};
+            HIPCHK(h, A.pool.alloc(shadow, p.bytes, false));
+            int const k = A.save.n++;
+            A.save.dst[k] = shadow;
+            A.save.src[k] = p.ptr;
+            A.save.bytes[k] = p.bytes;
+            A.restore.dst[k] = p.ptr;
+            A.restore.src[k] = shadow;
+            A.restore.bytes[k] = p.bytes;
+            if(p.ptr == h->V.n_iters) A.shadow_iters = reinterpret_cast<long long*>(shadow);
+        }
+        A.restore.n = A.save.n;
+        size_t const B = static_cast<size_t>(h->hc.batch);
+        HIPCHK(h, A.pool.alloc(A.hist, 3 * B * h->hc.rows));
+        HIPCHK(h, A.pool.alloc(A.q_each, B));
+        HIPCHK(h, A.pool.alloc(A.result, 1));
+        A.n_pts = 0;
+        A.allocated = true;
+        return PE_HIP_OK;
+    }
+
+    // corners of the generators whose parameters every instance shares (pe_front.hpp eval_devices: t0 = t + phase / (2 pi f), tm = fmod(t0, T);
+    // sawtooth 0; square 0, duty T; pulse 0, tr, duty T - tf, duty T; triangle 0, T / 2) inside (t0, t1]
+    void source_breakpoints(pe_hip_engine const* h, double t0, double t1, std::vector<double>& out)
+    {
+        auto const& hc = h->hc;
+        int const n = hc.nTs();
+        for(int i = 0; i < n; ++i)
+        {
+            int const kind = hc.ts_kind[static_cast<size_t>(i)];
+            if(kind == 0) continue;  // IAC: smooth
+            double const* p = &hc.ts_par[static_cast<size_t>(i) * 8];
+            bool shared = true;
+            for(int b = 1; b < hc.batch && shared; ++b)
+                shared = std::memcmp(p, &hc.ts_par[(static_cast<size_t>(b) * n + i) * 8], 8 * sizeof(double)) == 0;
+            double const freq = p[3];
+            if(!shared || !(freq > 0.0) || !((t1 - t0) * freq <= 1e5)) continue;
+            double const T = 1.0 / freq, shift = p[5] / (2.0 * 3.14159265358979323846) / freq;
+            double corner[4] = {0.0, 0.0, 0.0, 0.0};
+            int nc = 1;
+            if(kind == 2) corner[nc++] = p[4] * T;
+            else if(kind == 3)
+            {
+                corner[nc++] = p[6];
+                corner[nc++] = p[4] * T - p[7];
+                corner[nc++] = p[4] * T;
+            }
+            else if(kind == 4)
+                corner[nc++] = 0.5 * T;
+            double const k0 = std::floor((t0 + shift) / T) - 1.0, k1 = std::floor((t1 + shift) / T) + 1.0;
+            for(double k = k0; k <= k1; k += 1.0)
+                for(int c = 0; c < nc; ++c)
+                {
+                    double const tb = k * T + corner[c] - shift;
+                    if(corner[c] >= 0.0 && corner[c] < T && tb > t0 && tb <= t1) out.push_back(tb);
+                }
+        }
+    }
+}  // namespace pe_eng
 
 extern "C" {
 
@@ -631,6 +798,7 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     if(!h || !h->loaded || nsteps < 0 || !(dt > 0.0)) return h ? fail(h, PE_HIP_ERR_ARG, "analyze_tr: bad arguments or no circuit") : PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     ac_sweep_invalidate(h);
+    h->tra.n_pts = 0;  // (fixed steps restart the history of the variable-step transient)
     if(st) std::memset(st, 0, sizeof(*st));
     h->dominant_ms = 0.0;
     h->dominant_launches = 0;
@@ -644,49 +812,10 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     rc = snapshot_counters(h, s0, i0);
     if(rc != PE_HIP_OK) return rc;
     bool const may_reuse = !h->hc.nonlinear && !h->opt.refactor_every_solve && !has_overlay(h);
-    int const chunk = h->hc.rows > 2000 ? 32 : (h->hc.rows > 200 ? 256 : 2048);
     int launches = 0;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    int done = 0;
-    if(split_launch(h))
-    {
-        rc = run_m2_tr(h, dt, nsteps, launches);
-        if(rc != PE_HIP_OK) return rc;
-        done = nsteps;
-    }
-    if(done < nsteps) h->a_static.clear();  // (the resident kernel stamps the matrix itself: what the split schedule knew about it is void)
-    while(done < nsteps)
-    {
-        bool const reuse = may_reuse && h->fact_valid && h->fact_dt == dt;
-        int const n = reuse || !may_reuse ? std::min(chunk, nsteps - done) : 1;  // first step factors, the rest may reuse
-        if(h->probe.armed)
-        {
-            pe::ProbedView const pv = probe_view(h);
-            HIPCHK(h, pe::launch_tr_steps(h->stream, pv, dt, n, reuse));  // (probe_armed set: the kernel that records)
-        }
-        else
-            HIPCHK(h, pe::launch_tr_steps(h->stream, h->V, dt, n, reuse));
-        ++launches;
-        done += n;
-        if(may_reuse)
-        {
-            h->fact_valid = true;
-            h->fact_dt = dt;
-        }
-    }
-    for(int attempt = 0; attempt < 2; ++attempt)
-        {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            std::vector<std::pair<int, std::vector<int>>> groups;
-            rc = prepare_inaccurate_retry(h, true, dt, attempt, s0, nsteps, groups);
-            if(rc != PE_HIP_OK) return rc;
-            if(groups.empty()) break;
-            for(auto const& g: groups)
-            {
-                rc = run_m2_tr(h, dt, g.first, launches, &g.second);
-                if(rc != PE_HIP_OK) return rc;
-            }
-        }
+    rc = tr_run_steps(h, dt, nsteps, s0, launches);
+    if(rc != PE_HIP_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;
@@ -702,6 +831,228 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
         st->dominant_launches = split ? h->dominant_launches : launches;
     }
     return rc;
+}
+
+int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_control* c, pe_hip_tr_adaptive_stats* out)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(out) std::memset(out, 0, sizeof(*out));
+    if(!h->loaded || !c) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: no circuit or no control block");
+    auto const fin = [](double v) { return std::isfinite(v); };
+    if(!fin(t_stop) || !fin(c->dt_init) || !fin(c->dt_min) || !fin(c->dt_max) || !fin(c->lte_reltol) || !fin(c->lte_abstol_v) || !fin(c->lte_abstol_i) || !fin(c->trtol))
+        return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: non-finite argument");
+    if(!(c->dt_init > 0.0)) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: dt_init must be > 0");
+    if(c->n_breakpoints < 0 || (c->n_breakpoints > 0 && !c->breakpoints)) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: bad breakpoint list");
+    for(int k = 0; k < c->n_breakpoints; ++k)
+        if(!fin(c->breakpoints[k])) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: non-finite breakpoint");
+    if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: a host-stamp overlay keeps host state that a rejected step cannot roll back");
+    HIPCHK(h, hipSetDevice(h->device));
+    int const B = h->hc.batch;
+    std::vector<double> tb(static_cast<size_t>(B));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if(B) HIPCHK(h, hipMemcpy(tb.data(), h->V.t_now, tb.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for(int b = 1; b < B; ++b)
+        if(tb[static_cast<size_t>(b)] != tb[0]) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: the instances sit at different time points");
+    double t = B ? tb[0] : 0.0;
+    if(!(t_stop > t)) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: t_stop must lie after the current time");
+    double const dt_min = c->dt_min > 0.0 ? c->dt_min : c->dt_init * 1e-9;
+    double const dt_max = c->dt_max > 0.0 ? c->dt_max : (t_stop - t) / 50.0;
+    if(dt_min > dt_max) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: dt_min > dt_max");
+    bool const lte_on = !(c->lte_reltol < 0.0);
+    double const reltol = c->lte_reltol > 0.0 ? c->lte_reltol : 1e-3;
+    double const abstol_v = c->lte_abstol_v > 0.0 ? c->lte_abstol_v : 1e-6, abstol_i = c->lte_abstol_i > 0.0 ? c->lte_abstol_i : 1e-9;
+    double const trtol = c->trtol > 0.0 ? c->trtol : 7.0;
+    // ---- from here on the engine changes
+    ac_sweep_invalidate(h);
+    auto& A = h->tra;
+    A.log_dt.clear();
+    A.log_outcome.clear();
+    h->dominant_ms = 0.0;
+    h->dominant_launches = 0;
+    if(out) out->t_end = t;
+    if(h->hc.rows == 0 || B == 0) return PE_HIP_OK;
+    int rc = tr_adaptive_alloc(h);
+    if(rc != PE_HIP_OK) return rc;
+    // breakpoints after t, ascending; t_stop is the last one
+    std::vector<double> bps(c->breakpoints, c->breakpoints + c->n_breakpoints);
+    if(c->source_breakpoints) source_breakpoints(h, t, t_stop, bps);
+    bps.erase(std::remove_if(bps.begin(), bps.end(), [&](double v) { return !(v < t_stop); }), bps.end());
+    bps.push_back(t_stop);
+    std::sort(bps.begin(), bps.end());
+    constexpr double eps4 = 4.0 * 2.220446049250313e-16;
+    auto const reached = [&](double at, double bp) { return at >= bp || std::fabs(at - bp) <= eps4 * std::fabs(bp); };
+    size_t next_bp = 0;
+
+    std::vector<long long> s0, i0, s_now;
+    rc = snapshot_counters(h, s0, i0);
+    if(rc != PE_HIP_OK) return rc;
+    s_now = s0;
+    long long const analyses0 = h->n_symbolic;
+    bool const may_reuse = !h->hc.nonlinear && !h->opt.refactor_every_solve;
+    std::vector<int> const all(static_cast<size_t>(B), 1);
+    std::vector<int> status(static_cast<size_t>(B));
+    pe_hip_tr_adaptive_stats S{};
+    S.dt_smallest = INFINITY;
+    int launches = 0;
+    int final_rc = PE_HIP_OK;
+    bool failed_at_dt_min = false;
+    double dt = c->dt_init;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    auto const roll_back = [&]() -> int
+    {
+        // the state of the snapshot; the host side as pe_hip_checkpoint_load leaves it (what the step spent came with the LTE result)
+        HIPCHK(h, pe::launch_tr_state_copy(h->stream, A.restore));
+        h->fact_valid = false;
+        h->a_static.clear();
+        return PE_HIP_OK;
+    };
+    // (the loop in a function of its own: whichever way it ends, the statistics below are filled -- the log and t may have advanced)
+    auto const stepping = [&]() -> int
+    {
+        while(!reached(t, t_stop) && (c->max_steps <= 0 || static_cast<long long>(A.log_dt.size()) < c->max_steps))
+        {
+            while(next_bp + 1 < bps.size() && reached(t, bps[next_bp])) ++next_bp;
+            double const t_bp = bps[next_bp];
+            double const hs = std::min({dt, dt_max, t_bp - t});
+            if(!(hs > 0.0)) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_tr_adaptive: the step underflowed");
+            // snapshot, then one ordinary step that records nothing (the probes see it once it is accepted)
+            HIPCHK(h, pe::launch_tr_state_copy(h->stream, A.save));
+            rc = ensure_symbolic(h, true, hs);
+            if(rc != PE_HIP_OK) return rc;
+            HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(B) * sizeof(int), h->stream));
+            bool const armed = h->probe.armed;
+            h->probe.armed = false;
+            rc = tr_run_steps(h, hs, 1, s_now, launches);
+            h->probe.armed = armed;
+            if(rc != PE_HIP_OK) return rc;
+            if(!may_reuse) h->fact_valid = false;
+            // the test on the device, the decision from one small copy
+            bool const test = lte_on && A.n_pts >= 3;
+            double const t_new = t + hs;
+            pe::LteView L{};
+            L.hist = A.hist;
+            L.s2 = A.head;
+            L.s1 = (A.head + 2) % 3;
+            L.s0 = (A.head + 1) % 3;
+            L.t0 = A.t_pts[L.s0];
+            L.t1 = A.t_pts[L.s1];
+            L.t2 = A.t_pts[L.s2];
+            L.tn = t_new;
+            L.h = hs;
+            L.reltol = reltol;
+            L.abstol_v = abstol_v;
+            L.abstol_i = abstol_i;
+            L.trtol = trtol;
+            L.test = test ? 1 : 0;
+            L.q_each = A.q_each;
+            L.iters_now = h->V.n_iters;
+            L.iters_before = A.shadow_iters;
+            L.result = A.result;
+            HIPCHK(h, pe::launch_tr_lte(h->stream, h->V, L));
+            pe::LteResult res{};
+            HIPCHK(h, hipMemcpyAsync(&res, A.result, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            double const q = test ? pe::lte_value(res.q) : 0.0;
+            A.log_dt.push_back(hs);
+            S.dt_smallest = std::min(S.dt_smallest, hs);
+            S.dt_largest = std::max(S.dt_largest, hs);
+            bool const at_min = hs <= dt_min;
+            if(res.n_failed > 0 || res.n_nonfinite > 0)
+            {
+                A.log_outcome.push_back(2);
+                ++S.n_rejected_newton;
+                S.newton_iters_rejected += res.iters_spent;
+                if(at_min)
+                {
+                    // ends as pe_hip_analyze_tr does: the step rolled back, the failed instances keep their status
+                    HIPCHK(h, hipMemcpy(status.data(), h->V.status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
+                    if(res.n_failed == 0)
+                        for(auto& v: status) v = PE_HIP_ERR_NO_CONVERGENCE;  // (defensive: a non-finite candidate that passed for converged; the step's own finiteness flag fails it first, not reachable through the public calls)
+                    if(int const rrc = roll_back(); rrc != PE_HIP_OK) return rrc;
+                    HIPCHK(h, hipMemcpyAsync(h->V.status, status.data(), status.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+                    HIPCHK(h, hipStreamSynchronize(h->stream));
+                    failed_at_dt_min = true;
+                    break;
+                }
+                if(int const rrc = roll_back(); rrc != PE_HIP_OK) return rrc;
+                dt = std::max(hs / 8.0, dt_min);
+                continue;
+            }
+            if(test && !pe::lte_passes(q))
+            {
+                if(!at_min)
+                {
+                    A.log_outcome.push_back(1);
+                    ++S.n_rejected_lte;
+                    S.newton_iters_rejected += res.iters_spent;
+                    if(int const rrc = roll_back(); rrc != PE_HIP_OK) return rrc;
+                    double const f = q > 1.0 ? std::max(0.1, 0.9 * std::pow(q, -1.0 / 3.0)) : 0.1;  // (defensive: q is a NaN only with a NaN in the history, not reachable through the public calls -- the smallest factor)
+                    dt = std::max(hs * f, dt_min);
+                    continue;
+                }
+                ++S.n_at_dt_min;
+            }
+            // accepted
+            A.log_outcome.push_back(0);
+            ++S.n_accepted;
+            t = t_new;
+            for(auto& v: s_now) ++v;
+            if(armed)
+                if(int const prc = probe_record_step(h, all, t); prc != PE_HIP_OK) return prc;
+            bool const at_bp = next_bp + 1 < bps.size() && reached(t, t_bp);
+            if(at_bp) A.n_pts = 0;  // (the history restarts AT the breakpoint: the point pushed below is its first)
+            A.head = (A.head + 1) % 3;
+            HIPCHK(h, pe::launch_tr_history_push(h->stream, h->V, A.hist, A.head));
+            A.t_pts[A.head] = t;
+            A.n_pts = std::min(A.n_pts + 1, 4);
+            if(at_bp) dt = c->dt_init;
+            else if(test)
+                dt = hs * (q > 0.0 ? std::min(2.0, 0.9 * std::pow(q, -1.0 / 3.0)) : (q == 0.0 ? 2.0 : 1.0));  // (a NaN q accepted at dt_min: no growth)
+            else
+                dt = hs;
+            dt = std::max(dt, dt_min);
+        }
+        return PE_HIP_OK;
+    };
+    int const loop_rc = stepping();
+    S.n_analyses = static_cast<int>(h->n_symbolic - analyses0);
+    S.t_end = t;
+    if(A.log_dt.empty()) S.dt_smallest = 0.0;
+    S.run.n_launches = launches;
+    if(loop_rc != PE_HIP_OK)
+    {
+        A.n_pts = 0;  // (a step broken off half-way: the history no longer ends at the engine's state)
+        (void)hipStreamSynchronize(h->stream);
+        if(out) *out = S;
+        return loop_rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    final_rc = collect_stats(h, s0, i0, &S.run);
+    if(failed_at_dt_min && final_rc == PE_HIP_OK) final_rc = PE_HIP_ERR_NO_CONVERGENCE;
+    S.run.gpu_ms = ms;
+    S.run.n_launches = launches;
+    bool const split = h->dominant_launches > 0;
+    S.run.dominant_ms = split ? h->dominant_ms : ms;
+    S.run.dominant_launches = split ? h->dominant_launches : launches;
+    if(out) *out = S;
+    return final_rc;
+}
+
+int pe_hip_get_tr_step_log(pe_hip_engine* h, long long first, int capacity, double* dt, int* outcome, long long* n_total)
+{
+    if(!h || first < 0 || capacity < 0) return PE_HIP_ERR_ARG;
+    auto const& A = h->tra;
+    long long const n = static_cast<long long>(A.log_dt.size());
+    if(n_total) *n_total = n;
+    for(long long k = first; k < n && k - first < capacity; ++k)
+    {
+        if(dt) dt[k - first] = A.log_dt[static_cast<size_t>(k)];
+        if(outcome) outcome[k - first] = A.log_outcome[static_cast<size_t>(k)];
+    }
+    return PE_HIP_OK;
 }
 
 int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)

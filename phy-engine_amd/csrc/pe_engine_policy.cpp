@@ -617,6 +617,7 @@ namespace pe_eng PE_ENG_HIDDEN
         h->fact_valid = false;
         h->a_static.clear();
         h->analyze_ms = ms_since(t0);
+        ++h->n_symbolic;
         return PE_HIP_OK;
     }
 

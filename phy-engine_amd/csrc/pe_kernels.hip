@@ -24,6 +24,7 @@
 
 #include "pe_front.hpp"
 #include "pe_ac_sweep.hpp"
+#include "pe_lte.hpp"
 #include "pe_kernels.hpp"
 #include "pe_quad.hpp"
 #include "pe_top_plan.hpp"
@@ -1492,6 +1493,80 @@ namespace pe
     {
         if(V.batch <= 0) return hipSuccess;
         hipLaunchKernelGGL(k_probe_record, dim3(V.batch), dim3(64), 0, st, V, t);
+        return hipGetLastError();
+    }
+
+    // ---- variable-step transient (pe_lte.hpp, pe_engine_newton.cpp pe_hip_analyze_tr_adaptive): streaming kernels, no LDS
+    // q = max err / tol of the candidate against the history ring: blockIdx.y = instance, the workgroups of one instance share its rows;
+    // reduced per wavefront as integers (nothing drops a NaN), then one atomicMax per wavefront into the instance's slot and the batch's
+    __global__ void __launch_bounds__(256) k_tr_lte(DevView V, LteView L)
+    {
+        int const b = static_cast<int>(blockIdx.y);
+        int nonfinite = 0;
+        unsigned long long u = lte_partial(GridTeam{}, V, L, b, nonfinite);
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1)
+        {
+            unsigned long long const t = __shfl_xor(u, o);
+            u = t > u ? t : u;
+        }
+        bool const any_nonfinite = __ballot(nonfinite) != 0;
+        if((threadIdx.x & 63) == 0)
+        {
+            if(L.test)
+            {
+                atomicMax(L.q_each + b, u);
+                atomicMax(&L.result->q, u);
+            }
+            if(any_nonfinite) atomicAdd(&L.result->n_nonfinite, 1);
+            if(blockIdx.x == 0 && threadIdx.x == 0)
+            {
+                if(V.status[b] != 0) atomicAdd(&L.result->n_failed, 1);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&L.result->iters_spent), static_cast<unsigned long long>(L.iters_now[b] - L.iters_before[b]));
+            }
+        }
+    }
+    __global__ void __launch_bounds__(256) k_tr_history_push(DevView V, double* __restrict__ hist, int slot)
+    {
+        lte_history_push(GridTeam{}, V, hist, slot);
+    }
+    // snapshot / roll-back of the state of a step: blockIdx.y = part of the table, 16 bytes per lane and a 4-byte tail.  One launch instead
+    // of one stream-ordered copy per array: a small circuit's step is shorter than fourteen copy commands.
+    __global__ void __launch_bounds__(256) k_tr_state_copy(StateCopy S)
+    {
+        int const p = static_cast<int>(blockIdx.y);
+        unsigned long long const n = S.bytes[p], n16 = n / 16;
+        size_t const stride = static_cast<size_t>(gridDim.x) * blockDim.x, first = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+        uint4 const* s = static_cast<uint4 const*>(S.src[p]);
+        uint4* d = static_cast<uint4*>(S.dst[p]);
+        for(size_t i = first; i < n16; i += stride) d[i] = s[i];
+        unsigned const* s4 = static_cast<unsigned const*>(S.src[p]);
+        unsigned* d4 = static_cast<unsigned*>(S.dst[p]);
+        for(size_t i = n16 * 4 + first; i < n / 4; i += stride) d4[i] = s4[i];
+    }
+    hipError_t launch_tr_lte(hipStream_t st, DevView const& V, LteView const& L)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipError_t e = hipMemsetAsync(L.result, 0, sizeof(LteResult), st);
+        if(e == hipSuccess && L.test) e = hipMemsetAsync(L.q_each, 0, static_cast<size_t>(V.batch) * sizeof(unsigned long long), st);
+        if(e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_tr_lte, dim3(std::max(1, std::min(64, (V.rows + 255) / 256)), V.batch), dim3(256), 0, st, V, L);
+        return hipGetLastError();
+    }
+    hipError_t launch_tr_history_push(hipStream_t st, DevView const& V, double* hist, int slot)
+    {
+        size_t const n = static_cast<size_t>(V.batch) * V.rows;
+        if(n == 0) return hipSuccess;
+        hipLaunchKernelGGL(k_tr_history_push, dim3(static_cast<unsigned>(std::min<size_t>(4096, (n + 255) / 256))), dim3(256), 0, st, V, hist, slot);
+        return hipGetLastError();
+    }
+    hipError_t launch_tr_state_copy(hipStream_t st, StateCopy const& S)
+    {
+        if(S.n <= 0) return hipSuccess;
+        unsigned long long most = 0;
+        for(int p = 0; p < S.n; ++p) most = std::max(most, S.bytes[p]);
+        unsigned const g = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(2048, (most / 16 + 255) / 256)));
+        hipLaunchKernelGGL(k_tr_state_copy, dim3(g, S.n), dim3(256), 0, st, S);
         return hipGetLastError();
     }
 

@@ -63,4 +63,12 @@ namespace pe
     hipError_t launch_ac_residual_each(hipStream_t st, DevView const& V, AcSweepView const& S);
     hipError_t launch_ac_accumulate_each(hipStream_t st, DevView const& V, AcSweepView const& S, bool first);
     hipError_t launch_ac_sweep_gather(hipStream_t st, DevView const& V, AcSweepView const& S);
+    // variable-step transient (pe_lte.hpp): lte: q of the candidate V.x against the history ring + failed / non-finite instances into
+    // L.result (cleared first); history_push: V.x of every instance into ring slot `slot`; state_copy: every (dst, src, bytes) of the table
+    // (snapshot and roll-back of a step).  Builds without HIP: serial host definitions in pe_engine_newton.cpp.
+    struct LteView;
+    struct StateCopy;
+    hipError_t launch_tr_lte(hipStream_t st, DevView const& V, LteView const& L);
+    hipError_t launch_tr_history_push(hipStream_t st, DevView const& V, double* hist, int slot);
+    hipError_t launch_tr_state_copy(hipStream_t st, StateCopy const& S);
 }  // namespace pe

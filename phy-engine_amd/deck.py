@@ -450,6 +450,17 @@ def generators_tr() -> Deck:
     return d
 
 
+def pulse_rc() -> Deck:
+    """PULSE 0 / 5 V, 1 kHz, 1 us edges -> R 1k -> C 10n: two time scales (tau = 10 us against a 1 ms period), the variable-step
+    transient's second accuracy case."""
+    d = Deck()
+    d.n_nodes = 2
+    d.add("PULSE", (1, 0), 5.0, 0.0, 1e3, 0.5, 0.0, 1e-6, 1e-6)
+    d.add("R", (1, 2), 1000.0)
+    d.add("C", (2, 0), 1e-8)
+    return d
+
+
 def iac_rc() -> Deck:
     """IAC 1 mA / 1 kHz into R || C (TR); nothing in DC."""
     d = Deck()

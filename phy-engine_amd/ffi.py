@@ -31,6 +31,7 @@ EXPORTS = [
     "pe_hip_sweep_load_circuit", "pe_hip_sweep_reset", "pe_hip_sweep_operating_point", "pe_hip_sweep_run", "pe_hip_sweep_reduce", "pe_hip_sweep_get_solution",
     "pe_hip_sweep_get_instance_state", "pe_hip_set_probes", "pe_hip_arm_probes", "pe_hip_get_probe_samples", "pe_hip_get_measures",
     "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
+    "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
 ]
 # pe_hip_measure_kind
 MEAS_MIN, MEAS_MAX, MEAS_AVG, MEAS_RMS, MEAS_INTEG, MEAS_CROSS = 1, 2, 3, 4, 5, 6
@@ -139,6 +140,23 @@ class RunStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TrControl(C.Structure):
+    _fields_ = [("dt_init", C.c_double), ("dt_min", C.c_double), ("dt_max", C.c_double), ("lte_reltol", C.c_double), ("lte_abstol_v", C.c_double),
+                ("lte_abstol_i", C.c_double), ("trtol", C.c_double), ("max_steps", C.c_longlong), ("source_breakpoints", C.c_int),
+                ("n_breakpoints", C.c_int), ("breakpoints", C.POINTER(C.c_double))]
+
+
+class TrAdaptiveStats(C.Structure):
+    _fields_ = [("n_accepted", C.c_longlong), ("n_rejected_lte", C.c_longlong), ("n_rejected_newton", C.c_longlong), ("n_at_dt_min", C.c_longlong),
+                ("newton_iters_rejected", C.c_longlong), ("n_analyses", C.c_int), ("dt_smallest", C.c_double), ("dt_largest", C.c_double),
+                ("t_end", C.c_double), ("run", RunStats)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "run"}
+        d["run"] = self.run.asdict()
+        return d
+
+
 class AcSweepStats(C.Structure):
     _fields_ = [("n_points", C.c_int), ("n_passes", C.c_int), ("points_per_pass", C.c_int), ("n_analyses", C.c_int), ("n_refine_rounds", C.c_int),
                 ("n_fallback_points", C.c_int), ("gpu_ms", C.c_double)]
@@ -191,6 +209,8 @@ def lib():
         l.pe_hip_set_ac_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(AcSweepStats)]
         l.pe_hip_get_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_analyze_tr_adaptive.argtypes = [C.c_void_p, C.c_double, C.POINTER(TrControl), C.POINTER(TrAdaptiveStats)]
+        l.pe_hip_get_tr_step_log.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         _lib = l
     return _lib
 
@@ -371,6 +391,32 @@ class Engine(_Probes):
         d = st.asdict()
         d["rc"] = rc
         return d
+
+    def analyze_tr_adaptive(self, t_stop, dt_init, dt_min=0.0, dt_max=0.0, lte_reltol=0.0, lte_abstol_v=0.0, lte_abstol_i=0.0, trtol=0.0,
+                            max_steps=0, source_breakpoints=False, breakpoints=(), check=True):
+        """Variable-step transient up to the absolute time t_stop (pe_hip_analyze_tr_adaptive): the step follows the local truncation
+        error and is cut when Newton fails; 0 / omitted arguments take the defaults of include/pe_hip.h, a negative lte_reltol switches
+        the LTE test off.  Returns the statistics as a dict, the run statistics under 'run' and the return code under 'rc'."""
+        bp = np.ascontiguousarray(breakpoints, dtype=np.float64).reshape(-1)
+        c = TrControl(float(dt_init), float(dt_min), float(dt_max), float(lte_reltol), float(lte_abstol_v), float(lte_abstol_i), float(trtol),
+                      int(max_steps), 1 if source_breakpoints else 0, len(bp), _dp(bp) if len(bp) else None)
+        st = TrAdaptiveStats()
+        rc = lib().pe_hip_analyze_tr_adaptive(self._h, float(t_stop), C.byref(c), C.byref(st))
+        if check:
+            self._chk(rc)
+        d = st.asdict()
+        d["rc"] = rc
+        return d
+
+    def tr_step_log(self):
+        """(dt [n], outcome [n]) of every attempted step of the last adaptive call: 0 accepted, 1 rejected by the LTE test, 2 by Newton"""
+        n = C.c_longlong(0)
+        self._chk(lib().pe_hip_get_tr_step_log(self._h, 0, 0, None, None, C.byref(n)))
+        dt = np.empty(n.value)
+        oc = np.empty(n.value, dtype=np.int32)
+        if n.value:
+            self._chk(lib().pe_hip_get_tr_step_log(self._h, 0, int(n.value), _dp(dt), _ip(oc), C.byref(n)))
+        return dt, oc
 
     def analyze_dc(self, mode=MODE_DC, check=True):
         st = RunStats()

@@ -96,6 +96,13 @@ CASES["ac_linear_mix"] = (("ac_linear_mix", {}), "AC", 0.0, 0, 0.0, "", True)
 CASES["ac_nmos_amp"] = (("ac_nmos_amp", {}), "AC", 0.0, 0, 0.0, "", True)
 
 
+# fine-step references of the variable-step transient's accuracy tests (tests/test_tr_adaptive_emu.py): every 100th step of a run whose
+# step resolves the fastest feature throughout
+CASES["bridge_fine_tr"] = (("bridge_rectifier", {}), "TR", 1e-6, 40000, 1e-12, ",".join(str(i) for i in range(100, 40001, 100)), True)
+CASES["pulse_rc_fine_tr"] = (("pulse_rc", {}), "TR", 1e-7, 20000, 1e-12, ",".join(str(i) for i in range(100, 20001, 100)), True)
+NO_TRACE = ("bridge_fine_tr", "pulse_rc_fine_tr")   # (tens of thousands of steps: the per-step Newton counts are not kept, no test reads them)
+
+
 def tt_diode_deck():
     """test/0004.solver/pn_junction_tt_tr.cpp: VDC 0.7 + VAC 0.1 (omega*dt = pi/2) across a tt=1e-9 diode."""
     import math
@@ -130,6 +137,8 @@ def run_case(name):
         subprocess.run(cmd, check=True)
         meta = json.load(open(out + ".json"))
         meta["recipe"] = {"fn": fn, "kwargs": kw}
+        if name in NO_TRACE:
+            meta.pop("newton_iters", None)
         if name in R_OPEN:
             meta["r_open"] = R_OPEN[name]
         if name in AC_OMEGAS:
