@@ -364,6 +364,77 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
 /* phasors of the last sweep, in the CALLER's point order: re / im [n_points][count][n_kept_rows]; a failed point reads NaN */
 int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* re, double* im);
 
+/* ---- Small-signal noise analysis (.NOISE): the output noise spectral density of the circuit at its operating point, the share of every
+ * device in it, and the integrated noise over the swept band -- by the ADJOINT method: one solve of the transposed small-signal system per
+ * frequency point, whatever the number of sources.  With A the complex small-signal matrix of pe_hip_analyze_ac at omega and e the output
+ * selector, A^T y = e gives the transfer of a current injected between rows a and b to the output as y_b - y_a, so a white current source
+ * of density S_k there contributes S_k |y_b - y_a|^2.  The real-equivalent system solved is the transpose of [Ar -Ai; Ai Ar], which is
+ * that of A^H: A^H z = e has z = conj(y) for the real e, and |z_b - z_a| = |y_b - y_a|.
+ *   Output.  x[out_pos] - x[out_neg], x the small-signal solution (rows 0-based: node n is row n - 1, branch currents after the nodes);
+ *   -1 = none (ground).  out_pos == out_neg (both -1 included) is PE_HIP_ERR_ARG.  The result is a ONE-SIDED density in V^2/Hz (A^2/Hz when
+ *   the output is a branch row) at f = omega / 2 pi.
+ *   Temperature.  temp_k is the circuit temperature of the thermal sources; <= 0: 300.15 K, the models' default Temp of 27 C.  Constants as
+ *   the models use them: k = 1.380650524e-23, q = 1.6021765314e-19.
+ *   Sources.  White current sources, mutually uncorrelated, each between two rows, in this fixed order:
+ *     1. every resistor, in table order: S = 4 k T |g| between its nodes, g the conductance of its AC stamp;
+ *     2. every junction of the diode table, in table order (PN_junction; the four junctions of a full-bridge rectifier are four entries of
+ *        that table): shot noise S = 2 q |I_d| between anode and cathode;
+ *     3. every three-pin device, table by table in the order the tables were passed to pe_hip_load_circuit, each in table order: a
+ *        MOSFET one source S = (8/3) k T |gm| between D and S; a BJT two, base 2 q |I_b| between B and E (part 0), then collector
+ *        2 q |I_c| between C and E (part 1).
+ *   The bias currents are those that flow in the SOLVED LINEARISED NETWORK -- the last linearisation evaluated at the resident solution x:
+ *   I_d = geq V_d(x) + Ieq, I_b = geq V_j(x) + Ieq_be, I_c = gm V_j(x) + Ieq_c, gm that linearisation's -- not the model formula evaluated
+ *   again at x (the two differ at the level of the Newton tolerance; this one satisfies KCL with x).  Of a diode only the conduction
+ *   current counts: the diffusion-capacitance companion a transient stamp folds into the junction's conductance and current is taken out.
+ *   A device whose AC stamp is skipped (an unconnected pin) keeps its place with S = 0 and rows -1, -1 (a BJT: both parts).  Everything else is
+ *   noiseless: g_min, switch and relay contacts, controlled sources, op-amp, transformers, independent sources and generators.  There is
+ *   no flicker noise (the models have no KF / AF) and no input-referred noise (divide by |H|^2 from pe_hip_analyze_ac_sweep).
+ *   Operating point.  Like pe_hip_analyze_ac the call uses the last linearisation: run pe_hip_analyze_dc(PE_HIP_MODE_OP) first.  An
+ *   instance whose last analysis failed (status != 0 in pe_hip_get_instance_state) has no operating point: the call returns that status,
+ *   every point carries it and reads NaN.
+ *   Points.  The rules of pe_hip_analyze_ac_sweep: any order, duplicates and 0 allowed, the same bands (n_analyses counts them), the same
+ *   AC_SWEEP_POINTS knob and automatic pass size, gpu_ms measured the same way, results in the caller's order.  A point with a failing or
+ *   non-finite instance in its batch is retried ALONE: one pass of one point, under an analysis on its own values (counted in
+ *   n_retried_points, its analysis in n_analyses); if it fails again the point carries that status and reads NaN, the others stay
+ *   readable.  Returns PE_HIP_OK, or the first failing point's status.
+ *   Determinism.  The sum over the sources is formed on the device without floating-point atomics, in an order that depends on the number
+ *   of sources only: the densities and contributions of a point do not depend on the pass size, the batch or the pass it fell into.
+ *   They do depend on the other points of the call through the band: the pivot order of a band is made at its representative (first)
+ *   frequency, so a point reads the same bits in two calls only where it falls into bands with the same representative in both.
+ *   Integrated noise.  Trapezoidal rule in linear f over the distinct points sorted ascending, on the host from the stored densities;
+ *   NaN when any point failed.
+ *   The call has sweep state of its own (adjoint system, engines, buffers): a stored forward sweep stays readable, bit for bit.  The calls
+ *   that make a stored AC sweep unreadable make the stored noise result unreadable too (PE_HIP_ERR_ARG, "no noise analysis yet").
+ *   PE_HIP_ERR_ARG, engine unchanged: no circuit, n_points < 1, omegas or c NULL, a negative or non-finite omega, a row out of range,
+ *   out_pos == out_neg, a circuit with a host-stamp overlay (its models have no noise description).  There is no twin on the multi-device
+ *   pe_hip_sweep_* handle. */
+typedef struct pe_hip_noise_control {
+    int out_pos, out_neg;     /* rows of x; -1: ground */
+    double temp_k;            /* <= 0: 300.15 */
+    int keep_contributions;   /* 1: keep S_k |y_b - y_a|^2 of every source: n_points x batch x n_sources doubles, device and host */
+} pe_hip_noise_control;
+typedef struct pe_hip_noise_stats {
+    int n_points;             /* as passed */
+    int n_sources;            /* sources of the circuit */
+    int n_passes;             /* batched factor+solve passes, retries included */
+    int points_per_pass;      /* largest number of points put into one pass */
+    int n_analyses;           /* symbolic analyses: one per frequency band + one per retried point */
+    int n_refine_rounds;      /* correction solves, summed over passes */
+    int n_retried_points;     /* points that failed in their batch and were solved again alone */
+    double gpu_ms;            /* HIP-event time of the passes */
+} pe_hip_noise_stats;
+int pe_hip_analyze_noise(pe_hip_engine* h, int n_points, const double* omegas, const pe_hip_noise_control* c, int* point_status, pe_hip_noise_stats* stats);
+/* densities of the last call in the CALLER's point order: psd [n_points][count]; contrib NULL or [n_points][count][n_sources] (needs
+ * keep_contributions); a failed point reads NaN */
+int pe_hip_get_noise(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* psd, double* contrib);
+/* the source table of the resident circuit (no analysis needed): kind (pe_hip_kind), index of the device in its table, part (0; BJT
+ * collector: 1), the two rows (-1: ground); *n_sources receives the count, at most `capacity` entries are written; any pointer may be NULL */
+int pe_hip_get_noise_sources(pe_hip_engine* h, int capacity, int* kind, int* index, int* part, int* row_a, int* row_b, int* n_sources);
+/* current densities S_k of the last call, [count][n_sources], A^2/Hz; NaN after a call that was refused for a failed operating point */
+int pe_hip_get_noise_source_density(pe_hip_engine* h, int first_instance, int count, double* s);
+/* integrated output noise of the last call over its band, [count], V^2 (A^2) */
+int pe_hip_get_noise_integrated(pe_hip_engine* h, int first_instance, int count, double* v2);
+
 /* x = [node voltages ; branch currents], instance-major [count][rows] */
 int pe_hip_get_solution(pe_hip_engine* h, int first_instance, int count, double* x);
 int pe_hip_set_solution(pe_hip_engine* h, int first_instance, int count, const double* x);

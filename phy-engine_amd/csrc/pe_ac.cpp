@@ -17,7 +17,7 @@ namespace pe
         };
     }  // namespace
 
-    bool build_ac_circuit(HostCircuit const& hc, AcCircuit& out, OverlaySpec const* overlay)
+    bool build_ac_circuit(HostCircuit const& hc, AcCircuit& out, OverlaySpec const* overlay, AcAdjoint const* adjoint)
     {
         out = AcCircuit{};
         auto& ac = out.hc;
@@ -315,6 +315,16 @@ namespace pe
         }
         for(int nn = 0; nn < NN; ++nn) A_re(nn, nn, DV_GMIN, false, false);  // circuit.h:1107-1110
 
+        if(adjoint)
+        {
+            // the transposed real-equivalent system [Ar^T Ai^T; -Ai^T Ar^T] (that of A^H): every emitted cell moves to its mirror cell, in
+            // the order it was emitted, so a '=' and the explicit zeros it leaves clear the mirror cell exactly as they cleared the cell;
+            // the right-hand side is the output selector, real half only
+            for(auto& e: ea) std::swap(e.row, e.col);
+            eb.clear();
+            if(adjoint->out_pos >= 0) eb.push_back({adjoint->out_pos, 0, (DV_ONE << 1) | 0, false});
+            if(adjoint->out_neg >= 0) eb.push_back({adjoint->out_neg, 0, (DV_ONE << 1) | 1, false});
+        }
         ac.dv_len = DV_FIXED + static_cast<int>(out.slots.size());
         // ---- CSR pattern + contribution lists (src -1 = explicit zero written by a complex '=')
         std::int64_t const R = ac.rows;

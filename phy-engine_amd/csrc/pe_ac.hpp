@@ -39,8 +39,19 @@ namespace pe
         std::vector<AcSlot> slots;  // dv index DV_FIXED + i  <-  slots[i]
     };
 
-    // builds the real-equivalent AC circuit of `hc`
-    bool build_ac_circuit(HostCircuit const& hc, AcCircuit& out, OverlaySpec const* overlay = nullptr);
+    // the adjoint of the small-signal system (noise analysis, pe_noise.hpp): output = x[out_pos] - x[out_neg], rows of the complex system,
+    // -1 = none (ground)
+    struct AcAdjoint
+    {
+        int out_pos, out_neg;
+    };
+
+    // builds the real-equivalent AC circuit of `hc`.  With `adjoint` the same emitted cells are used with row and column swapped -- the
+    // transpose [Ar^T Ai^T; -Ai^T Ar^T] of [Ar -Ai; Ai Ar], which is the real-equivalent form of A^H -- and the right-hand-side lists hold
+    // the output selector (+DV_ONE at out_pos, -DV_ONE at out_neg, real half).  A^H z = e has z = conj(y) with A^T y = e for a real e, so
+    // |z_b - z_a| = |y_b - y_a|: the transfer magnitudes from a current between rows a, b to the output.  Slots and value vector are those
+    // of the forward system.
+    bool build_ac_circuit(HostCircuit const& hc, AcCircuit& out, OverlaySpec const* overlay = nullptr, AcAdjoint const* adjoint = nullptr);
 
     // main-engine state the AC values depend on, downloaded once per analyze_ac call
     struct AcOperatingPoint

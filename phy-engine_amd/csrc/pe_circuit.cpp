@@ -205,6 +205,7 @@ namespace pe
                     hc.error = "each device kind may appear in one table only";
                     return false;
                 }
+                if(t.kind >= PE_HIP_NMOS && t.kind <= PE_HIP_BJT_PNP && t.count > 0) hc.n3_tables.push_back(t.kind);
                 for(int i = 0; i < t.count; ++i)
                 {
                     bool connected = true;

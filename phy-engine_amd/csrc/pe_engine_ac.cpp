@@ -1,19 +1,22 @@
 // pe_engine_ac.cpp -- small-signal AC on the device: pe_hip_analyze_ac / pe_hip_get_solution_ac (the real-equivalent system of pe_ac.hpp
 // solved by a second engine, iterative refinement on the device) and pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep (a whole frequency
-// sweep as batches of that system on a third engine, pe_ac_sweep.hpp).
+// sweep as batches of that system on a third engine, pe_ac_sweep.hpp), and pe_hip_analyze_noise / pe_hip_get_noise* (the same sweep body
+// on the adjoint system, pe_noise.hpp).
 #include "pe_engine_internal.hpp"
+
+#include <functional>
 
 using namespace pe_eng;
 
 namespace
 {
-    // the real-equivalent AC system of the resident circuit and the second engine that solves it, built on first use
-    int ensure_ac_built(pe_hip_engine* h)
+    // the real-equivalent AC system of the resident circuit and the second engine that solves it, built on first use (A: h->ac, or with
+    // `adjoint` the transposed system of the noise analysis, h->noise.sys)
+    int ensure_ac_built(pe_hip_engine* h, pe_hip_engine::Ac& A, pe::AcAdjoint const* adjoint = nullptr)
     {
         auto& hc = h->hc;
-        auto& A = h->ac;
         if(A.built) return PE_HIP_OK;
-        if(!pe::build_ac_circuit(hc, A.circ, has_overlay(h) ? &h->overlay : nullptr)) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_ac: could not build the AC system");
+        if(!pe::build_ac_circuit(hc, A.circ, has_overlay(h) ? &h->overlay : nullptr, adjoint)) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_ac: could not build the AC system");
         if(pe_hip_create(h->device, &A.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_ac: " + std::string(pe_hip_last_error(nullptr)));
         A.eng->knobs = h->knobs;  // (the real-equivalent system is analysed under the same tuning knobs)
         // The right-hand side of the device copy comes from one value slot per row: the host evaluates the sources' lists
@@ -37,30 +40,29 @@ namespace
         A.sym_omega = -1.0;
         return PE_HIP_OK;
     }
+    int ensure_ac_built(pe_hip_engine* h) { return ensure_ac_built(h, h->ac); }
 
-    // ---- frequency-batched sweep (pe_hip_analyze_ac_sweep)
-    void sweep_engine_drop(pe_hip_engine* h)
+    // ---- frequency-batched sweep (pe_hip_analyze_ac_sweep, and on the adjoint system pe_hip_analyze_noise)
+    void sweep_engine_drop(pe_hip_engine::Ac::Sweep& W)
     {
-        auto& W = h->ac.sweep;
         if(W.eng) pe_hip_destroy(W.eng);  // (synchronises its stream first: nothing reads the buffers below any more)
         W.eng = nullptr;
         W.P = 0;
         W.pass_pool.release();
     }
 
-    // the third engine: the AC system with batch (circuit batch) x P, constructed like h->ac.eng, and the buffers sized by that batch
-    int sweep_engine_build(pe_hip_engine* h, int P)
+    // the third engine: the AC system with batch (circuit batch) x P, constructed like A.eng, and the buffers sized by that batch
+    int sweep_engine_build(pe_hip_engine* h, pe_hip_engine::Ac& A, int P, std::string const& name)
     {
-        auto& A = h->ac;
         auto& W = A.sweep;
-        sweep_engine_drop(h);
-        if(pe_hip_create(h->device, &W.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_ac_sweep: " + std::string(pe_hip_last_error(nullptr)));
+        sweep_engine_drop(W);
+        if(pe_hip_create(h->device, &W.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, name + ": " + std::string(pe_hip_last_error(nullptr)));
         W.eng->knobs = h->knobs;
         W.eng->opt = h->opt;
         W.eng->hc = A.circ.hc;
         W.eng->hc.batch = h->hc.batch * P;
         int const rc = finish_load(W.eng);
-        if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac_sweep: " + W.eng->err);
+        if(rc != PE_HIP_OK) return fail(h, rc, name + ": " + W.eng->err);
         size_t const Q = static_cast<size_t>(h->hc.batch) * P, R2 = static_cast<size_t>(A.circ.hc.rows);
         double* omega{};
         int* point{};
@@ -95,12 +97,21 @@ namespace pe_eng
 {
     void ac_sweep_drop(pe_hip_engine* h)
     {
-        sweep_engine_drop(h);
         auto& W = h->ac.sweep;
+        sweep_engine_drop(W);
         W.circ_pool.release();
         W.res_pool.release();
         if(W.d_keep) (void)hipFree(W.d_keep);
         W = pe_hip_engine::Ac::Sweep{};
+        // the noise analysis: its adjoint system with both engines, the source table, the result
+        auto& Z = h->noise;
+        sweep_engine_drop(Z.sys.sweep);
+        if(Z.sys.eng) pe_hip_destroy(Z.sys.eng);
+        Z.sys.sweep.circ_pool.release();
+        Z.src_pool.release();
+        Z.pass_pool.release();
+        Z.res_pool.release();
+        Z = pe_hip_engine::Noise{};
     }
 }  // namespace pe_eng
 
@@ -262,6 +273,288 @@ int pe_hip_set_ac_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows)
     return PE_HIP_OK;
 }
 
+}  // extern "C"
+
+namespace
+{
+    bool numerical(int rc) { return rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE; }
+
+    // What the forward sweep and the noise call do differently around the shared body below.
+    struct SweepHooks
+    {
+        std::string name;                                       // prefix of the error messages
+        std::function<int(int P)> prepare;                      // the batched engine stands with P points per pass: result buffers on the device
+        std::function<int(pe_hip_engine* E)> epilogue;          // end of a pass, after refinement: gather the kept rows / accumulate the noise
+        std::function<int(std::vector<char>& failed)> collect;  // after the passes: the one device-to-host copy; marks the points that are not finite
+        std::function<int(int i)> single;                       // forward sweep: failed point i on the single-point path (sets its status)
+        std::function<int(int i, bool& finite)> reread;         // noise (no `single`): point i was retried alone in a pass of its own -- read it back
+    };
+
+    // The body of a frequency sweep on the real-equivalent system A (forward: h->ac, adjoint: h->noise.sys): base vectors, bands,
+    // representative values, pass size, the batched engine, the passes with their refinement, and the bookkeeping of the points that
+    // failed in their batch.  pst: status per point (all PE_HIP_OK on entry).  S.n_fallback_points counts the failed points handled at the
+    // end, by K.single or by a retry pass.
+    int sweep_body(pe_hip_engine* h, pe_hip_engine::Ac& A, int n_points, double const* omegas, std::vector<int>& pst, pe_hip_ac_sweep_stats& S,
+                   SweepHooks const& K)
+    {
+        auto& hc = h->hc;
+        auto& W = A.sweep;
+        int const B = hc.batch, N = hc.rows;
+        auto const& ah = A.circ.hc;
+        int const rhs0 = A.rhs0;
+        if(rhs0 < pe::DV_FIXED + static_cast<int>(A.circ.slots.size())) return fail(h, PE_HIP_ERR_INTERNAL, K.name + ": value vector shorter than its slots");
+
+        // ---- one base vector per circuit instance (the values at omega = 1) + how every value follows omega: uploaded once per sweep
+        std::vector<double> base(static_cast<size_t>(B) * rhs0, 0.0);
+        std::vector<int> scale(static_cast<size_t>(rhs0), pe::AC_CONST);
+        {
+            pe::AcOperatingPoint op;
+            op.d_geq.resize(static_cast<size_t>(B) * hc.nD());
+            op.dv.resize(static_cast<size_t>(B) * hc.dv_len);
+            op.rl_engaged.resize(static_cast<size_t>(B) * hc.nRl());
+            if(!op.d_geq.empty()) HIPCHK(h, hipMemcpy(op.d_geq.data(), h->V.d_geq, op.d_geq.size() * sizeof(double), hipMemcpyDeviceToHost));
+            if(!op.dv.empty()) HIPCHK(h, hipMemcpy(op.dv.data(), h->V.dv, op.dv.size() * sizeof(double), hipMemcpyDeviceToHost));
+            if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
+            std::vector<double> one(static_cast<size_t>(ah.dv_len), 0.0);
+            for(int b = 0; b < B; ++b)
+            {
+                pe::fill_ac_values(hc, A.circ, op, b, 1.0, h->opt.g_min, r_open_of(h), one.data());
+                std::copy(one.begin(), one.begin() + rhs0, base.begin() + static_cast<size_t>(b) * rhs0);
+            }
+            for(size_t i = 0; i < A.circ.slots.size(); ++i)
+                switch(A.circ.slots[i].kind)
+                {
+                    case pe::AcSlot::C_W:
+                    case pe::AcSlot::KL_W11:
+                    case pe::AcSlot::KL_W12:
+                    case pe::AcSlot::KL_W22: scale[pe::DV_FIXED + i] = pe::AC_OMEGA; break;
+                    case pe::AcSlot::L_W:
+                    case pe::AcSlot::D_WC: scale[pe::DV_FIXED + i] = pe::AC_OMEGA_ZERO; break;
+                    default: break;
+                }
+        }
+        if(!W.V.base)
+        {
+            double* d_base{};
+            int* d_scale{};
+            HIPCHK(h, W.circ_pool.alloc(d_base, base.size(), false));
+            HIPCHK(h, W.circ_pool.alloc(d_scale, scale.size(), false));
+            HIPCHK(h, W.circ_pool.upload(W.V.b_ptr0, A.b_ptr0));
+            HIPCHK(h, W.circ_pool.upload(W.V.b_src0, A.b_src0));
+            W.V.scale = d_scale;
+            W.V.base = d_base;
+            W.V.rhs0 = rhs0;
+            W.V.n_inst = B;
+            W.V.n_half = N;
+        }
+        HIPCHK(h, hipMemcpy(const_cast<double*>(W.V.base), base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.scale), scale.data(), scale.size() * sizeof(int), hipMemcpyHostToDevice));
+
+        // ---- frequency bands: the static pivot order is matched on representative values at one frequency and holds for a decade above it
+        // (the rule of pe_hip_analyze_ac).  Points ascending; omega == 0 a band of its own; a band starts at its first omega w0 and takes every
+        // point with omega <= 10 w0.
+        std::vector<int> order(static_cast<size_t>(n_points));
+        for(int i = 0; i < n_points; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return omegas[a] < omegas[b]; });
+        std::vector<std::pair<int, int>> bands;  // [first, last) in `order`
+        for(int i = 0; i < n_points;)
+        {
+            double const w0 = omegas[order[i]];
+            int j = i + 1;
+            while(j < n_points && (w0 == 0.0 ? omegas[order[j]] == 0.0 : omegas[order[j]] <= 10.0 * w0)) ++j;
+            bands.emplace_back(i, j);
+            i = j;
+        }
+        int largest_band = 0;
+        for(auto const& bd: bands) largest_band = std::max(largest_band, bd.second - bd.first);
+
+        // instance 0's matrix values at omega: what a band's symbolic analysis is matched on (analyse_here of the single-point path)
+        auto representative = [&](double omega, std::vector<double>& out)
+        {
+            int const nnz = static_cast<int>(ah.ci.size());
+            out.assign(static_cast<size_t>(nnz), 0.0);
+            for(int s = 0; s < nnz; ++s)
+            {
+                double acc = 0.0;
+                for(int e = ah.a_ptr[s]; e < ah.a_ptr[s + 1]; ++e)
+                {
+                    int const i = ah.a_src[e] >> 1;
+                    double const v = pe::ac_sweep_value(base[i], scale[i], omega);
+                    acc = (ah.a_src[e] & 1) ? acc - v : acc + v;
+                }
+                out[s] = acc;
+            }
+        };
+
+        // ---- points per pass: the knob, else what fits the memory budget; never more than the largest band needs
+        int const knob_p = knob(h, "AC_SWEEP_POINTS", 0);
+        long long cap = knob_p > 0 ? knob_p : 0;
+        if(cap == 0)
+        {
+            if(W.bytes_per_instance == 0)
+            {
+                // bytes of one instance of the AC system incl. its factor storage, from the single-point engine.  When that has no symbolic
+                // analysis yet one is made on a band's values and forgotten again: pe_hip_analyze_ac then analyses as it always did.  A band
+                // whose values cannot be analysed (a singular system at its omega) says nothing about the others: the next band is tried, and
+                // when none can be analysed the sweep runs one point per pass -- its bands then fail one by one into the single-point path.
+                bool const had = A.eng->sym_class >= 0;
+                int src = had ? PE_HIP_OK : PE_HIP_ERR_SINGULAR;
+                for(size_t k = 0; !had && k < bands.size() && src != PE_HIP_OK; ++k)
+                {
+                    representative(omegas[order[bands[k].first]], A.eng->sym_values_override);
+                    A.eng->sym_class = -1;
+                    src = ensure_symbolic(A.eng, false, 0.0);
+                    if(src != PE_HIP_OK && !numerical(src))
+                    {
+                        A.eng->sym_class = -1;
+                        A.sym_omega = -1.0;
+                        return fail(h, src, K.name + " (sizing): " + A.eng->err);
+                    }
+                }
+                pe_hip_info info{};
+                int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng, &info) : PE_HIP_OK;
+                if(!had)
+                {
+                    A.eng->sym_class = -1;
+                    A.sym_omega = -1.0;
+                }
+                if(rc != PE_HIP_OK) return fail(h, rc, K.name + " (sizing): " + A.eng->err);
+                if(src == PE_HIP_OK) W.bytes_per_instance = std::max<long long>(1, info.bytes_per_instance);
+            }
+            cap = W.bytes_per_instance > 0 ? sweep_memory_budget() / (W.bytes_per_instance * static_cast<long long>(B)) : 1;
+        }
+        cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
+        int const P = static_cast<int>(std::min<long long>(cap, largest_band));
+        if(!W.eng || W.P != P)
+            if(int const rc = sweep_engine_build(h, A, P, K.name); rc != PE_HIP_OK) return rc;
+        S.points_per_pass = 0;
+
+        // ---- result buffers on the device
+        if(int const rc = K.prepare(P); rc != PE_HIP_OK) return rc;
+
+        pe_hip_engine* const E = W.eng;
+        hipStream_t const es = E->stream;
+        int const Q = B * P;
+        std::vector<char> failed(static_cast<size_t>(n_points), 0);
+        std::vector<int> inst_status(static_cast<size_t>(Q)), now(static_cast<size_t>(Q));
+        std::vector<double> omega_h(static_cast<size_t>(P)), worst_h;
+        std::vector<int> point_h(static_cast<size_t>(P));
+        // one batched factor + solve of all Q instances from the device's value vectors; a numerical failure of some instances is theirs alone
+        auto solve = [&]() -> int
+        {
+            HIPCHK(h, hipMemset(E->V.status, 0, static_cast<size_t>(Q) * sizeof(int)));
+            int const rc = pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
+            if(rc != PE_HIP_OK && !numerical(rc)) return fail(h, rc, K.name + ": " + E->err);
+            if(rc != PE_HIP_OK)
+            {
+                // (a status that no instance carries was raised before anything was launched: nothing of this solve is usable)
+                HIPCHK(h, hipMemcpy(now.data(), E->V.status, static_cast<size_t>(Q) * sizeof(int), hipMemcpyDeviceToHost));
+                bool const none = std::all_of(now.begin(), now.end(), [](int s) { return s == 0; });
+                for(int q = 0; q < Q; ++q)
+                    if(inst_status[q] == 0) inst_status[q] = none ? rc : now[q];
+            }
+            return PE_HIP_OK;
+        };
+        // one pass: the n <= P points pts[0 .. n) (the caller's indices) as instances of the engine, under its current symbolic analysis
+        auto run_pass = [&](int const* pts, int n) -> int
+        {
+            for(int p = 0; p < P; ++p)
+            {
+                point_h[p] = p < n ? pts[p] : -1;
+                omega_h[p] = omegas[pts[std::min(p, n - 1)]];
+            }
+            ++S.n_passes;
+            S.points_per_pass = std::max(S.points_per_pass, n);
+            HIPCHK(h, hipMemcpy(const_cast<double*>(W.V.omega), omega_h.data(), static_cast<size_t>(P) * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.point), point_h.data(), static_cast<size_t>(P) * sizeof(int), hipMemcpyHostToDevice));
+            std::fill(inst_status.begin(), inst_status.end(), 0);
+            HIPCHK(h, hipEventRecord(h->ev0, es));
+            HIPCHK(h, pe::launch_ac_sweep_fill(es, E->V, W.V));
+            if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+            HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
+            // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds), decided per instance: the host reads one int per round
+            int above = 0;
+            for(int round = 0; round < 3; ++round)
+            {
+                HIPCHK(h, pe::launch_ac_residual_each(es, E->V, W.V));
+                HIPCHK(h, hipMemcpyAsync(&above, W.V.n_above, sizeof(int), hipMemcpyDeviceToHost, es));
+                HIPCHK(h, hipStreamSynchronize(es));
+                if(above == 0) break;
+                if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+                HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, false));
+                ++S.n_refine_rounds;
+            }
+            if(int const rc = K.epilogue(E); rc != PE_HIP_OK) return rc;
+            HIPCHK(h, hipEventRecord(h->ev1, es));
+            HIPCHK(h, hipStreamSynchronize(es));
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            S.gpu_ms += ms;
+            if(above != 0)
+            {
+                // the rounds ran out with instances still above the threshold: fine when their error is merely not at rounding level yet (the
+                // single-point path stops there too), a failure when it is not a number
+                worst_h.resize(static_cast<size_t>(Q));
+                HIPCHK(h, hipMemcpy(worst_h.data(), W.V.worst, static_cast<size_t>(Q) * sizeof(double), hipMemcpyDeviceToHost));
+                for(int q = 0; q < Q; ++q)
+                    if(!std::isfinite(worst_h[q]) && inst_status[q] == 0) inst_status[q] = PE_HIP_ERR_INACCURATE;
+            }
+            for(int p = 0; p < n; ++p)
+                for(int b = 0; b < B; ++b)
+                    if(inst_status[static_cast<size_t>(b) * P + p] != 0) failed[point_h[p]] = 1;
+            return PE_HIP_OK;
+        };
+        for(auto const& bd: bands)
+        {
+            // the band's symbolic analysis, on the host, before its passes (so that gpu_ms is theirs alone).  Values that cannot be analysed
+            // (a structurally or numerically singular system at w0, e.g. a node held by capacitors only at omega = 0) fail the BAND, not the
+            // sweep: nothing is launched for it and each of its points goes to the single-point path, which reports that point's own status.
+            representative(omegas[order[bd.first]], E->sym_values_override);
+            E->sym_class = -1;
+            ++S.n_analyses;
+            if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK)
+            {
+                if(!numerical(rc)) return fail(h, rc, K.name + ": " + E->err);
+                for(int k = bd.first; k < bd.second; ++k) failed[order[k]] = 1;
+                continue;
+            }
+            for(int first = bd.first; first < bd.second; first += P)
+                if(int const rc = run_pass(&order[first], std::min(P, bd.second - first)); rc != PE_HIP_OK) return rc;
+        }
+        // ---- one copy of the results of every point, then the points that failed in their batch: the single-point path (forward sweep), or
+        // alone in one pass of one point under an analysis on that point's own values (noise)
+        if(int const rc = K.collect(failed); rc != PE_HIP_OK) return rc;
+        for(int i = 0; i < n_points; ++i)
+        {
+            if(!failed[i]) continue;
+            ++S.n_fallback_points;
+            if(K.single)
+            {
+                if(int const rc = K.single(i); rc != PE_HIP_OK) return rc;
+                continue;
+            }
+            representative(omegas[i], E->sym_values_override);
+            E->sym_class = -1;
+            ++S.n_analyses;
+            if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK)
+            {
+                if(!numerical(rc)) return fail(h, rc, K.name + ": " + E->err);
+                pst[i] = rc;
+                continue;
+            }
+            failed[i] = 0;
+            if(int const rc = run_pass(&i, 1); rc != PE_HIP_OK) return rc;
+            for(int b = 0; b < B && pst[i] == PE_HIP_OK; ++b) pst[i] = inst_status[static_cast<size_t>(b) * P];
+            bool finite = true;
+            if(int const rc = K.reread(i, finite); rc != PE_HIP_OK) return rc;
+            if(pst[i] == PE_HIP_OK && !finite) pst[i] = PE_HIP_ERR_INACCURATE;
+        }
+        return PE_HIP_OK;
+    }
+}  // namespace
+
+extern "C" {
+
 /* A whole frequency sweep as batches of the real-equivalent system: the points of a pass are extra instances of a third engine
  * (h->ac.sweep.eng), the value vectors are made on the device from one base vector per circuit instance (k_ac_sweep_fill), refinement runs
  * per instance, the kept rows are gathered on the device and copied back once.  Bands, passes and the fallback: include/pe_hip.h. */
@@ -301,7 +594,6 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
     // point's status; anything else (a HIP error) ends the call.
     auto single = [&](int i) -> int
     {
-        ++S.n_fallback_points;
         int const rc = pe_hip_analyze_ac(h, omegas[i], nullptr);
         pst[i] = rc;
         double* re = &W.res[static_cast<size_t>(i) * B * K];
@@ -320,274 +612,73 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
         }
         std::fill(re, re + static_cast<size_t>(B) * K, std::nan(""));
         std::fill(im, im + static_cast<size_t>(B) * K, std::nan(""));
-        return (rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE) ? PE_HIP_OK : rc;
+        return numerical(rc) ? PE_HIP_OK : rc;
     };
-    auto numerical = [](int rc) { return rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE; };
     if(has_overlay(h))
     {
         // host-stamped models: their values come from callbacks per omega -- every point takes the single-point path
         for(int i = 0; i < n_points; ++i)
+        {
+            ++S.n_fallback_points;
             if(int const rc = single(i); rc != PE_HIP_OK) return rc;
+        }
         return finish();
     }
     if(int const brc = ensure_ac_built(h); brc != PE_HIP_OK) return brc;
-    auto const& ah = A.circ.hc;
-    int const R2 = ah.rows, rhs0 = A.rhs0;
-    if(rhs0 < pe::DV_FIXED + static_cast<int>(A.circ.slots.size())) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_ac_sweep: value vector shorter than its slots");
-
-    // ---- one base vector per circuit instance (the values at omega = 1) + how every value follows omega: uploaded once per sweep
-    std::vector<double> base(static_cast<size_t>(B) * rhs0, 0.0);
-    std::vector<int> scale(static_cast<size_t>(rhs0), pe::AC_CONST);
+    SweepHooks hooks;
+    hooks.name = "analyze_ac_sweep";
+    // result buffer and kept rows on the device
+    hooks.prepare = [&](int) -> int
     {
-        pe::AcOperatingPoint op;
-        op.d_geq.resize(static_cast<size_t>(B) * hc.nD());
-        op.dv.resize(static_cast<size_t>(B) * hc.dv_len);
-        op.rl_engaged.resize(static_cast<size_t>(B) * hc.nRl());
-        if(!op.d_geq.empty()) HIPCHK(h, hipMemcpy(op.d_geq.data(), h->V.d_geq, op.d_geq.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if(!op.dv.empty()) HIPCHK(h, hipMemcpy(op.dv.data(), h->V.dv, op.dv.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
-        std::vector<double> one(static_cast<size_t>(ah.dv_len), 0.0);
-        for(int b = 0; b < B; ++b)
+        if(W.res_len != plane || !W.V.res_re)
         {
-            pe::fill_ac_values(hc, A.circ, op, b, 1.0, h->opt.g_min, r_open_of(h), one.data());
-            std::copy(one.begin(), one.begin() + rhs0, base.begin() + static_cast<size_t>(b) * rhs0);
+            W.res_pool.release();
+            W.V.res_re = W.V.res_im = nullptr;
+            W.res_len = 0;
+            HIPCHK(h, W.res_pool.alloc(W.V.res_re, plane, false));
+            HIPCHK(h, W.res_pool.alloc(W.V.res_im, plane, false));
+            W.res_len = plane;
         }
-        for(size_t i = 0; i < A.circ.slots.size(); ++i)
-            switch(A.circ.slots[i].kind)
+        if(!W.rows_on_device)
+        {
+            // (a buffer of its own, reused while it is large enough: a caller alternating row selections allocates nothing)
+            W.V.keep = nullptr;
+            if(W.rows.size() > W.keep_cap)
             {
-                case pe::AcSlot::C_W:
-                case pe::AcSlot::KL_W11:
-                case pe::AcSlot::KL_W12:
-                case pe::AcSlot::KL_W22: scale[pe::DV_FIXED + i] = pe::AC_OMEGA; break;
-                case pe::AcSlot::L_W:
-                case pe::AcSlot::D_WC: scale[pe::DV_FIXED + i] = pe::AC_OMEGA_ZERO; break;
-                default: break;
+                if(W.d_keep) (void)hipFree(W.d_keep);
+                W.d_keep = nullptr;
+                W.keep_cap = 0;
+                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&W.d_keep), W.rows.size() * sizeof(int)));
+                W.keep_cap = W.rows.size();
             }
-    }
-    if(!W.V.base)
-    {
-        double* d_base{};
-        int* d_scale{};
-        HIPCHK(h, W.circ_pool.alloc(d_base, base.size(), false));
-        HIPCHK(h, W.circ_pool.alloc(d_scale, scale.size(), false));
-        HIPCHK(h, W.circ_pool.upload(W.V.b_ptr0, A.b_ptr0));
-        HIPCHK(h, W.circ_pool.upload(W.V.b_src0, A.b_src0));
-        W.V.scale = d_scale;
-        W.V.base = d_base;
-        W.V.rhs0 = rhs0;
-        W.V.n_inst = B;
-        W.V.n_half = N;
-    }
-    HIPCHK(h, hipMemcpy(const_cast<double*>(W.V.base), base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.scale), scale.data(), scale.size() * sizeof(int), hipMemcpyHostToDevice));
-
-    // ---- frequency bands: the static pivot order is matched on representative values at one frequency and holds for a decade above it
-    // (the rule of pe_hip_analyze_ac).  Points ascending; omega == 0 a band of its own; a band starts at its first omega w0 and takes every
-    // point with omega <= 10 w0.
-    std::vector<int> order(static_cast<size_t>(n_points));
-    for(int i = 0; i < n_points; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return omegas[a] < omegas[b]; });
-    std::vector<std::pair<int, int>> bands;  // [first, last) in `order`
-    for(int i = 0; i < n_points;)
-    {
-        double const w0 = omegas[order[i]];
-        int j = i + 1;
-        while(j < n_points && (w0 == 0.0 ? omegas[order[j]] == 0.0 : omegas[order[j]] <= 10.0 * w0)) ++j;
-        bands.emplace_back(i, j);
-        i = j;
-    }
-    int largest_band = 0;
-    for(auto const& bd: bands) largest_band = std::max(largest_band, bd.second - bd.first);
-
-    // instance 0's matrix values at omega: what a band's symbolic analysis is matched on (analyse_here of the single-point path)
-    auto representative = [&](double omega, std::vector<double>& out)
-    {
-        int const nnz = static_cast<int>(ah.ci.size());
-        out.assign(static_cast<size_t>(nnz), 0.0);
-        for(int s = 0; s < nnz; ++s)
-        {
-            double acc = 0.0;
-            for(int e = ah.a_ptr[s]; e < ah.a_ptr[s + 1]; ++e)
+            if(!W.rows.empty())
             {
-                int const i = ah.a_src[e] >> 1;
-                double const v = pe::ac_sweep_value(base[i], scale[i], omega);
-                acc = (ah.a_src[e] & 1) ? acc - v : acc + v;
+                HIPCHK(h, hipMemcpy(W.d_keep, W.rows.data(), W.rows.size() * sizeof(int), hipMemcpyHostToDevice));
+                W.V.keep = W.d_keep;
             }
-            out[s] = acc;
+            W.rows_on_device = true;
         }
-    };
-
-    // ---- points per pass: the knob, else what fits the memory budget; never more than the largest band needs
-    int const knob_p = knob(h, "AC_SWEEP_POINTS", 0);
-    long long cap = knob_p > 0 ? knob_p : 0;
-    if(cap == 0)
-    {
-        if(W.bytes_per_instance == 0)
-        {
-            // bytes of one instance of the AC system incl. its factor storage, from the single-point engine.  When that has no symbolic
-            // analysis yet one is made on a band's values and forgotten again: pe_hip_analyze_ac then analyses as it always did.  A band
-            // whose values cannot be analysed (a singular system at its omega) says nothing about the others: the next band is tried, and
-            // when none can be analysed the sweep runs one point per pass -- its bands then fail one by one into the single-point path.
-            bool const had = A.eng->sym_class >= 0;
-            int src = had ? PE_HIP_OK : PE_HIP_ERR_SINGULAR;
-            for(size_t k = 0; !had && k < bands.size() && src != PE_HIP_OK; ++k)
-            {
-                representative(omegas[order[bands[k].first]], A.eng->sym_values_override);
-                A.eng->sym_class = -1;
-                src = ensure_symbolic(A.eng, false, 0.0);
-                if(src != PE_HIP_OK && !numerical(src))
-                {
-                    A.eng->sym_class = -1;
-                    A.sym_omega = -1.0;
-                    return fail(h, src, "analyze_ac_sweep (sizing): " + A.eng->err);
-                }
-            }
-            pe_hip_info info{};
-            int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng, &info) : PE_HIP_OK;
-            if(!had)
-            {
-                A.eng->sym_class = -1;
-                A.sym_omega = -1.0;
-            }
-            if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac_sweep (sizing): " + A.eng->err);
-            if(src == PE_HIP_OK) W.bytes_per_instance = std::max<long long>(1, info.bytes_per_instance);
-        }
-        cap = W.bytes_per_instance > 0 ? sweep_memory_budget() / (W.bytes_per_instance * static_cast<long long>(B)) : 1;
-    }
-    cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
-    int const P = static_cast<int>(std::min<long long>(cap, largest_band));
-    if(!W.eng || W.P != P)
-        if(int const rc = sweep_engine_build(h, P); rc != PE_HIP_OK) return rc;
-    S.points_per_pass = 0;
-
-    // ---- result buffer and kept rows on the device
-    if(W.res_len != plane || !W.V.res_re)
-    {
-        W.res_pool.release();
-        W.V.res_re = W.V.res_im = nullptr;
-        W.res_len = 0;
-        HIPCHK(h, W.res_pool.alloc(W.V.res_re, plane, false));
-        HIPCHK(h, W.res_pool.alloc(W.V.res_im, plane, false));
-        W.res_len = plane;
-    }
-    if(!W.rows_on_device)
-    {
-        // (a buffer of its own, reused while it is large enough: a caller alternating row selections allocates nothing)
-        W.V.keep = nullptr;
-        if(W.rows.size() > W.keep_cap)
-        {
-            if(W.d_keep) (void)hipFree(W.d_keep);
-            W.d_keep = nullptr;
-            W.keep_cap = 0;
-            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&W.d_keep), W.rows.size() * sizeof(int)));
-            W.keep_cap = W.rows.size();
-        }
-        if(!W.rows.empty())
-        {
-            HIPCHK(h, hipMemcpy(W.d_keep, W.rows.data(), W.rows.size() * sizeof(int), hipMemcpyHostToDevice));
-            W.V.keep = W.d_keep;
-        }
-        W.rows_on_device = true;
-    }
-    W.V.n_keep = K;
-
-    pe_hip_engine* const E = W.eng;
-    hipStream_t const es = E->stream;
-    int const Q = B * P;
-    std::vector<char> failed(static_cast<size_t>(n_points), 0);
-    std::vector<int> inst_status(static_cast<size_t>(Q)), now(static_cast<size_t>(Q));
-    std::vector<double> omega_h(static_cast<size_t>(P)), worst_h;
-    std::vector<int> point_h(static_cast<size_t>(P));
-    // one batched factor + solve of all Q instances from the device's value vectors; a numerical failure of some instances is theirs alone
-    auto solve = [&]() -> int
-    {
-        HIPCHK(h, hipMemset(E->V.status, 0, static_cast<size_t>(Q) * sizeof(int)));
-        int const rc = pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
-        if(rc != PE_HIP_OK && !numerical(rc)) return fail(h, rc, "analyze_ac_sweep: " + E->err);
-        if(rc != PE_HIP_OK)
-        {
-            // (a status that no instance carries was raised before anything was launched: nothing of this solve is usable)
-            HIPCHK(h, hipMemcpy(now.data(), E->V.status, static_cast<size_t>(Q) * sizeof(int), hipMemcpyDeviceToHost));
-            bool const none = std::all_of(now.begin(), now.end(), [](int s) { return s == 0; });
-            for(int q = 0; q < Q; ++q)
-                if(inst_status[q] == 0) inst_status[q] = none ? rc : now[q];
-        }
+        W.V.n_keep = K;
         return PE_HIP_OK;
     };
-    for(auto const& bd: bands)
+    hooks.epilogue = [&](pe_hip_engine* E) -> int
     {
-        // the band's symbolic analysis, on the host, before its passes (so that gpu_ms is theirs alone).  Values that cannot be analysed
-        // (a structurally or numerically singular system at w0, e.g. a node held by capacitors only at omega = 0) fail the BAND, not the
-        // sweep: nothing is launched for it and each of its points goes to the single-point path, which reports that point's own status.
-        representative(omegas[order[bd.first]], E->sym_values_override);
-        E->sym_class = -1;
-        ++S.n_analyses;
-        if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK)
-        {
-            if(!numerical(rc)) return fail(h, rc, "analyze_ac_sweep: " + E->err);
-            for(int k = bd.first; k < bd.second; ++k) failed[order[k]] = 1;
-            continue;
-        }
-        for(int first = bd.first; first < bd.second; first += P)
-        {
-            int const n = std::min(P, bd.second - first);
-            for(int p = 0; p < P; ++p)
-            {
-                point_h[p] = p < n ? order[first + p] : -1;
-                omega_h[p] = omegas[order[first + std::min(p, n - 1)]];
-            }
-            ++S.n_passes;
-            S.points_per_pass = std::max(S.points_per_pass, n);
-            HIPCHK(h, hipMemcpy(const_cast<double*>(W.V.omega), omega_h.data(), static_cast<size_t>(P) * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.point), point_h.data(), static_cast<size_t>(P) * sizeof(int), hipMemcpyHostToDevice));
-            std::fill(inst_status.begin(), inst_status.end(), 0);
-            HIPCHK(h, hipEventRecord(h->ev0, es));
-            HIPCHK(h, pe::launch_ac_sweep_fill(es, E->V, W.V));
-            if(int const rc = solve(); rc != PE_HIP_OK) return rc;
-            HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
-            // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds), decided per instance: the host reads one int per round
-            int above = 0;
-            for(int round = 0; round < 3; ++round)
-            {
-                HIPCHK(h, pe::launch_ac_residual_each(es, E->V, W.V));
-                HIPCHK(h, hipMemcpyAsync(&above, W.V.n_above, sizeof(int), hipMemcpyDeviceToHost, es));
-                HIPCHK(h, hipStreamSynchronize(es));
-                if(above == 0) break;
-                if(int const rc = solve(); rc != PE_HIP_OK) return rc;
-                HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, false));
-                ++S.n_refine_rounds;
-            }
-            HIPCHK(h, pe::launch_ac_sweep_gather(es, E->V, W.V));
-            HIPCHK(h, hipEventRecord(h->ev1, es));
-            HIPCHK(h, hipStreamSynchronize(es));
-            float ms = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            S.gpu_ms += ms;
-            if(above != 0)
-            {
-                // the rounds ran out with instances still above the threshold: fine when their error is merely not at rounding level yet (the
-                // single-point path stops there too), a failure when it is not a number
-                worst_h.resize(static_cast<size_t>(Q));
-                HIPCHK(h, hipMemcpy(worst_h.data(), W.V.worst, static_cast<size_t>(Q) * sizeof(double), hipMemcpyDeviceToHost));
-                for(int q = 0; q < Q; ++q)
-                    if(!std::isfinite(worst_h[q]) && inst_status[q] == 0) inst_status[q] = PE_HIP_ERR_INACCURATE;
-            }
-            for(int p = 0; p < n; ++p)
-                for(int b = 0; b < B; ++b)
-                    if(inst_status[static_cast<size_t>(b) * P + p] != 0) failed[point_h[p]] = 1;
-        }
-    }
-    // ---- one copy of the kept rows of every point, then the single-point path for the points that failed in their batch
-    HIPCHK(h, hipMemcpy(W.res.data(), W.V.res_re, plane * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(W.res.data() + plane, W.V.res_im, plane * sizeof(double), hipMemcpyDeviceToHost));
-    size_t const per_point = static_cast<size_t>(B) * K;
-    for(int i = 0; i < n_points; ++i)
+        HIPCHK(h, pe::launch_ac_sweep_gather(E->stream, E->V, W.V));
+        return PE_HIP_OK;
+    };
+    // one copy of the kept rows of every point
+    hooks.collect = [&](std::vector<char>& failed) -> int
     {
-        for(size_t k = 0; k < per_point && !failed[i]; ++k)
-            if(!std::isfinite(W.res[i * per_point + k]) || !std::isfinite(W.res[plane + i * per_point + k])) failed[i] = 1;
-        if(failed[i])
-            if(int const rc = single(i); rc != PE_HIP_OK) return rc;
-    }
+        HIPCHK(h, hipMemcpy(W.res.data(), W.V.res_re, plane * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(W.res.data() + plane, W.V.res_im, plane * sizeof(double), hipMemcpyDeviceToHost));
+        size_t const per_point = static_cast<size_t>(B) * K;
+        for(int i = 0; i < n_points; ++i)
+            for(size_t k = 0; k < per_point && !failed[i]; ++k)
+                if(!std::isfinite(W.res[i * per_point + k]) || !std::isfinite(W.res[plane + i * per_point + k])) failed[i] = 1;
+        return PE_HIP_OK;
+    };
+    hooks.single = single;
+    if(int const rc = sweep_body(h, A, n_points, omegas, pst, S, hooks); rc != PE_HIP_OK) return rc;
     return finish();
 }
 
@@ -606,6 +697,350 @@ int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
         std::memcpy(re + dst, &W.res[src], static_cast<size_t>(count) * K * sizeof(double));
         std::memcpy(im + dst, &W.res[plane + src], static_cast<size_t>(count) * K * sizeof(double));
     }
+    return PE_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace
+{
+    static_assert(pe::NOISE_KIND_BJT_NPN == PE_HIP_BJT_NPN, "pe_noise.hpp names the kind without including the C header");
+
+    // the source table of the resident circuit, in the definition order of include/pe_hip.h (host only)
+    void noise_table_build(pe_hip_engine* h)
+    {
+        auto& Z = h->noise;
+        if(Z.table_built) return;
+        auto const& hc = h->hc;
+        Z.src.clear();
+        Z.kind.clear();
+        Z.index.clear();
+        Z.part.clear();
+        auto add = [&](int type, int idx, int a, int b, int kind, int index, int part)
+        {
+            Z.src.push_back({type, idx, a, b});
+            Z.kind.push_back(kind);
+            Z.index.push_back(index);
+            Z.part.push_back(part);
+        };
+        for(size_t i = 0; i < hc.map_r.size(); ++i)
+        {
+            int const c = hc.map_r[i];
+            if(c < 0) add(pe::NOISE_NONE, 0, -1, -1, PE_HIP_R, static_cast<int>(i), 0);
+            else
+                add(pe::NOISE_R, c, hc.r_a[c], hc.r_b[c], PE_HIP_R, static_cast<int>(i), 0);
+        }
+        for(size_t i = 0; i < hc.map_d.size(); ++i)
+        {
+            int const c = hc.map_d[i];
+            if(c < 0) add(pe::NOISE_NONE, 0, -1, -1, PE_HIP_DIODE, static_cast<int>(i), 0);
+            else
+                add(pe::NOISE_DIODE, c, hc.d_a[c], hc.d_c[c], PE_HIP_DIODE, static_cast<int>(i), 0);
+        }
+        // the three-pin tables as the caller passed them, each in table order: the order n3 was filled in, with the devices that have an
+        // unconnected pin (no n3 entry, no stamp) in their place as sources of density 0
+        for(int const kind : hc.n3_tables)
+        {
+            bool const mos = kind == PE_HIP_NMOS || kind == PE_HIP_PMOS;
+            auto const& map = hc.map_gen[static_cast<size_t>(kind)];
+            for(size_t p = 0; p < map.size(); ++p)
+            {
+                int const index = static_cast<int>(p);
+                if(map[p] < 0)
+                {
+                    add(pe::NOISE_NONE, 0, -1, -1, kind, index, 0);
+                    if(!mos) add(pe::NOISE_NONE, 0, -1, -1, kind, index, 1);
+                    continue;
+                }
+                int const j = hc.gen[static_cast<size_t>(map[p])].aux;
+                int const* n = &hc.n3_n[3 * static_cast<size_t>(j)];
+                if(mos) add(pe::NOISE_MOS, j, n[0], n[2], kind, index, 0);  // D - S
+                else
+                {
+                    add(pe::NOISE_BJT_B, j, n[0], n[2], kind, index, 0);  // B - E
+                    add(pe::NOISE_BJT_C, j, n[1], n[2], kind, index, 1);  // C - E
+                }
+            }
+        }
+        Z.table_built = true;
+        Z.table_on_device = false;
+    }
+
+    // right-hand-side lists of the adjoint system for an output pair: what build_ac_circuit makes of it (a new pair changes only these)
+    void noise_selector_lists(int rows2, int out_pos, int out_neg, std::vector<int>& b_ptr, std::vector<int>& b_src)
+    {
+        b_ptr.assign(static_cast<size_t>(rows2) + 1, 0);
+        b_src.clear();
+        for(int r = 0; r < rows2; ++r)
+        {
+            if(r == out_pos) b_src.push_back((pe::DV_ONE << 1) | 0);
+            if(r == out_neg) b_src.push_back((pe::DV_ONE << 1) | 1);
+            b_ptr[static_cast<size_t>(r) + 1] = static_cast<int>(b_src.size());
+        }
+    }
+}  // namespace
+
+extern "C" {
+
+/* Output noise density by the adjoint method: one solve of the transposed small-signal system per frequency point -- the sweep body of
+ * pe_hip_analyze_ac_sweep on the adjoint system with state of its own (h->noise) --, the sources' densities from the resident operating
+ * point (k_noise_sources), their reduction per (instance, point) on the device (k_noise_accumulate).  Definitions: include/pe_hip.h. */
+int pe_hip_analyze_noise(pe_hip_engine* h, int n_points, const double* omegas, const pe_hip_noise_control* ctl, int* point_status, pe_hip_noise_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(n_points < 1 || !omegas || !ctl) return fail(h, PE_HIP_ERR_ARG, "analyze_noise: n_points < 1, no omegas or no control");
+    for(int i = 0; i < n_points; ++i)
+        if(!std::isfinite(omegas[i]) || omegas[i] < 0.0) return fail(h, PE_HIP_ERR_ARG, "analyze_noise: negative or non-finite omega");
+    auto& hc = h->hc;
+    int const B = hc.batch, N = hc.rows;
+    int const out_pos = ctl->out_pos, out_neg = ctl->out_neg;
+    if(out_pos < -1 || out_pos >= N || out_neg < -1 || out_neg >= N) return fail(h, PE_HIP_ERR_ARG, "analyze_noise: output row out of range");
+    if(out_pos == out_neg) return fail(h, PE_HIP_ERR_ARG, "analyze_noise: the output needs two different rows (-1: ground)");
+    if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_noise: host-stamped overlay models have no noise description");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto& Z = h->noise;
+    auto& A = Z.sys;
+    auto& W = A.sweep;
+    Z.valid = false;
+    bool const keep = ctl->keep_contributions != 0;
+
+    // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
+    {
+        std::vector<int> inst(static_cast<size_t>(B), 0);
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+        for(int b = 0; b < B; ++b)
+        {
+            if(inst[static_cast<size_t>(b)] == PE_HIP_OK) continue;
+            noise_table_build(h);
+            Z.res.assign(static_cast<size_t>(n_points) * B * (1 + (keep ? Z.src.size() : 0)), std::nan(""));
+            Z.integrated.assign(static_cast<size_t>(B), std::nan(""));
+            Z.n_points = n_points;
+            Z.batch = B;
+            Z.kept = keep;
+            Z.have_density = false;  // (k_noise_sources has not run: the density getter reads NaN like the points)
+            Z.valid = true;
+            if(point_status) std::fill(point_status, point_status + n_points, inst[static_cast<size_t>(b)]);
+            if(stats)
+            {
+                stats->n_points = n_points;
+                stats->n_sources = static_cast<int>(Z.src.size());
+            }
+            return fail(h, inst[static_cast<size_t>(b)], "analyze_noise: instance " + std::to_string(b) + " has no operating point (its last analysis failed)");
+        }
+    }
+
+    // ---- the adjoint system for this output pair
+    pe::AcAdjoint const adj{out_pos, out_neg};
+    if(!A.built)
+    {
+        if(int const rc = ensure_ac_built(h, A, &adj); rc != PE_HIP_OK) return rc;
+    }
+    else if(!Z.have_pair || Z.out_pos != out_pos || Z.out_neg != out_neg)
+    {
+        noise_selector_lists(A.circ.hc.rows, out_pos, out_neg, A.b_ptr0, A.b_src0);
+        W.circ_pool.release();  // (base vectors, scale flags and the lists: uploaded again by the sweep body)
+        W.V.base = nullptr;
+        W.V.scale = nullptr;
+        W.V.b_ptr0 = W.V.b_src0 = nullptr;
+    }
+    Z.have_pair = true;
+    Z.out_pos = out_pos;
+    Z.out_neg = out_neg;
+
+    // ---- the sources: table once per circuit, densities once per call from the resident operating point
+    noise_table_build(h);
+    int const n_src = static_cast<int>(Z.src.size());
+    if(!Z.table_on_device)
+    {
+        Z.src_pool.release();
+        HIPCHK(h, Z.src_pool.upload(Z.V.src, Z.src));
+        HIPCHK(h, Z.src_pool.alloc(Z.V.rows, static_cast<size_t>(n_src)));
+        HIPCHK(h, Z.src_pool.alloc(Z.V.S, static_cast<size_t>(B) * n_src));
+        Z.table_on_device = true;
+    }
+    Z.V.n_src = n_src;
+    Z.V.n_chunks = std::max(1, (n_src + pe::NOISE_CHUNK - 1) / pe::NOISE_CHUNK);
+    Z.V.n_inst = B;
+    Z.V.n_half = N;
+    Z.V.temp_k = ctl->temp_k > 0.0 ? ctl->temp_k : pe::NOISE_TEMP_DEFAULT;
+    HIPCHK(h, pe::launch_noise_sources(h->stream, h->V, Z.V));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the passes run on the adjoint engine's stream)
+
+    // ---- result: densities, then the contributions when they are kept; one buffer, one copy back
+    size_t const n_psd = static_cast<size_t>(n_points) * B;
+    size_t const total = n_psd + (keep ? n_psd * static_cast<size_t>(n_src) : 0);
+    Z.res.assign(total, std::nan(""));
+    Z.integrated.assign(static_cast<size_t>(B), std::nan(""));
+    pe_hip_ac_sweep_stats S{};
+    S.n_points = n_points;
+    std::vector<int> pst(static_cast<size_t>(n_points), PE_HIP_OK);
+
+    SweepHooks hooks;
+    hooks.name = "analyze_noise";
+    hooks.prepare = [&](int P) -> int
+    {
+        if(Z.res_len != total || !Z.d_res)
+        {
+            Z.res_pool.release();
+            Z.d_res = nullptr;
+            Z.res_len = 0;
+            HIPCHK(h, Z.res_pool.alloc(Z.d_res, total, false));
+            Z.res_len = total;
+        }
+        HIPCHK(h, hipMemset(Z.d_res, 0xff, total * sizeof(double)));  // (all ones: a NaN -- a point no pass wrote reads NaN)
+        size_t const need = static_cast<size_t>(B) * P * Z.V.n_chunks;
+        if(Z.partial_len != need || !Z.V.partial)
+        {
+            Z.pass_pool.release();
+            Z.V.partial = nullptr;
+            Z.partial_len = 0;
+            HIPCHK(h, Z.pass_pool.alloc(Z.V.partial, need));
+            Z.partial_len = need;
+        }
+        Z.V.P = P;
+        Z.V.xacc = W.V.xacc;
+        Z.V.point = W.V.point;
+        Z.V.psd = Z.d_res;
+        Z.V.contrib = keep ? Z.d_res + n_psd : nullptr;
+        return PE_HIP_OK;
+    };
+    hooks.epilogue = [&](pe_hip_engine* E) -> int
+    {
+        HIPCHK(h, pe::launch_noise_accumulate(E->stream, E->V, Z.V));
+        return PE_HIP_OK;
+    };
+    hooks.collect = [&](std::vector<char>& failed) -> int
+    {
+        HIPCHK(h, hipMemcpy(Z.res.data(), Z.d_res, total * sizeof(double), hipMemcpyDeviceToHost));
+        for(int i = 0; i < n_points; ++i)
+            for(int b = 0; b < B && !failed[i]; ++b)
+                if(!std::isfinite(Z.res[static_cast<size_t>(i) * B + b])) failed[i] = 1;
+        return PE_HIP_OK;
+    };
+    hooks.reread = [&](int i, bool& finite) -> int
+    {
+        size_t const o = static_cast<size_t>(i) * B;
+        HIPCHK(h, hipMemcpy(&Z.res[o], Z.d_res + o, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
+        if(keep && n_src > 0)
+            HIPCHK(h, hipMemcpy(&Z.res[n_psd + o * n_src], Z.d_res + n_psd + o * n_src, static_cast<size_t>(B) * n_src * sizeof(double), hipMemcpyDeviceToHost));
+        finite = true;
+        for(int b = 0; b < B; ++b) finite = finite && std::isfinite(Z.res[o + b]);
+        return PE_HIP_OK;
+    };
+    if(int const rc = sweep_body(h, A, n_points, omegas, pst, S, hooks); rc != PE_HIP_OK) return rc;
+
+    // a failed point reads NaN
+    for(int i = 0; i < n_points; ++i)
+    {
+        if(pst[i] == PE_HIP_OK) continue;
+        size_t const o = static_cast<size_t>(i) * B;
+        std::fill(Z.res.begin() + o, Z.res.begin() + o + B, std::nan(""));
+        if(keep) std::fill(Z.res.begin() + n_psd + o * n_src, Z.res.begin() + n_psd + (o + B) * n_src, std::nan(""));
+    }
+    // ---- integrated noise: trapezoidal rule in linear f = omega / 2 pi over the distinct points, ascending, on the host in that fixed order
+    {
+        std::vector<int> order(static_cast<size_t>(n_points));
+        for(int i = 0; i < n_points; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return omegas[a] < omegas[b]; });
+        bool const any_failed = std::any_of(pst.begin(), pst.end(), [](int s) { return s != PE_HIP_OK; });
+        constexpr double two_pi = 6.283185307179586476925286766559;
+        for(int b = 0; b < B; ++b)
+        {
+            double acc = 0.0;
+            int prev = order[0];
+            for(int k = 1; k < n_points; ++k)
+            {
+                int const i = order[k];
+                if(omegas[i] == omegas[prev]) continue;
+                acc += (omegas[i] / two_pi - omegas[prev] / two_pi) * (Z.res[static_cast<size_t>(i) * B + b] + Z.res[static_cast<size_t>(prev) * B + b]) / 2.0;
+                prev = i;
+            }
+            Z.integrated[static_cast<size_t>(b)] = any_failed ? std::nan("") : acc;
+        }
+    }
+    Z.n_points = n_points;
+    Z.batch = B;
+    Z.kept = keep;
+    Z.have_density = true;
+    Z.valid = true;
+    if(point_status) std::copy(pst.begin(), pst.end(), point_status);
+    if(stats)
+    {
+        stats->n_points = n_points;
+        stats->n_sources = n_src;
+        stats->n_passes = S.n_passes;
+        stats->points_per_pass = S.points_per_pass;
+        stats->n_analyses = S.n_analyses;
+        stats->n_refine_rounds = S.n_refine_rounds;
+        stats->n_retried_points = S.n_fallback_points;
+        stats->gpu_ms = S.gpu_ms;
+    }
+    for(int i = 0; i < n_points; ++i)
+        if(pst[i] != PE_HIP_OK) return fail(h, pst[i], "analyze_noise: point " + std::to_string(i) + " failed");
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_noise(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* psd, double* contrib)
+{
+    if(!h || !h->loaded || !psd) return PE_HIP_ERR_ARG;
+    auto const& Z = h->noise;
+    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_noise: no noise analysis yet");
+    if(first_point < 0 || n_points < 0 || first_point > Z.n_points - n_points || first_instance < 0 || count < 0 || first_instance > Z.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_noise: points or instances out of range");
+    if(contrib && !Z.kept) return fail(h, PE_HIP_ERR_ARG, "get_noise: the contributions were not kept (pe_hip_noise_control.keep_contributions)");
+    size_t const n_src = Z.src.size(), n_psd = static_cast<size_t>(Z.n_points) * Z.batch;
+    for(int i = 0; i < n_points && count > 0; ++i)
+    {
+        size_t const src = static_cast<size_t>(first_point + i) * Z.batch + first_instance, dst = static_cast<size_t>(i) * count;
+        std::memcpy(psd + dst, &Z.res[src], static_cast<size_t>(count) * sizeof(double));
+        if(contrib && n_src > 0) std::memcpy(contrib + dst * n_src, &Z.res[n_psd + src * n_src], static_cast<size_t>(count) * n_src * sizeof(double));
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_noise_sources(pe_hip_engine* h, int capacity, int* kind, int* index, int* part, int* row_a, int* row_b, int* n_sources)
+{
+    if(!h || !h->loaded || capacity < 0) return PE_HIP_ERR_ARG;
+    noise_table_build(h);
+    auto const& Z = h->noise;
+    int const n = static_cast<int>(Z.src.size());
+    if(n_sources) *n_sources = n;
+    for(int k = 0; k < std::min(n, capacity); ++k)
+    {
+        if(kind) kind[k] = Z.kind[static_cast<size_t>(k)];
+        if(index) index[k] = Z.index[static_cast<size_t>(k)];
+        if(part) part[k] = Z.part[static_cast<size_t>(k)];
+        if(row_a) row_a[k] = Z.src[static_cast<size_t>(k)].a;
+        if(row_b) row_b[k] = Z.src[static_cast<size_t>(k)].b;
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_noise_source_density(pe_hip_engine* h, int first_instance, int count, double* s)
+{
+    if(!h || !h->loaded || !s) return PE_HIP_ERR_ARG;
+    auto const& Z = h->noise;
+    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_noise_source_density: no noise analysis yet");
+    if(first_instance < 0 || count < 0 || first_instance > Z.batch - count) return fail(h, PE_HIP_ERR_ARG, "get_noise_source_density: instances out of range");
+    size_t const n_src = Z.src.size();
+    if(!Z.have_density) std::fill(s, s + static_cast<size_t>(count) * n_src, std::nan(""));
+    else if(count > 0 && n_src > 0)
+    {
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemcpy(s, Z.V.S + static_cast<size_t>(first_instance) * n_src, static_cast<size_t>(count) * n_src * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_noise_integrated(pe_hip_engine* h, int first_instance, int count, double* v2)
+{
+    if(!h || !h->loaded || !v2) return PE_HIP_ERR_ARG;
+    auto const& Z = h->noise;
+    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_noise_integrated: no noise analysis yet");
+    if(first_instance < 0 || count < 0 || first_instance > Z.batch - count) return fail(h, PE_HIP_ERR_ARG, "get_noise_integrated: instances out of range");
+    std::copy(Z.integrated.begin() + first_instance, Z.integrated.begin() + first_instance + count, v2);
     return PE_HIP_OK;
 }
 
@@ -647,6 +1082,27 @@ namespace pe
     hipError_t launch_ac_sweep_gather(hipStream_t, DevView const& V, AcSweepView const& S)
     {
         for(int q = 0; q < V.batch; ++q) ac_sweep_gather(SweepHostTeam{}, V, S, q);
+        return hipSuccess;
+    }
+    // ... and the noise launchers with the text of pe_noise.hpp (one thread: every chunk is summed in ascending order)
+    hipError_t launch_noise_sources(hipStream_t, DevView const& V, NoiseView const& Z)
+    {
+        for(int b = 0; b < V.batch; ++b) noise_sources(SweepHostTeam{}, V, Z, b);
+        return hipSuccess;
+    }
+    hipError_t launch_noise_accumulate(hipStream_t, DevView const& V, NoiseView const& Z)
+    {
+        for(int q = 0; q < V.batch; ++q)
+        {
+            for(int c = 0; c < Z.n_chunks; ++c)
+            {
+                double const sum = noise_accumulate_chunk(SweepHostTeam{}, Z, V.rows, q, c);
+                if(Z.n_chunks > 1) Z.partial[static_cast<long long>(q) * Z.n_chunks + c] = sum;
+                else if(double* dst = noise_slot_psd(Z, q))
+                    *dst = sum;
+            }
+            if(Z.n_chunks > 1) noise_finish(Z, q);
+        }
         return hipSuccess;
     }
 }  // namespace pe

@@ -5,7 +5,7 @@
 //   pe_engine_policy.cpp      launch geometry by batch size, symbolic analysis + its upload (the PHY_ENGINE_HIP_* knobs live here)
 //   pe_engine_newton.cpp      host-driven Newton / transient loops of the split schedule, residual safety net, pe_hip_analyze_tr / _dc
 //   pe_engine_checkpoint.cpp  pe_hip_checkpoint_*
-//   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep
+//   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep, pe_hip_analyze_noise / pe_hip_get_noise*
 //   pe_engine_seam.cpp        pe_hip_solve_csr_complex (the complex twin of the solver seam)
 #pragma once
 // (the helpers below are shared between the engine's translation units only: not exported from libpe_hip.so)
@@ -29,6 +29,7 @@
 #include "pe_device.hpp"
 #include "pe_kernels.hpp"
 #include "pe_lte.hpp"
+#include "pe_noise.hpp"
 #include "pe_symbolic.hpp"
 
 #include <map>
@@ -202,6 +203,31 @@ struct pe_hip_engine
             std::vector<double> res;          // [2][n_points][batch][n_keep]: real parts, then imaginary parts
         } sweep;
     } ac;
+    // noise analysis (pe_hip_analyze_noise, pe_noise.hpp): the ADJOINT real-equivalent system with sweep state of its own -- its AcCircuit,
+    // its single-point engine (only the automatic pass size is measured on it), its batched engine and pass buffers -- so that a stored
+    // forward sweep is not disturbed; the source table of the circuit, the densities of the last call and its result
+    struct Noise
+    {
+        Ac sys;
+        bool have_pair{};
+        int out_pos{-1}, out_neg{-1};     // the output pair the right-hand-side lists of `sys` select
+        bool table_built{}, table_on_device{};
+        std::vector<pe::NoiseSource> src; // definition order: resistors, junctions, three-pin devices
+        std::vector<int> kind, index, part;
+        Pool src_pool;                    // sized by the circuit: source table, row pairs, densities
+        Pool pass_pool;                   // sized by batch x P x chunks: chunk sums
+        size_t partial_len{};
+        Pool res_pool;                    // sized by the call: [psd | contributions]
+        size_t res_len{};
+        double* d_res{};
+        pe::NoiseView V{};
+        bool valid{};                     // `res` is the noise of the current circuit at its current operating point
+        bool kept{};                      // ... with contributions
+        bool have_density{};              // V.S holds the densities of that call (not after a call refused for a failed operating point)
+        int n_points{}, batch{};
+        std::vector<double> res;          // [n_points][batch] densities, then [n_points][batch][n_src] contributions when kept
+        std::vector<double> integrated;   // [batch]
+    } noise;
     std::vector<double> sym_values_override;  // representative |A| values for the row matching (AC engine)
 
     // solve_csr_real seam (separate small state)
@@ -297,8 +323,12 @@ namespace pe_eng PE_ENG_HIDDEN
     // pe_engine_newton.cpp: variable-step transient
     void tr_adaptive_drop(pe_hip_engine* h);  // shadow state, history ring and step log gone (pe_hip_load_circuit)
     // pe_engine_ac.cpp: the stored AC sweep
-    void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy)
-    inline void ac_sweep_invalidate(pe_hip_engine* h) { h->ac.sweep.valid = false; }  // whatever moves the operating point or the circuit
+    void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy); the noise state too
+    inline void ac_sweep_invalidate(pe_hip_engine* h)  // whatever moves the operating point or the circuit: the stored sweep and the stored noise result
+    {
+        h->ac.sweep.valid = false;
+        h->noise.valid = false;
+    }
     // pe_engine_newton.cpp
     bool has_overlay(pe_hip_engine const* h);
     int overlay_call(pe_hip_engine* h, int event, int mode, double t, double dt, int b = 0);

@@ -24,6 +24,7 @@
 
 #include "pe_front.hpp"
 #include "pe_ac_sweep.hpp"
+#include "pe_noise.hpp"
 #include "pe_lte.hpp"
 #include "pe_kernels.hpp"
 #include "pe_quad.hpp"
@@ -1668,6 +1669,59 @@ namespace pe
     {
         if(V.batch <= 0 || S.n_keep <= 0) return hipSuccess;
         hipLaunchKernelGGL(k_ac_sweep_gather, dim3(sweep_grid(S.n_keep), V.batch), dim3(256), 0, st, V, S);
+        return hipGetLastError();
+    }
+
+    // ---- noise analysis (pe_noise.hpp, pe_engine_ac.cpp pe_hip_analyze_noise)
+    // densities of every source of circuit instance blockIdx.y from the main engine's resident operating point (once per call)
+    __global__ void __launch_bounds__(256) k_noise_sources(DevView V, NoiseView Z)
+    {
+        noise_sources(GridTeam{}, V, Z, static_cast<int>(blockIdx.y));
+    }
+    struct NoiseBlockTeam  // one workgroup owns one chunk of sources of one instance
+    {
+        __device__ __forceinline__ int tid() const { return static_cast<int>(threadIdx.x); }
+        __device__ __forceinline__ int size() const { return NOISE_THREADS; }
+    };
+    // adjoint-engine instance blockIdx.y, source chunk blockIdx.x: contributions + their sum.  Deterministic: every thread sums a fixed
+    // strided subsequence in ascending order, the 64 lanes combine by a fixed __shfl_down tree, the four wavefronts through LDS in
+    // wavefront order, one lane stores.  No floating-point atomics; nothing here depends on P, the batch or the pass.
+    __global__ void __launch_bounds__(NOISE_THREADS) k_noise_accumulate(NoiseView Z, int rows2)
+    {
+        __shared__ double wave_sum[NOISE_THREADS / 64];
+        int const q = static_cast<int>(blockIdx.y), c = static_cast<int>(blockIdx.x);
+        double acc = noise_accumulate_chunk(NoiseBlockTeam{}, Z, rows2, q, c);
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+        if((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if(threadIdx.x != 0) return;
+        double total = wave_sum[0];
+#pragma unroll
+        for(int w = 1; w < NOISE_THREADS / 64; ++w) total += wave_sum[w];
+        if(Z.n_chunks > 1)
+            Z.partial[static_cast<long long>(q) * Z.n_chunks + c] = total;
+        else if(double* dst = noise_slot_psd(Z, q))
+            *dst = total;
+    }
+    // second stage of a circuit with more than one chunk: one thread per instance adds its chunk sums in ascending order
+    __global__ void __launch_bounds__(256) k_noise_finish(NoiseView Z, int n)
+    {
+        int const q = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+        if(q < n) noise_finish(Z, q);
+    }
+    hipError_t launch_noise_sources(hipStream_t st, DevView const& V, NoiseView const& Z)
+    {
+        if(V.batch <= 0 || Z.n_src <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_noise_sources, dim3(sweep_grid(Z.n_src), V.batch), dim3(256), 0, st, V, Z);
+        return hipGetLastError();
+    }
+    hipError_t launch_noise_accumulate(hipStream_t st, DevView const& V, NoiseView const& Z)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        // (a circuit without sources still writes its zero densities: one chunk)
+        hipLaunchKernelGGL(k_noise_accumulate, dim3(Z.n_chunks, V.batch), dim3(NOISE_THREADS), 0, st, Z, V.rows);
+        if(Z.n_chunks > 1) hipLaunchKernelGGL(k_noise_finish, dim3((V.batch + 255) / 256), dim3(256), 0, st, Z, V.batch);
         return hipGetLastError();
     }
 

@@ -63,6 +63,13 @@ namespace pe
     hipError_t launch_ac_residual_each(hipStream_t st, DevView const& V, AcSweepView const& S);
     hipError_t launch_ac_accumulate_each(hipStream_t st, DevView const& V, AcSweepView const& S, bool first);
     hipError_t launch_ac_sweep_gather(hipStream_t st, DevView const& V, AcSweepView const& S);
+    // noise analysis (pe_noise.hpp).  sources: V is the MAIN engine's view -- Z.S[b][k] of every circuit instance from its resident operating
+    // point, and the shared row pairs Z.rows.  accumulate: V is the view of the adjoint sweep engine after refinement -- for every instance
+    // b * Z.P + p with Z.point[p] >= 0 the contributions S_k |y_b - y_a|^2 (into Z.contrib when kept) and their sum into Z.psd, in a
+    // summation order that depends on Z.n_src only.  Builds without HIP: serial host definitions in pe_engine_ac.cpp.
+    struct NoiseView;
+    hipError_t launch_noise_sources(hipStream_t st, DevView const& V, NoiseView const& Z);
+    hipError_t launch_noise_accumulate(hipStream_t st, DevView const& V, NoiseView const& Z);
     // variable-step transient (pe_lte.hpp): lte: q of the candidate V.x against the history ring + failed / non-finite instances into
     // L.result (cleared first); history_push: V.x of every instance into ring slot `slot`; state_copy: every (dst, src, bytes) of the table
     // (snapshot and roll-back of a step).  Builds without HIP: serial host definitions in pe_engine_newton.cpp.

@@ -32,6 +32,7 @@ EXPORTS = [
     "pe_hip_sweep_get_instance_state", "pe_hip_set_probes", "pe_hip_arm_probes", "pe_hip_get_probe_samples", "pe_hip_get_measures",
     "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
     "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
+    "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
 ]
 # pe_hip_measure_kind
 MEAS_MIN, MEAS_MAX, MEAS_AVG, MEAS_RMS, MEAS_INTEG, MEAS_CROSS = 1, 2, 3, 4, 5, 6
@@ -165,6 +166,18 @@ class AcSweepStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class NoiseControl(C.Structure):
+    _fields_ = [("out_pos", C.c_int), ("out_neg", C.c_int), ("temp_k", C.c_double), ("keep_contributions", C.c_int)]
+
+
+class NoiseStats(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_sources", C.c_int), ("n_passes", C.c_int), ("points_per_pass", C.c_int), ("n_analyses", C.c_int),
+                ("n_refine_rounds", C.c_int), ("n_retried_points", C.c_int), ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -209,6 +222,11 @@ def lib():
         l.pe_hip_set_ac_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(AcSweepStats)]
         l.pe_hip_get_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_analyze_noise.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(NoiseControl), C.POINTER(C.c_int), C.POINTER(NoiseStats)]
+        l.pe_hip_get_noise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_get_noise_sources.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 6
+        l.pe_hip_get_noise_source_density.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        l.pe_hip_get_noise_integrated.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         l.pe_hip_analyze_tr_adaptive.argtypes = [C.c_void_p, C.c_double, C.POINTER(TrControl), C.POINTER(TrAdaptiveStats)]
         l.pe_hip_get_tr_step_log.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         _lib = l
@@ -543,6 +561,49 @@ class Engine(_Probes):
         d = st.asdict()
         d["rc"] = rc
         return re + 1j * im, status[:n], d
+
+    def analyze_noise(self, omegas, out_pos, out_neg=-1, temp_k=0.0, contributions=False, check=True):
+        """Output noise density of x[out_pos] - x[out_neg] (rows of x, -1: ground) at every omega of `omegas` (rad/s, any order) by the
+        adjoint method on the device (pe_hip_analyze_noise).  Returns (psd [n_points][batch], one-sided, V^2/Hz -- NaN where a point
+        failed --, contrib [n_points][batch][n_sources] or None, status [n_points], stats dict with the return code under 'rc')."""
+        w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        n = len(w)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        st = NoiseStats()
+        ctl = NoiseControl(int(out_pos), int(out_neg), float(temp_k), 1 if contributions else 0)
+        rc = lib().pe_hip_analyze_noise(self._h, n, _dp(w), C.byref(ctl), _ip(status), C.byref(st))
+        if check:
+            self._chk(rc)
+        psd = np.full((n, self.batch), np.nan)
+        contrib = np.full((n, self.batch, st.n_sources), np.nan) if contributions else None
+        if rc not in (ERR_ARG, ERR_NO_DEVICE, ERR_INTERNAL) and n:
+            self._chk(lib().pe_hip_get_noise(self._h, 0, n, 0, self.batch, _dp(psd), _dp(contrib) if contributions and st.n_sources else None))
+        d = st.asdict()
+        d["rc"] = rc
+        return psd, contrib, status[:n], d
+
+    def noise_sources(self):
+        """the source table of the resident circuit: dict of int arrays kind (pe_hip_kind), index (in its table), part (BJT collector: 1),
+        row_a, row_b (-1: ground), in the order of the contributions"""
+        n = C.c_int()
+        self._chk(lib().pe_hip_get_noise_sources(self._h, 0, None, None, None, None, None, C.byref(n)))
+        out = {k: np.zeros(n.value, dtype=np.int32) for k in ("kind", "index", "part", "row_a", "row_b")}
+        self._chk(lib().pe_hip_get_noise_sources(self._h, n.value, *[_ip(out[k]) for k in ("kind", "index", "part", "row_a", "row_b")], C.byref(n)))
+        return out
+
+    def noise_source_density(self):
+        """current densities S_k of the last analyze_noise, [batch][n_sources], A^2/Hz"""
+        n = C.c_int()
+        self._chk(lib().pe_hip_get_noise_sources(self._h, 0, None, None, None, None, None, C.byref(n)))
+        s = np.zeros((self.batch, n.value))
+        self._chk(lib().pe_hip_get_noise_source_density(self._h, 0, self.batch, _dp(s)))
+        return s
+
+    def noise_integrated(self):
+        """integrated output noise of the last analyze_noise over its band (trapezoidal rule in f), [batch], V^2"""
+        v = np.zeros(self.batch)
+        self._chk(lib().pe_hip_get_noise_integrated(self._h, 0, self.batch, _dp(v)))
+        return v
 
     def phase_clocks_coop(self, instance=0):
         """Per-layout breakdown of the cooperative fronts (see pe_hip_get_phase_clocks_ex), microseconds / counts."""

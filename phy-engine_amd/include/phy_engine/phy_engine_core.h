@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -1350,6 +1351,48 @@ namespace phy_engine
             return true;
         }
         pe_hip_ac_sweep_stats last_ac_sweep_stats{};  // of the last linear / logarithmic sweep
+
+        // Small-signal noise analysis (pe_hip_analyze_noise, include/pe_hip.h): the one-sided output noise density of
+        // v(out_pos) - v(out_neg) (out_neg null: ground) at every omega [rad/s] of `omegas`, any order, at the circuit's operating point --
+        // prepared and, when a non-linear device needs a linearisation, solved first, as the AC case of analyze() does.  noise_results
+        // receives {omega, psd [V^2/Hz]} per point in the caller's order (NaN where a point failed), noise_integrated the trapezoidal
+        // integral over f = omega / 2 pi of the band (NaN when a point failed), last_noise_stats the rest.  temp_k <= 0: 300.15 K.
+        struct noise_point
+        {
+            double omega{};
+            double psd{};
+        };
+        ::std::vector<noise_point> noise_results{};
+        double noise_integrated{};
+        pe_hip_noise_stats last_noise_stats{};
+        auto& get_noise_results() noexcept { return noise_results; }
+        [[nodiscard]] bool analyze_noise(::phy_engine::model::node_t const& out_pos, ::phy_engine::model::node_t const* out_neg, ::std::vector<double> const& omegas,
+                                         double temp_k = 0.0) noexcept
+        {
+            noise_results.clear();
+            noise_integrated = ::std::numeric_limits<double>::quiet_NaN();
+            last_noise_stats = pe_hip_noise_stats{};
+            auto const saved = at;
+            at = analyze_type::AC;
+            bool ok = prepare();
+            if(ok && has_nonlinear_device())
+            {
+                at = analyze_type::OP;
+                ok = solve();
+            }
+            at = saved;
+            if(!ok || !gpu_ || !loaded_) return false;
+            auto row = [&](::phy_engine::model::node_t const* n) { return (!n || n == &nl.ground_node) ? -1 : static_cast<int>(n->node_index); };
+            pe_hip_noise_control const ctl{row(&out_pos), row(out_neg), temp_k, 0};
+            int const n = static_cast<int>(omegas.size());
+            int const rc = pe_hip_analyze_noise(gpu_, n, omegas.data(), &ctl, nullptr, &last_noise_stats);
+            if(rc == PE_HIP_ERR_ARG || rc == PE_HIP_ERR_NO_DEVICE || rc == PE_HIP_ERR_INTERNAL) return gpu_fail();
+            ::std::vector<double> psd(omegas.size());
+            if(pe_hip_get_noise(gpu_, 0, n, 0, 1, psd.data(), nullptr) != PE_HIP_OK) return gpu_fail();
+            for(::std::size_t i = 0; i < omegas.size(); ++i) noise_results.push_back({omegas[i], psd[i]});
+            if(pe_hip_get_noise_integrated(gpu_, 0, 1, &noise_integrated) != PE_HIP_OK) return gpu_fail();
+            return rc == PE_HIP_OK || gpu_fail();
+        }
 
         // one AC solve (solve_once with iterate_ac): phasors scattered into the nodes / branches as complex values
         bool solve_ac_point(double omega) noexcept
