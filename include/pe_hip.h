@@ -187,6 +187,15 @@ const char* pe_hip_build_id(void);
 int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch, int n_tables, const pe_hip_device_table* tables);
 int pe_hip_set_options(pe_hip_engine* h, const pe_hip_options* opt);
 int pe_hip_get_info(pe_hip_engine* h, pe_hip_info* out);
+/* The fronts of an analysis the engine holds, in postorder (children before parents), copied from its symbolic tables: read-only, nothing
+ * is recomputed.  `which` 0: the resident circuit (after its first analysis), 1: the last analysis of pe_hip_solve_csr_real, 2: that of
+ * pe_hip_solve_csr_complex (its real-equivalent 2n system); PE_HIP_ERR_ARG when that analysis does not exist.  Arrays of `capacity` ints
+ * (any may be NULL), *n_fronts receives the count -- call with capacity 0 first.  Per front s: pivots[s], updates[s] (order m = pivots +
+ * updates), parent[s] (-1: root), kind[s] (0 wave front, 1 cooperative front of a part, 2 top front), quad[s] (1: factored by the lane-group
+ * kernel, as counted by pe_hip_info::n_quad_fronts), mode[s] (LDS layout: 0 whole front, 1 pivot panels + pulled Schur tiles, 2 chain link,
+ * 3 chain link continued in LDS), n_children[s], n_own[s] (entries of A assembled into the front). */
+int pe_hip_get_front_table(pe_hip_engine* h, int which, int capacity, int* pivots, int* updates, int* parent, int* kind, int* quad, int* mode,
+                           int* n_children, int* n_own, int* n_fronts);
 
 /* Tuning knobs of ONE engine: the launch-geometry / symbolic-analysis parameters INTEGRATION.md lists as the PHY_ENGINE_HIP_* environment
  * family (the counterpart of the reference's cuda_policy / cuda_node_threshold members plus its PHY_ENGINE_CUDA_* variables,

@@ -540,6 +540,32 @@ int pe_hip_get_info(pe_hip_engine* h, pe_hip_info* out)
     return PE_HIP_OK;
 }
 
+int pe_hip_get_front_table(pe_hip_engine* h, int which, int capacity, int* pivots, int* updates, int* parent, int* kind, int* quad, int* mode,
+                           int* n_children, int* n_own, int* n_fronts)
+{
+    if(!h || !n_fronts || capacity < 0) return PE_HIP_ERR_ARG;
+    pe::Symbolic const* S = nullptr;
+    pe::DevView const* V = nullptr;
+    if(which == 0 && h->loaded && h->sym_class >= 0) S = &h->sym, V = &h->V;
+    else if(which == 1 && h->csr.have) S = &h->csr.sym, V = &h->csr.V;
+    else if(which == 2 && h->csrz.have) S = &h->csrz.sym, V = &h->csrz.V;
+    if(!S) return fail(h, PE_HIP_ERR_ARG, "get_front_table: no such analysis");
+    auto at = [](std::vector<int> const& v, int s) { return static_cast<size_t>(s) < v.size() ? v[static_cast<size_t>(s)] : 0; };
+    *n_fronts = S->nfronts;
+    for(int s = 0; s < S->nfronts && s < capacity; ++s)
+    {
+        if(pivots) pivots[s] = S->f_p[s];
+        if(updates) updates[s] = S->f_u[s];
+        if(parent) parent[s] = S->f_parent[s];
+        if(kind) kind[s] = at(S->f_kind, s);
+        if(quad) quad[s] = (V->quad && at(S->f_quad, s)) ? 1 : 0;
+        if(mode) mode[s] = at(S->f_mode, s);
+        if(n_children) n_children[s] = S->f_child_ptr[s + 1] - S->f_child_ptr[s];
+        if(n_own) n_own[s] = S->f_asm_ptr[s + 1] - S->f_asm_ptr[s];
+    }
+    return PE_HIP_OK;
+}
+
 int pe_hip_set_time(pe_hip_engine* h, double t, double last_step)
 {
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;

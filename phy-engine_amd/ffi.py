@@ -23,7 +23,7 @@ OK, ERR_ARG, ERR_NO_DEVICE, ERR_SINGULAR, ERR_NO_CONVERGENCE, ERR_INTERNAL, ERR_
 
 EXPORTS = [
     "pe_hip_device_count", "pe_hip_create", "pe_hip_destroy", "pe_hip_last_error", "pe_hip_solve_csr_real", "pe_hip_solve_csr_complex", "pe_hip_build_id",
-    "pe_hip_load_circuit", "pe_hip_set_options", "pe_hip_get_info", "pe_hip_set_digital_drives", "pe_hip_set_overlay", "pe_hip_set_knob", "pe_hip_get_knob", "pe_hip_update_param",
+    "pe_hip_load_circuit", "pe_hip_set_options", "pe_hip_get_info", "pe_hip_get_front_table", "pe_hip_set_digital_drives", "pe_hip_set_overlay", "pe_hip_set_knob", "pe_hip_get_knob", "pe_hip_update_param",
     "pe_hip_reset", "pe_hip_analyze_dc", "pe_hip_analyze_tr", "pe_hip_get_solution", "pe_hip_set_solution",
     "pe_hip_get_instance_state", "pe_hip_sweep_statistics", "pe_hip_measure_hbm_ceiling", "pe_hip_get_safety_net_counters", "pe_hip_get_newton_trace", "pe_hip_get_matrix", "pe_hip_analyze_pattern",
     "pe_hip_analyze_pattern_fronts", "pe_hip_get_phase_clocks", "pe_hip_get_phase_clocks_ex", "pe_hip_analyze_ac", "pe_hip_get_solution_ac", "pe_hip_set_ac_sweep_rows", "pe_hip_analyze_ac_sweep", "pe_hip_get_ac_sweep", "pe_hip_checkpoint_size", "pe_hip_checkpoint_save", "pe_hip_checkpoint_load", "pe_hip_set_time",
@@ -195,6 +195,7 @@ def lib():
         l.pe_hip_load_circuit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DeviceTable)]
         l.pe_hip_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
         l.pe_hip_get_info.argtypes = [C.c_void_p, C.POINTER(Info)]
+        l.pe_hip_get_front_table.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 9
         l.pe_hip_set_digital_drives.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         l.pe_hip_update_param.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
         l.pe_hip_reset.argtypes = [C.c_void_p]
@@ -397,6 +398,16 @@ class Engine(_Probes):
         i = Info()
         self._chk(lib().pe_hip_get_info(self._h, C.byref(i)))
         return i.asdict()
+
+    def front_table(self, which=0):
+        """the fronts of an analysis this engine holds, in postorder: dict of int32 arrays p, u, parent, kind (0 wave, 1 cooperative, 2 top),
+        quad, mode, n_children, n_own (pe_hip_get_front_table).  which: 0 the resident circuit, 1 / 2 the last solve_csr / solve_csr_complex"""
+        n = C.c_int()
+        self._chk(lib().pe_hip_get_front_table(self._h, int(which), 0, *[None] * 8, C.byref(n)))
+        names = ("p", "u", "parent", "kind", "quad", "mode", "n_children", "n_own")
+        out = {k: np.zeros(n.value, dtype=np.int32) for k in names}
+        self._chk(lib().pe_hip_get_front_table(self._h, int(which), n.value, *[_ip(out[k]) for k in names], C.byref(n)))
+        return out
 
     def reset(self):
         self._chk(lib().pe_hip_reset(self._h))
