@@ -1,0 +1,1209 @@
+"""Shared by tests/test_device_eval_emu.py and tests/test_gpu_device_eval.py: one Newton iteration's linearisation -- what eval_devices and
+companion_update of pe_front.hpp put into the matrix and the right-hand side -- against a restatement of every formula in mpmath (256
+bits), value by value.
+
+The probe.  max_newton caps the iterations, set_solution() sets the iterate, matrix(b) returns the last stamped A and rhs of instance b.
+Every pin of a device under test sits on a node of its own that a VDC of its own ties to ground (or is ground): the source adds only
+incidence entries in its branch row and column, so the node-by-node cells among a device's pins hold that device's values alone (g_min is
+0), the system is non-singular and after any solve every pin is on its source value.  An instance that hits the iteration cap reports
+ERR_NO_CONVERGENCE; its stamp stays readable and the failure is not sticky (every analysis clears the status).  Forms:
+  DC1   reset, set x, DC with max_newton = 1: the diode sees vlimit(Ud = x, Ud_last = 0)
+  TR1   reset, set x, one TR step with max_newton = 1: companion_update sets Ud_last = Ud, the stamp is the unlimited model at x
+  TR2   the same with max_newton = 2: iteration 1 at the set x, its solve puts the pins on the sources, iteration 2 stamps
+        vlimit(Ud = V_a - V_c, Ud_last = the first iteration's) -- any pair; on the split schedule iteration 2 is the dynamic_only path.
+        solution() is asserted bitwise on the source values: that is what allows taking Ud from the parameters.
+
+The reference.  Class E carries, for every intermediate, the value in mpmath (.v), the SAME expression evaluated in double (.d, Python
+floats: IEEE add / subtract / multiply / divide are bit-identical everywhere, so branch predicates -- x > 50, Ud_0 > Uth, Vov <= 0,
+Vx < Vov, tm_ < duty * T ... -- are evaluated on .d exactly as written in pe_front.hpp) and a running error bound (.e).
+
+Tolerance (derived, not fitted).  u = 2^-53.  ASSUMPTION: the device's fp64 exp / log / sin / sqrt are good to 1 ulp (ROCm's documented
+accuracy of these functions), i.e. 2 u relative; + - * / are correctly rounded (u relative; HIP compiles fp64 division and fmod without
+fast-math).  Every operation adds u |result| (a libm call 2 u |result|) to the bounds its operands bring, a transcendental amplifies its
+argument's bound by its derivative: the bound is sum over the roundings of u * (magnitude of that intermediate) -- the "(c + sum |a|) u S"
+of a formula with c roundings whose intermediates are at most S, evaluated term by term.  A fused multiply-add removes one rounding, so the
+bound holds for contracted code as well -- provided that the reference takes no rounded product for an exact input: the pulse's
+Ton = duty * T enters the value as E(duty) * T (exact product, one rounding in the bound), so that a device that fuses duty * T - tf is
+covered.  Predicates are evaluated unfused; the only one a contraction could change is tm_ < Ton - tf, and the points on or beside it
+have an exact product duty * T (powers of two), where fused and unfused agree.  E.e == 0 (a value that is an input, a constant, or one of two constants chosen by a predicate)
+demands bitwise equality; values that are ONE rounded operation of inputs are compared bitwise against .d.
+For the diode the bound is the closed form  |q_dev - q_ref| <= (8 + |Ud / Ute| + |Ud / Uter|) u S  with
+S(geq) = the larger of the two conductance terms, S(Ieq) = max(|Id|, |Ud geq|, Is, Isr); c = 8: the quotient Ud / Ute is the amplified
+term, then per junction term exp (2), the product and the quotient with Ute (2), for Ieq the subtraction e - 1 and the product (2, in
+place of the quotient), the sum of the two terms (1) and the final Ud * geq and subtraction (fused: 1, shared error of geq counted in S).
+A limited junction voltage (an arm of vlimit with a log, or the breakdown mirror's two additions) is not an input but a computed value:
+its own bound dUd (from E) enters through the derivative, dgeq = geq dUd / Ute and dIeq = |Ud / Ute| geq dUd."""
+import math
+import os
+import re
+
+import mpmath as mp
+import numpy as np
+import scipy.sparse as sp
+
+from parity_common import ROOT, pe
+
+mp.mp.prec = 256
+F = pe.ffi
+U = mp.mpf(2) ** -53
+SCHEDULES = [{"SPLIT": 0}, {"SPLIT": 1, "GRAPH": 0}, {"SPLIT": 1, "GRAPH": 1}]
+IDS = ["resident", "split", "split_graph"]
+NO_CONV = F.ERR_NO_CONVERGENCE
+
+
+def _from_source(name, pattern):
+    with open(os.path.join(ROOT, "phy-engine_amd", "csrc", name)) as f:
+        m = re.findall(pattern, f.read())
+    assert len(m) == 1, f"{name}: {pattern!r} matches {len(m)} times"
+    return int(m[0])
+
+
+PE_THREADS = _from_source("pe_kernels.hpp", r"#define PE_THREADS (\d+)")      # the resident kernels' launch bound
+M2_EVAL_THREADS = _from_source("pe_kernels.hip", r"hipLaunchKernelGGL\(k_m2_eval, dim3\(G, B\), dim3\((\d+)\)")      # k_m2_eval's workgroup
+WRAP_CELLS = max(PE_THREADS, M2_EVAL_THREADS) + 3
+DT = 2.0 ** -20
+
+
+# ---- arithmetic with a running error bound -------------------------------------------------------------------------------------------------
+class E:
+    __slots__ = ("d", "v", "e")
+
+    def __init__(self, d, v=None, e=0):
+        self.d = float(d)
+        self.v = mp.mpf(self.d) if v is None else v
+        self.e = mp.mpf(e)
+
+    def __neg__(self):
+        return E(-self.d, -self.v, self.e)
+
+    def __add__(self, o):
+        o = _c(o)
+        v = self.v + o.v
+        return E(self.d + o.d, v, self.e + o.e + U * abs(v))
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        return self + (-_c(o))
+
+    def __rsub__(self, o):
+        return _c(o) + (-self)
+
+    def __mul__(self, o):
+        o = _c(o)
+        v = self.v * o.v
+        return E(self.d * o.d, v, abs(self.v) * o.e + abs(o.v) * self.e + self.e * o.e + U * abs(v))
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = _c(o)
+        v = self.v / o.v
+        return E(self.d / o.d, v, (self.e + abs(v) * o.e) / (abs(o.v) - o.e) + U * abs(v))
+
+    def __rtruediv__(self, o):
+        return _c(o) / self
+
+
+def _c(x):
+    return x if isinstance(x, E) else E(x)
+
+
+def f_exp(a):
+    v = mp.exp(a.v)
+    return E(math.exp(a.d), v, v * (mp.exp(a.e) - 1) + 2 * U * v)
+
+
+def f_log(a):
+    v = mp.log(a.v)
+    return E(math.log(a.d), v, a.e / (abs(a.v) - a.e) + 2 * U * abs(v))
+
+
+def f_sin(a):
+    v = mp.sin(a.v)
+    return E(math.sin(a.d), v, a.e + 2 * U * abs(v))
+
+
+def f_sqrt(a):
+    v = mp.sqrt(a.v)
+    return E(math.sqrt(a.d), v, a.e / (2 * (v - a.e)) + 2 * U * v)
+
+
+class Worst:
+    """worst error / bound per quantity name; values with a zero bound must be bitwise equal"""
+
+    def __init__(self):
+        self.ratio = {}
+        self.arms = set()
+
+    def check(self, name, got, ref, what="", bound=None):
+        bound = ref.e if bound is None else bound
+        err = abs(mp.mpf(float(got)) - ref.v)
+        if bound == 0:
+            assert err == 0, f"{name} {what}: {float(got)!r} is not bitwise {float(ref.v)!r}"
+            r = 0.0
+        else:
+            r = float(err / bound)
+        self.ratio[name] = max(self.ratio.get(name, 0.0), r)
+        assert r <= 1.0, f"{name} {what}: device {float(got)!r}, reference {mp.nstr(ref.v, 20)}, error {float(err):.3g} = {r:.3g} of the bound {float(bound):.3g}"
+
+    def bitwise(self, name, got, want, what=""):
+        self.ratio.setdefault(name, 0.0)
+        assert float(got) == float(want), f"{name} {what}: {float(got)!r} is not bitwise {float(want)!r}"
+
+    def need(self, arms, what):
+        missing = sorted(set(arms) - self.arms)
+        assert not missing, f"{what}: arms not reached by the bias set: {missing}; reached {sorted(self.arms)}"
+
+    def report(self, what):
+        print(f"RATIOS {what}: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(self.ratio.items())))
+
+
+# ---- the formulas of pe_front.hpp, restated -------------------------------------------------------------------------------------------------
+def ref_limexp(x, arms, tag):
+    """limexp: predicates on the double quotient.  Returns E."""
+    if x.d > 50.0:
+        arms.add(f"limexp {tag}: x > 50")
+        return f_exp(E(50.0)) * (1.0 + (x - 50.0))
+    if x.d < -50.0:
+        arms.add(f"limexp {tag}: x < -50")
+        return f_exp(E(-50.0))
+    if x.d == 50.0 or x.d == -50.0:
+        arms.add(f"limexp {tag}: x on {x.d:+.0f}")
+    arms.add(f"limexp {tag}: exp")
+    return f_exp(x)
+
+
+def ref_vlimit(Ud, Ud_last, Ute, Uth, Bv_eff, Bv_set, arms):
+    """vlimit with the breakdown mirror; Ud, Ud_last: E.  Returns E (its .e is dUd)"""
+    flag = False
+    thr = min(0.0, -Bv_eff + 10.0 * Ute)
+    if Bv_set and Ud.d == thr:
+        arms.add("vlimit: Ud on the flag threshold")
+    if Bv_set and Ud.d < thr:
+        Ud_0, Ud_1, flag = -(Ud + Bv_eff), -(Ud_last + Bv_eff), True
+    else:
+        Ud_0, Ud_1 = Ud, Ud_last
+    m = "mirrored " if flag else ""
+    if Ud_0.d > Uth and abs(Ud_0.d - Ud_1.d) > 2.0 * Ute:
+        if Ud_1.d > 0:
+            arg = (Ud_0 - Ud_1) / Ute
+            if arg.d > 0.0:
+                arms.add(f"vlimit: {m}Ud_1 > 0, arg > 0")
+                Ud_f = Ud_1 + Ute * (2.0 + f_log(arg - 2.0))
+            else:
+                arms.add(f"vlimit: {m}Ud_1 > 0, arg < 0")
+                Ud_f = Ud_1 - Ute * (2.0 + f_log(2.0 - arg))
+        else:
+            arms.add(f"vlimit: {m}Ud_1 <= 0, Ute log(Ud_0 / Ute)")
+            Ud_f = Ute * f_log(Ud_0 / Ute)
+    else:
+        Ud_f = Ud_0
+        clipped = False
+        if Ud_0.d < 0.0:
+            arg = (-1.0 - Ud_1) if Ud_1.d > 0.0 else (2.0 * Ud_1 - 1)
+            if Ud_0.d < arg.d:
+                Ud_f, clipped = arg, True
+                arms.add(f"vlimit: {m}small, clipped, " + ("Ud_1 > 0" if Ud_1.d > 0.0 else "Ud_1 <= 0"))
+        if not clipped:
+            arms.add(f"vlimit: {m}small, not clipped")
+    return -(Ud_f + Bv_eff) if flag else Ud_f
+
+
+class DiodeRef:
+    """one diode's state (Ud_last, geq, hist, prevg) through companion_update / eval_devices; par: the prepared DP_* columns"""
+
+    def __init__(self, par):
+        self.Is, self.Isr, self.Ute, self.Uter, self.Uth, self.Bv_eff = (float(par[k]) for k in range(6))
+        self.Bv_set, self.tt, self.tt_stamp = par[6] != 0.0, float(par[7]), par[8] != 0.0
+        self.udl, self.geq, self.hist, self.prevg = E(0.0), E(0.0), E(0.0), E(0.0)
+
+    def companion(self, vd, dt):
+        """vd: the double the device reads (fl(x_a - x_c))"""
+        self.udl = E(vd)
+        cd = self.tt * self.geq
+        if not (dt > 0.0) or not (self.tt > 0.0) or not (self.geq.d > 0.0) or not (cd.d > 0.0):
+            self.hist, self.prevg = E(0.0), E(0.0)
+        else:
+            g_new = 2.0 * cd / dt
+            self.hist = -(g_new + self.prevg) * vd - self.hist
+            self.prevg = g_new
+
+    def eval(self, vd, tr, arms):
+        """returns (g, ie, bound_g, bound_ie): the values stamped (mpf) and their bounds"""
+        Ud = ref_vlimit(E(vd), self.udl, self.Ute, self.Uth, self.Bv_eff, self.Bv_set, arms)
+        self.udl = Ud
+        dUd = Ud.e
+        Ux = E(Ud.d, Ud.v, 0)      # the limited voltage as a value: its bound enters through the derivative below, not through E
+        if self.Bv_set and Ud.d == -self.Bv_eff:
+            arms.add("diode: Ud on -Bv_eff")
+        if self.Bv_set and Ud.d < -self.Bv_eff:
+            arms.add("diode: breakdown")
+            x = -(self.Bv_eff + Ux) / self.Ute
+            e = ref_limexp(x, arms, "breakdown")
+            Id, geq = -self.Is * e.v, self.Is * e.v / self.Ute
+            amp, S_g, S_i = abs(x.v), abs(geq), max(abs(Id), abs(Ux.v * geq), self.Is, self.Isr)
+        else:
+            arms.add("diode: forward / reverse" + (" with recombination" if self.Isr > 0.0 else ""))
+            x, xr = Ux / self.Ute, Ux / self.Uter
+            e, er = ref_limexp(x, arms, "Ute"), ref_limexp(xr, arms, "Uter")
+            g1, g2 = self.Is * e.v / self.Ute, self.Isr * er.v / self.Uter
+            geq = g1 + g2
+            Id = self.Is * (e.v - 1) + self.Isr * (er.v - 1)
+            amp = abs(x.v) + (abs(xr.v) if self.Isr > 0.0 else 0)
+            S_g, S_i = max(abs(g1), abs(g2)), max(abs(Id), abs(Ux.v * geq), self.Is, self.Isr)
+        Ieq = Id - Ux.v * geq
+        b_g = (8 + amp) * U * S_g + geq * dUd / self.Ute
+        b_i = (8 + amp) * U * S_i + abs(Ux.v / self.Ute) * geq * dUd
+        self.geq = E(float(geq), geq, b_g)
+        g, ie = geq, Ieq
+        if tr and self.tt_stamp and self.prevg.d != 0.0:
+            arms.add("diode: diffusion companion summed")
+            g, ie = geq + self.prevg.v, Ieq + self.hist.v
+            b_g += self.prevg.e + U * abs(g)
+            b_i += self.hist.e + U * abs(ie)
+        return g, ie, b_g, b_i
+
+
+def ref_mos(nmos, v0, v1, v2, Kp, lam, Vth, arms):
+    """level-1 MOSFET, pins D G S at the doubles v0 v1 v2: (gds, gm, ieq) as E"""
+    v0, v1, v2 = E(v0), E(v1), E(v2)
+    t = "NMOS" if nmos else "PMOS"
+    Vc = (v1 - v2) if nmos else (v2 - v1)
+    Vds = v0 - v2
+    Vx = Vds if nmos else -Vds
+    Vov = Vc - Vth
+    Id, gm, gds = E(0.0), E(0.0), E(0.0)
+    lt = "lambda = 0" if lam == 0.0 else "lambda > 0"
+    if Vov.d <= 0.0:
+        arms.add(f"{t} {lt}: cut-off" if Vov.d < 0.0 else f"{t} {lt}: Vov = 0")
+    elif Vx.d < Vov.d:
+        arms.add(f"{t} {lt}: " + ("reversed" if Vx.d < 0.0 else ("Vx = 0" if Vx.d == 0.0 else "triode")))
+        B = Vov * Vx - 0.5 * Vx * Vx
+        Ids = Kp * B * (1.0 + lam * Vx)
+        dI = Kp * ((Vov - Vx) * (1.0 + lam * Vx) + B * lam)
+        Id = Ids if nmos else -Ids
+        gm = Kp * Vx * (1.0 + lam * Vx)
+        gds = dI if nmos else -dI
+    else:
+        arms.add(f"{t} {lt}: " + ("Vx = Vov" if Vx.d == Vov.d else "saturation"))
+        Ids = 0.5 * Kp * Vov * Vov * (1.0 + lam * Vx)
+        Id = Ids if nmos else -Ids
+        gm = Kp * Vov * (1.0 + lam * Vx)
+        gds = (0.5 * Kp * Vov * Vov * lam) if nmos else (0.5 * Kp * Vov * Vov * (-lam))
+    return gds, gm, Id - gm * Vc - gds * Vds
+
+
+def ref_bjt(npn, v0, v2, Is_eff, Ute, BetaF, arms):
+    """forward-active Ebers-Moll, pins B . E: (geq, i1, gm, i2) as E"""
+    v0, v2 = E(v0), E(v2)
+    Vj = (v0 - v2) if npn else (v2 - v0)
+    arms.add(("NPN" if npn else "PNP") + (": Vj < 0" if Vj.d < 0.0 else (": Vj = 0" if Vj.d == 0.0 else ": Vj > 0")))
+    e = f_exp(Vj / Ute)
+    geq = Is_eff * e / Ute
+    Ij = Is_eff * (e - 1.0)
+    gm = BetaF * geq
+    return geq, Ij - Vj * geq, gm, BetaF * Ij - gm * Vj
+
+
+def bjt_prepared(par):
+    """(Is * Area, N * Ut, BetaF) as gen_derive of pe_circuit.cpp prepares them on the host (host preparation is not under test)"""
+    Is, N, BetaF, Temp, Area = par
+    Ut = 1.380650524e-23 * (Temp - (-273.15)) / 1.6021765314e-19
+    return Is * Area, N * Ut, BetaF
+
+
+def diode_prepared(par):
+    """the DP_* columns of one diode from its ten deck parameters, as diode_derive of pe_circuit.cpp (host preparation: not under test)"""
+    Is, N, Isr, Nr, Temp, Ibv, Bv, Bv_set, Area, tt = par
+    Is_eff, Isr_eff = Is * Area, Isr * Area
+    Ut = 1.380650524e-23 * (Temp - (-273.15)) / 1.6021765314e-19
+    Bv_eff = Bv - N * Ut * math.log(Ibv / Is_eff) if Bv_set != 0.0 else Bv
+    Uth = N * Ut * math.log(N * Ut / (1.4142135623730950488016887242096981 * Is_eff))
+    return [Is_eff, Isr_eff, N * Ut, Nr * Ut, Uth, Bv_eff, 1.0 if Bv_set != 0.0 else 0.0, tt, 1.0]
+
+
+def ref_generator(kind, p, tt, arms):
+    """kind 1 SAW, 2 SQR, 3 PULSE, 4 TRI; p = (Vh, Vl, freq, duty, phase, tr, tf); tt the double time the device evaluates at.  t0, T and
+    tm_ are divisions, one addition and fmod of doubles: evaluated in double (bit-identical wherever fmod is exact, and it is by definition)"""
+    Vh, Vl, freq, duty, phase, trise, tfall = (float(q) for q in p)
+    T = 1.0 / freq
+    t0 = tt + phase / (2.0 * 3.14159265358979323846) / freq
+    tm = math.fmod(t0, T)
+    name = {1: "SAW", 2: "SQR", 3: "PULSE", 4: "TRI"}[kind]
+    if tm < 0.0:
+        arms.add(f"{name}: tm_ < 0")
+    if tm == 0.0:
+        arms.add(f"{name}: tm_ = 0")
+    if kind == 1:
+        return E(Vl) + ((E(Vh) - Vl) / T) * tm
+    if kind == 2:
+        if tm == duty * T:
+            arms.add("SQR: tm_ = duty T")
+        arms.add("SQR: high" if tm < duty * T else "SQR: low")
+        return E(Vh if tm < duty * T else Vl)
+    if kind == 3:
+        Ton = duty * T
+        if tm < trise:
+            arms.add("PULSE: rising")
+            return E(Vl) + ((E(Vh) - Vl) / max(trise, 1e-30)) * tm
+        if tm < Ton - tfall:
+            arms.add("PULSE: high")
+            return E(Vh)
+        if tm == Ton - tfall:
+            arms.add("PULSE: tm_ = Ton - tf")
+        if tm < Ton:
+            arms.add("PULSE: falling")
+            return E(Vh) - ((E(Vh) - Vl) / max(tfall, 1e-30)) * (E(tm) - (E(duty) * T - tfall))
+        arms.add("PULSE: low")
+        return E(Vl)
+    amp = E(Vh) - Vl
+    if tm == 0.5 * T:
+        arms.add("TRI: tm_ = T / 2")
+    if tm < 0.5 * T:
+        arms.add("TRI: up")
+        return E(Vl) + (2.0 * amp / T) * tm
+    arms.add("TRI: down")
+    return E(Vh) - (2.0 * amp / T) * (E(tm) - E(0.5) * T)
+
+
+def ref_sine(p, tt):
+    return E(p[0]) * f_sin(E(p[1]) * tt + p[2])
+
+
+# ---- engine plumbing ------------------------------------------------------------------------------------------------------------------------
+class OracleEngine:
+    """oracle/pe_oracle.py (float64 numpy, the second implementation) behind the few Engine methods the checks use, so that every check
+    of this module runs on it unchanged: one Oracle per instance on a deck that carries that instance's parameters, the Newton loop of
+    Oracle.solve with the iteration cap, the last stamp kept for matrix(b).  (Oracle.solve_once would stamp a second time, and a stamp
+    moves the diode and relay state: the loop here stamps once per iteration.)"""
+
+    def __init__(self, mod, deck, batch, overrides, max_newton):
+        self.rows, self.batch, self.cap = deck.rows, batch, max_newton or 64
+        self.o, self.last, self.trace = [], [None] * batch, []
+        self.status = np.zeros(batch, dtype=np.int32)
+        for b in range(batch):
+            d = pe.deck.Deck()
+            d.n_nodes = deck.n_nodes
+            seen = {}
+            for kind, nodes, par in deck.devices:
+                key = "VGEN" if kind in pe.deck.VGEN_LAYOUT else kind
+                j = seen.get(key, 0)
+                seen[key] = j + 1
+                if overrides and key in overrides:
+                    row = np.asarray(overrides[key], dtype=float)[b, j]
+                    par = list(par)
+                    if key == "VGEN":
+                        for col, q in enumerate(pe.deck.VGEN_LAYOUT[kind][1]):
+                            if q >= 0:
+                                par[q] = float(row[1 + col])
+                    else:
+                        par[:len(row)] = [float(v) for v in row]
+                d.devices.append((kind, nodes, tuple(par)))
+            o = mod.Oracle(d)
+            o.prepare()      # at reset x is zero: Ud_last = 0
+            self.o.append(o)
+
+    def set_solution(self, x):
+        for o, xb in zip(self.o, np.asarray(x, dtype=float).reshape(self.batch, self.rows)):
+            o.x = xb.copy()
+
+    def _solve(self, mode):
+        import scipy.sparse.linalg as spla
+        worst = 0
+        for b, o in enumerate(self.o):
+            self.status[b] = NO_CONV
+            for it in range(self.cap):
+                prev = o.x.copy()
+                A, rhs = o.assemble(mode)
+                self.last[b] = (sp.csr_matrix(A), rhs)
+                lu = spla.splu(A, permc_spec="COLAMD", diag_pivot_thresh=1.0)
+                o.x = lu.solve(rhs)
+                o.x = o.x + lu.solve(rhs - A @ o.x)      # one refinement step puts every driven pin bitwise on its source, as the checks assume
+                worst = max(worst, it + 1)
+                tol = np.where(np.arange(self.rows) < o.N, 1e-6, 1e-12) + 1e-3 * np.maximum(np.abs(o.x), np.abs(prev))      # Oracle.solve's test
+                if not o.nonlinear or np.all(np.abs(o.x - prev) <= tol):
+                    self.status[b] = 0
+                    break
+        self.trace.append(worst)
+        return {"rc": 0}
+
+    def analyze_dc(self, mode, check=False):
+        return self._solve({F.MODE_DC: "DC", F.MODE_OP: "OP", F.MODE_TROP: "TROP"}[mode])
+
+    def analyze_tr(self, dt, nsteps, check=False):
+        if not dt > 0.0:
+            return {"rc": F.ERR_ARG}
+        assert nsteps == 1
+        for o in self.o:
+            o.update_tr_step(dt)
+            o.t = o.t + dt
+        return self._solve("TR")
+
+    def state(self):
+        return {"status": self.status.copy(), "t": np.array([o.t for o in self.o])}
+
+    def solution(self):
+        return np.array([o.x for o in self.o])
+
+    def matrix(self, b):
+        A, rhs = self.last[b]
+        return A.indptr, A.indices, A.data, rhs
+
+    def newton_trace(self):
+        return np.array(self.trace)
+
+    def info(self):
+        return {}
+
+    def close(self):
+        pass
+
+
+def engine(deck, batch, knobs, overrides=None, max_newton=0):
+    if "ORACLE" in knobs:
+        return OracleEngine(knobs["ORACLE"], deck, batch, overrides, max_newton)
+    e = F.Engine()
+    e.set_options(g_min=0.0, max_newton=max_newton, residual_tol=-1.0)     # (residual safety net off: a retry would stamp again)
+    for k, v in knobs.items():
+        e.set_knob(k, v)
+    e.load_deck(deck, batch, overrides)
+    e.reset()
+    return e
+
+
+def stamped(e, b):
+    rp, ci, va, rhs = e.matrix(b)
+    return sp.csr_matrix((va, ci, rp), shape=(e.rows, e.rows)), rhs
+
+
+def branch_rows(deck):
+    """first branch row of every device that has one, by position in deck.devices"""
+    k, out = deck.n_nodes, {}
+    for i, (kind, _, _) in enumerate(deck.devices):
+        if pe.deck.NBRANCH[kind]:
+            out[i] = k
+            k += pe.deck.NBRANCH[kind]
+    return out
+
+
+class Cells:
+    """a deck whose pins are nodes with a VDC of their own"""
+
+    def __init__(self):
+        self.deck = pe.deck.Deck()
+        self.vdc = {}      # node -> index among the VDCs
+
+    def pin(self):
+        n = self.deck.new_node()
+        self.vdc[n] = self.deck.count("VDC")
+        self.deck.add("VDC", (n, 0), 0.0)
+        return n
+
+    def tables(self, volts):
+        """volts [B][n_nodes + 1] per node id (column 0: ground) -> (x [B][rows] with the nodes set, overrides VDC [B][nV][1])"""
+        volts = np.asarray(volts, dtype=float)
+        B = len(volts)
+        x = np.zeros((B, self.deck.rows))
+        x[:, :self.deck.n_nodes] = volts[:, 1:]
+        v = np.zeros((B, len(self.vdc), 1))
+        for n, k in self.vdc.items():
+            v[:, k, 0] = volts[:, n]
+        return x, v
+
+
+def r(n):
+    """row of node id n (-1: ground)"""
+    return n - 1
+
+
+def cell(A, a, b):
+    return float(A[r(a), r(b)]) if a > 0 and b > 0 else 0.0
+
+
+def statuses_ok(e, what):
+    st = e.state()["status"]
+    assert all(s in (0, NO_CONV) for s in st), f"{what}: statuses {sorted(set(st.tolist()))}"
+    return st
+
+
+# ---- non-linear devices ---------------------------------------------------------------------------------------------------------------------
+D_DEFAULT = pe.deck.DEFAULTS["D"]
+
+
+def _emission_for(ute, temp=27.0):
+    """N with fl(N * Ut) == ute: with a power of two for N Ut the quotients Ud / Ute = +-50 are met exactly (with the default N = 1 no
+    double has the quotient 50: neighbouring junction voltages give quotients 1.5 ulp(50) apart)"""
+    Ut = 1.380650524e-23 * (temp - (-273.15)) / 1.6021765314e-19
+    n = ute / Ut
+    for k in range(-8, 9):
+        cand = float(n + k * math.ulp(n))
+        if cand * Ut == ute:
+            return cand
+    raise AssertionError(f"no emission coefficient gives N Ut == {ute}")
+
+
+_N = _emission_for(2.0 ** -5)
+D_BREAK = (1e-14, _N, 1e-11, 2.0 * _N, 27.0, 1e-3, 5.0, 1.0, 1.0, 0.0)     # Isr > 0, Nr = 2 N, Bv_set, Bv_eff ~ 4.2; N Ut = 1 / 32
+# a large emission coefficient (N Ut = 1 / 4): the breakdown mirror is taken below -Bv_eff + 10 N Ut = -Bv_eff + 2.5 V, so the mirrored
+# Ud_0 = -(Ud + Bv_eff) goes down to -2.5 V, below the clipping levels of the "small" arm (-1 - Ud_1 and 2 Ud_1 - 1, at or below -1 V); with
+# the two sets above (10 N Ut = 0.26 V and 0.31 V) the mirrored small arm never clips.  Bv_eff ~ 5.67, Uth ~ 7.6
+D_WIDE = (1e-14, _emission_for(2.0 ** -2), 0.0, 2.0 * _emission_for(2.0 ** -2), 27.0, 1e-3, 12.0, 1.0, 1.0, 0.0)
+MOS_PAR = {"l0": (2e-3, 0.0, 1.0), "l1": (2e-3, 0.02, 1.0)}
+BJT_PAR = (1e-16, 1.0, 100.0, 27.0, 1.0)
+
+
+def nl_cells():
+    """D (default), D (breakdown set), D (breakdown with a large N), NMOS / PMOS with lambda 0 and > 0 on three driven pins, NMOS / PMOS with the source on ground,
+    NPN / PNP on three driven pins and with the emitter on ground"""
+    c = Cells()
+    dev = []
+    for name, par in (("D default", D_DEFAULT), ("D breakdown", D_BREAK), ("D wide", D_WIDE)):
+        a, k = c.pin(), c.pin()
+        c.deck.add("D", (a, k), *par)
+        dev.append(("D", name, (a, k), par))
+    for kind in ("NMOS", "PMOS"):
+        for lt, par in MOS_PAR.items():
+            n = (c.pin(), c.pin(), c.pin())
+            c.deck.add(kind, n, *par)
+            dev.append((kind, f"{kind} {lt}", n, par))
+        n = (c.pin(), c.pin(), 0)
+        c.deck.add(kind, n, *MOS_PAR["l1"])
+        dev.append((kind, f"{kind} source on ground", n, MOS_PAR["l1"]))
+    for kind in ("NPN", "PNP"):
+        n = (c.pin(), c.pin(), c.pin())
+        c.deck.add(kind, n, *BJT_PAR)
+        dev.append((kind, kind, n, BJT_PAR))
+        n = (c.pin(), c.pin(), 0)
+        c.deck.add(kind, n, *BJT_PAR)
+        dev.append((kind, f"{kind} emitter on ground", n, BJT_PAR))
+    return c, dev
+
+
+def _on_quotient(q, den):
+    """a double Ud with fl(Ud / den) == q exactly if one of the neighbours of q * den has it, else q * den (then the point and its
+    neighbours straddle the limit without landing on it; the arms that need the limit itself come from the power-of-two N Ut)"""
+    u = q * den
+    for k in range(-4, 5):
+        cand = float(u + k * math.ulp(u))
+        if cand / den == q:
+            return cand
+    return float(u)
+
+
+def _around(v):
+    return [float(np.nextafter(v, -math.inf)), float(v), float(np.nextafter(v, math.inf))]
+
+
+def diode_points(par):
+    """junction voltages of the one-iteration forms (exact inputs): on and one ulp to either side of every predicate boundary"""
+    p = diode_prepared(par)
+    Ute, Uter, Bv_eff = p[2], p[3], p[5]
+    pts = [0.0, 0.3, 0.65, -0.5, -0.75 * Bv_eff, -Bv_eff - 0.5]
+    for den in (Ute, Uter):
+        for q in (50.0, -50.0):
+            pts += _around(_on_quotient(q, den))      # (on the limit where a double has that quotient, else the two that straddle it)
+    pts += _around(-Bv_eff)
+    pts += _around(min(0.0, -Bv_eff + 10.0 * Ute))
+    if par[7] != 0.0:      # the breakdown exponential on its upper limit: searched through the whole TR1 path (mirror included)
+        u0 = -Bv_eff - 50.0 * Ute
+        for k in range(-300, 300):
+            u = float(u0 + k * math.ulp(u0))
+            ref, arms = DiodeRef(p), set()
+            ref.companion(u, DT)
+            ref.eval(u, True, arms)
+            if "limexp breakdown: x on +50" in arms:
+                pts += _around(u)
+                break
+        else:
+            pts += _around(u0)      # (no double lands on it with this N Ut: the two sides)
+    return pts
+
+
+def diode_pairs(par):
+    """(Ud_1, Ud_0) of the two-iteration form, every arm of vlimit, off the predicate boundaries"""
+    p = diode_prepared(par)
+    Bv = p[5]
+    pairs = [(0.3, 0.9), (1.2, 0.8), (-0.5, 0.9), (0.5, -3.0), (-0.2, -3.0), (0.2, 0.25), (-1.0, -1.5), (0.0, 0.6)]
+    if par[7] != 0.0:
+        pairs += [(-Bv - 0.3, -Bv - 0.9), (-Bv - 1.2, -Bv - 0.8), (-3.0, -Bv - 0.9), (-Bv - 0.2, -Bv - 0.25), (-Bv - 0.2, -Bv + 0.1), (0.4, -Bv - 0.3)]
+        if 10.0 * p[2] > 1.5:
+            # mirrored Ud_0 = -1.5 below the clipping level -1.2, from Ud_1 = 0.2 (-1 - Ud_1) and from Ud_1 = -0.1 (2 Ud_1 - 1): both return
+            # -Bv_eff + 1.2; the first iteration (Ud == Ud_last, mirrored, small, not clipped) leaves Ud_last where it was set
+            pairs += [(-Bv - 0.2, -Bv + 1.5), (-Bv + 0.1, -Bv + 1.5)]
+    return pairs
+
+
+VLIMIT_ARMS = ["vlimit: Ud_1 > 0, arg > 0", "vlimit: Ud_1 > 0, arg < 0", "vlimit: Ud_1 <= 0, Ute log(Ud_0 / Ute)", "vlimit: small, clipped, Ud_1 > 0",
+               "vlimit: small, clipped, Ud_1 <= 0", "vlimit: small, not clipped", "vlimit: mirrored Ud_1 > 0, arg > 0", "vlimit: mirrored Ud_1 > 0, arg < 0",
+               "vlimit: mirrored Ud_1 <= 0, Ute log(Ud_0 / Ute)", "vlimit: mirrored small, clipped, Ud_1 > 0", "vlimit: mirrored small, clipped, Ud_1 <= 0",
+               "vlimit: mirrored small, not clipped"]
+# (the mirrored small arm clips only where 10 Ute exceeds the clipping levels' 1 V: the cell "D wide")
+ONE_ITER_ARMS = [f"limexp {t}: {a}" for t in ("Ute", "Uter") for a in ("x > 50", "x < -50", "x on +50", "x on -50", "exp")] + [
+    "limexp breakdown: x > 50", "limexp breakdown: x on +50", "limexp breakdown: exp", "diode: Ud on -Bv_eff", "diode: breakdown",
+    "diode: forward / reverse", "diode: forward / reverse with recombination", "vlimit: Ud on the flag threshold"]
+S, X = 0.25, math.ulp(1.25)
+# (Vg, Vd, Vs) of an NMOS with Vth = 1 (the PMOS cells take the negated triple): cut-off, Vov = 0, triode, Vx = Vov and one ulp to either
+# side, saturation, Vx = 0, reversed
+MOS_BIAS = [(0.75, 2.0, S), (1.25, 2.0, S), (2.25, 0.75, S), (2.25, 1.25, S), (2.25, 1.25 - X, S), (2.25, 1.25 + X, S), (2.25, 3.25, S), (2.25, S, S),
+            (2.25, -0.25, S), (1.75, 0.5, S), (3.0, 4.0, S)]
+MOS_ARMS = [f"{t} {lt}: {a}" for t in ("NMOS", "PMOS") for lt in ("lambda = 0", "lambda > 0")
+            for a in ("cut-off", "Vov = 0", "triode", "Vx = Vov", "saturation", "Vx = 0", "reversed")]
+BJT_VJ = [-1.0, -0.3, 0.0, 0.3, 0.6, 0.75, 0.9]
+BJT_ARMS = [f"{t}: {a}" for t in ("NPN", "PNP") for a in ("Vj < 0", "Vj = 0", "Vj > 0")]
+
+
+def nl_volts(c, dev, diode_ud, shift=0):
+    """[B][n_nodes + 1] pin voltages: instance b takes point (b + shift) of every device's own list (lists cycle); diode_ud(par) -> list"""
+    lists = {}
+    for kind, name, n, par in dev:
+        if kind == "D":
+            lists[name] = [(ud + 0.5, 0.5) for ud in diode_ud(par)]      # cathode on 0.5 V: Ud = fl(x_a - x_c), whatever it rounds to
+        elif kind in ("NMOS", "PMOS"):
+            sg = 1.0 if kind == "NMOS" else -1.0
+            lists[name] = [(sg * vd, sg * vg, sg * vs) if n[2] else (sg * (vd - vs), sg * (vg - vs)) for vg, vd, vs in MOS_BIAS]
+        else:
+            sg = 1.0 if kind == "NPN" else -1.0
+            lists[name] = [(sg * (vj + 0.25), sg * 2.0, sg * 0.25) if n[2] else (sg * vj, sg * 2.0) for vj in BJT_VJ]
+    B = max(len(v) for v in lists.values())
+    volts = np.zeros((B, c.deck.n_nodes + 1))
+    for kind, name, n, par in dev:
+        pts = lists[name]
+        for b in range(B):
+            for node, v in zip(n, pts[(b + shift) % len(pts)]):
+                if node:
+                    volts[b, node] = v
+    return volts
+
+
+def check_nl_stamps(e, dev, volts, diodes, tr, W, what):
+    """every device's cells of every instance against the reference at the pin voltages volts[b]; diodes: {(name, b): DiodeRef} (state)"""
+    for b in range(len(volts)):
+        A, rhs = stamped(e, b)
+        v = volts[b]
+        for kind, name, n, par in dev:
+            w = f"{what}, instance {b}, {name}"
+            if kind == "D":
+                a, k = n
+                g, ie, bg, bi = diodes[name, b].eval(v[a] - v[k], tr, W.arms)
+                W.check("diode geq", cell(A, a, a), E(0, g), w, bg)
+                W.check("diode Ieq", -rhs[r(a)], E(0, ie), w, bi)
+                assert cell(A, a, k) == -cell(A, a, a) == cell(A, k, a) == -cell(A, k, k) and rhs[r(k)] == -rhs[r(a)], w
+            elif kind in ("NMOS", "PMOS"):
+                d, g_, s = n
+                gds, gm, ieq = ref_mos(kind == "NMOS", v[d], v[g_], v[s], *par, W.arms)
+                W.check(f"{kind} gds", cell(A, d, d), gds, w)
+                W.check(f"{kind} gm", cell(A, d, g_) * (1.0 if kind == "NMOS" else -1.0), gm, w)
+                W.check(f"{kind} Ieq", -rhs[r(d)], ieq, w)
+                if s:
+                    assert cell(A, s, d) == -cell(A, d, d) and cell(A, s, g_) == -cell(A, d, g_) and rhs[r(s)] == -rhs[r(d)], w
+                    assert cell(A, s, s) == cell(A, d, d) + cell(A, d, g_) and cell(A, d, s) == -cell(A, s, s), w
+            else:
+                bb, cc, ee = n
+                npn = kind == "NPN"
+                geq, i1, gm, i2 = ref_bjt(npn, v[bb], v[ee], *bjt_prepared(par), W.arms)
+                sg = 1.0 if npn else -1.0
+                W.check(f"{kind} geq", cell(A, bb, bb), geq, w)
+                W.check(f"{kind} Ij - Vj geq", -sg * rhs[r(bb)], i1, w)
+                W.check(f"{kind} gm", cell(A, cc, bb), gm, w)
+                W.check(f"{kind} BetaF Ij - gm Vj", -sg * rhs[r(cc)], i2, w)
+                if ee:
+                    assert cell(A, cc, ee) == -cell(A, cc, bb) and cell(A, bb, ee) == -cell(A, bb, bb), w
+
+
+def check_nonlinear(knobs, label=""):
+    """DC1, TR1 and TR2 of the diode / MOSFET / BJT cells; returns the Worst record"""
+    c, dev = nl_cells()
+    W = Worst()
+    dpar = {name: par for kind, name, n, par in dev if kind == "D"}
+    # -- one-iteration forms: exact inputs, predicate boundaries
+    volts = nl_volts(c, dev, diode_points)
+    x, vdc = c.tables(volts)
+    B = len(volts)
+    for form in ("DC1", "TR1"):
+        e = engine(c.deck, B, knobs, {"VDC": vdc}, max_newton=1)
+        e.set_solution(x)
+        diodes = {(name, b): DiodeRef(diode_prepared(par)) for name, par in dpar.items() for b in range(B)}
+        if form == "DC1":
+            e.analyze_dc(F.MODE_DC, check=False)
+        else:
+            for kind, name, n, par in dev:
+                if kind == "D":
+                    for b in range(B):
+                        diodes[name, b].companion(volts[b][n[0]] - volts[b][n[1]], DT)
+            e.analyze_tr(DT, 1, check=False)
+        st = statuses_ok(e, form)
+        # here the iterate IS the fixed point (the sources carry the same values): one iteration converges; the cap is met in TR2
+        check_nl_stamps(e, dev, volts, diodes, form == "TR1", W, f"{label} {form}")
+        print(f"{label} {form}: statuses {sorted(set(st.tolist()))}")
+        e.close()
+    W.need(ONE_ITER_ARMS + MOS_ARMS + BJT_ARMS + ["vlimit: Ud_1 <= 0, Ute log(Ud_0 / Ute)", "vlimit: small, clipped, Ud_1 <= 0"], "one-iteration forms")
+    # -- two iterations: the first at the set x (Ud_1), the second on the sources (Ud_0).  The MOSFET / BJT cells take their lists
+    # shifted by three for the set x, so that no instance starts on its fixed point; the diode cells take the two members of pair b
+    v1 = nl_volts(c, dev, lambda par: [p[0] for p in diode_pairs(par)], shift=3)
+    v2 = nl_volts(c, dev, lambda par: [p[1] for p in diode_pairs(par)])
+    B = len(v1)
+    diodes = {(name, b): DiodeRef(diode_prepared(par)) for name, par in dpar.items() for b in range(B)}
+    for kind, name, n, par in dev:
+        if kind == "D":
+            pr = diode_pairs(par)
+            for b in range(B):
+                v1[b, n[0]], v1[b, n[1]] = pr[b % len(pr)][0] + 0.5, 0.5
+                diodes[name, b].companion(v1[b, n[0]] - v1[b, n[1]], DT)
+                diodes[name, b].eval(v1[b, n[0]] - v1[b, n[1]], True, set())      # first iteration: leaves Ud_last
+    x, _ = c.tables(v1)
+    _, vdc = c.tables(v2)
+    e = engine(c.deck, B, knobs, {"VDC": vdc}, max_newton=2)
+    e.set_solution(x)
+    e.analyze_tr(DT, 1, check=False)
+    st = statuses_ok(e, "TR2")
+    sol = e.solution()
+    assert np.array_equal(sol[:, :c.deck.n_nodes], v2[:, 1:]), f"{label} TR2: the nodes are not bitwise on their sources"
+    assert np.count_nonzero(st == NO_CONV) > 0, f"{label} TR2: no instance met the iteration cap"
+    W2 = Worst()
+    check_nl_stamps(e, dev, v2, diodes, True, W2, f"{label} TR2")
+    W2.need(VLIMIT_ARMS + MOS_ARMS + BJT_ARMS, "two-iteration form")
+    e.close()
+    for k, v in W2.ratio.items():      # the diode's two-iteration figures are reported on their own: they carry the bound of the limited voltage
+        if k.startswith("diode"):
+            W.ratio[k + " (limited)"] = v
+        else:
+            W.ratio[k] = max(v, W.ratio.get(k, 0.0))
+    W.arms |= W2.arms
+    W.report(f"{label} non-linear")
+    return W
+
+
+# ---- relay ----------------------------------------------------------------------------------------------------------------------------------
+def check_relay(knobs, label=""):
+    """coil voltage on Von and Voff and one ulp to either side, from both contact states; then a switch inside the second iteration"""
+    VON, VOFF, ROPEN = 5.0, 3.0, 1e12
+    c = Cells()
+    cp, cn, a = c.pin(), c.pin(), c.pin()
+    bnode = c.deck.new_node()
+    c.deck.add("R", (bnode, 0), 100.0)
+    ri = c.deck.add("RELAY", (cp, cn, a, bnode), VON, VOFF)
+    k = branch_rows(c.deck)[ri]
+    pts = [(eng0, v) for eng0 in (0, 1) for v in _around(VON) + _around(VOFF) + [0.0, 8.0]]
+    B = len(pts)
+    W = Worst()
+
+    def volts(coil):
+        v = np.zeros((B, c.deck.n_nodes + 1))
+        v[:, cn], v[:, a] = 0.5, 1.0
+        v[:, cp] = np.asarray(coil) + 0.5
+        return v
+
+    def contact(e, b):
+        A, _ = stamped(e, b)
+        return float(A[k, k])
+
+    def step(eng, vctrl):
+        if not eng:
+            return 1 if vctrl >= VON else 0
+        return 0 if vctrl <= VOFF else 1
+
+    for tr in (False, True):
+        first = volts([8.0 if eng0 else 0.0 for eng0, _ in pts])
+        x, vdc = c.tables(first)
+        e = engine(c.deck, B, knobs, {"VDC": vdc}, max_newton=1)
+        run = (lambda: e.analyze_tr(DT, 1, check=False)) if tr else (lambda: e.analyze_dc(F.MODE_DC, check=False))
+        e.set_solution(x)
+        run()
+        statuses_ok(e, "relay, first call")
+        state = [step(0, first[b, cp] - first[b, cn]) for b in range(B)]
+        assert state == [eng0 for eng0, _ in pts]
+        second = volts([v for _, v in pts])
+        x, _ = c.tables(second)
+        e.set_solution(x)
+        run()
+        statuses_ok(e, "relay, second call")
+        for b, (eng0, v) in enumerate(pts):
+            vc = second[b, cp] - second[b, cn]
+            assert vc == v
+            state[b] = step(state[b], vc)
+            W.arms.add(f"relay: from {'engaged' if eng0 else 'open'}, coil {'on Von' if v == VON else 'on Voff' if v == VOFF else 'off the thresholds'}"
+                       f" -> {'engaged' if state[b] else 'open'}")
+            W.bitwise("relay contact", contact(e, b), -0.0 if state[b] else -ROPEN, f"{label} relay {'TR' if tr else 'DC'}, from state {eng0}, coil {v!r}")
+        e.close()
+    W.need(["relay: from open, coil on Von -> engaged", "relay: from open, coil on Voff -> open", "relay: from engaged, coil on Voff -> open",
+            "relay: from engaged, coil on Von -> engaged", "relay: from open, coil off the thresholds -> engaged", "relay: from engaged, coil off the thresholds -> open"], "relay")
+    # the second iteration of one solve point (the dynamic_only path of the split schedule) moves the contact: set x below, sources above
+    # Von (instances 0, 1) and the reverse from the engaged state (2, 3)
+    for tr in (False, True):
+        B2 = 4
+        v_set = np.zeros((B2, c.deck.n_nodes + 1))
+        v_set[:, cn], v_set[:, a] = 0.5, 1.0
+        v_src = v_set.copy()
+        v_set[:, cp] = np.array([0.0, 4.0, 8.0, 8.0]) + 0.5
+        v_src[:, cp] = np.array([8.0, 5.0, 0.0, 4.0]) + 0.5
+        x, _ = c.tables(v_set)
+        _, vdc = c.tables(v_src)
+        e = engine(c.deck, B2, knobs, {"VDC": vdc}, max_newton=2)
+        e.set_solution(x)
+        (e.analyze_tr(DT, 1, check=False) if tr else e.analyze_dc(F.MODE_DC, check=False))
+        statuses_ok(e, "relay, two iterations")
+        sol = e.solution()
+        assert np.array_equal(sol[:, r(cp)], v_src[:, cp]) and np.array_equal(sol[:, r(cn)], v_src[:, cn])
+        for b in range(B2):
+            s1 = step(0, v_set[b, cp] - v_set[b, cn])
+            s2 = step(s1, v_src[b, cp] - v_src[b, cn])
+            W.bitwise("relay contact", contact(e, b), -0.0 if s2 else -ROPEN, f"{label} relay, second iteration, instance {b}")
+        e.close()
+    W.report(f"{label} relay")
+    return W
+
+
+# ---- time sources ---------------------------------------------------------------------------------------------------------------------------
+T0 = 3.0 / 1024.0
+# per instance: freq, duty, phase, tr, tf of the generators; omega, phase of IAC / VAC
+SRC_ROWS = [
+    (1024.0, 0.5, 0.0, 2.0 ** -13, 2.0 ** -13, 2.0 * math.pi * 50.0, 0.0),         # t = 3 T: tm_ = 0; one ulp below: tm_ just under T
+    (512.0, 0.5, 0.0, 2.0 ** -13, 2.0 ** -13, 1e4, 0.3),                           # t = 1.5 T: tm_ = T / 2 = duty T
+    (256.0, 0.75, 0.0, 2.0 ** -13, 2.0 ** -12, 1e4, -2.0),                         # t = 0.75 T = duty T
+    (256.0, 0.75 + 2.0 ** -4, 0.0, 2.0 ** -13, 2.0 ** -12, 1e4, 7.5),              # tm_ = Ton - tf
+    (1000.0, 0.3, -30.0, 2e-5, 3e-5, 1e6 / T0, 0.0),                               # phase negative: fmod returns a negative tm_; omega t ~ 1e6
+    (1000.0, 0.3, 7.5, 2e-5, 3e-5, 1e6 / T0, 1.0),                                 # phase above 2 pi
+    (1000.0, 0.0, 0.4, 2e-5, 3e-5, 3e6 / T0, -1.0),                                # duty 0
+    (1000.0, 1.0, 0.4, 2e-5, 3e-5, 1e3, 0.5),                                      # duty 1
+    (700.0, 0.5, 0.0, 0.0, 0.0, 1e3, 0.5),                                         # tr = tf = 0, t = 0 in the DC modes: tm_ = 0
+    (3000.0, 0.5, 0.2, 2e-5, 3e-5, 2.0 * math.pi * 1e3, 0.5),
+    (3000.0, 0.05, 3.0, 2e-5, 3e-5, 2.0 * math.pi * 1e3, 0.5),                     # pulse: falling edge / low
+]
+SRC_ARMS = ["SAW: tm_ < 0", "SAW: tm_ = 0", "SQR: tm_ = duty T", "SQR: high", "SQR: low", "PULSE: rising", "PULSE: high", "PULSE: tm_ = Ton - tf",
+            "PULSE: falling", "PULSE: low", "TRI: tm_ = T / 2", "TRI: up", "TRI: down", "TRI: tm_ < 0", "SQR: tm_ < 0", "PULSE: tm_ < 0"]
+
+
+def check_sources(knobs, label=""):
+    VH, VL, AMP = 5.0, -1.0, 2.0
+    d = pe.deck.Deck()
+    d.n_nodes = 8
+    gi = [d.add("SAW", (1, 0)), d.add("SQR", (2, 0)), d.add("PULSE", (3, 0)), d.add("TRI", (4, 0))]
+    vi = d.add("VAC", (5, 0))
+    d.add("IAC", (6, 7))
+    d.add("VAC", (0, 8))          # a pin on ground on the other side
+    for n in range(1, 9):
+        d.add("R", (n, 0), 100.0 * n)
+    br = branch_rows(d)
+    B = len(SRC_ROWS)
+    gen = np.zeros((B, 4, 8))
+    vac = np.zeros((B, 2, 3))
+    iac = np.zeros((B, 1, 3))
+    for b, (f, duty, ph, trise, tfall, om, sph) in enumerate(SRC_ROWS):
+        for k in range(4):
+            gen[b, k] = (k, VH, VL, f * (k + 1) if b >= 4 else f, duty, ph, trise, tfall)
+        vac[b, 0] = (AMP, om, sph)
+        vac[b, 1] = (AMP, om * 0.37, sph + 0.1)
+        iac[b, 0] = (1e-3, om, sph)
+    ov = {"VGEN": gen, "VAC": vac, "IAC": iac}
+    W = Worst()
+    runs = [("TR", T0), ("TR", float(np.nextafter(T0, 0.0))), ("TR", 0.0123), ("DC", 0.0), ("OP", 0.0), ("TROP", 0.0)]
+    for mode, t in runs:
+        e = engine(d, B, knobs, ov)
+        if mode == "TR":
+            st = e.analyze_tr(t, 1, check=False)
+        else:
+            st = e.analyze_dc({"DC": F.MODE_DC, "OP": F.MODE_OP, "TROP": F.MODE_TROP}[mode], check=False)
+        assert st["rc"] == 0, (mode, t, st)
+        assert np.all(e.state()["t"] == t)
+        for b in range(B):
+            _, rhs = stamped(e, b)
+            w = f"{label} {mode} t = {t!r}, instance {b}"
+            for k in range(4):
+                ref = ref_generator(k + 1, gen[b, k, 1:], t, W.arms)
+                name = ("SAW", "SQR", "PULSE", "TRI")[k]
+                if ref.e == 0:
+                    W.bitwise(name, rhs[br[gi[k]]], ref.d, w)
+                else:
+                    W.check(name, rhs[br[gi[k]]], ref, w)
+            for k, dev_i in enumerate((vi, vi + 2)):
+                if mode in ("TR", "TROP"):
+                    W.check("VAC", rhs[br[dev_i]], ref_sine(vac[b, k], t), w)
+                    W.arms.add(f"VAC: {mode}")
+                else:
+                    W.bitwise("VAC", rhs[br[dev_i]], 0.0, w)
+            if mode in ("TR", "TROP"):
+                ref = ref_sine(iac[b, 0], t)
+                W.check("IAC", -rhs[r(6)], ref, w)
+                W.bitwise("IAC", rhs[r(7)], -rhs[r(6)], w)
+                if max(abs(om * t) for *_, om, _ in [SRC_ROWS[b]]) > 9e5:
+                    W.arms.add("sine: omega t ~ 1e6")
+            else:
+                W.bitwise("IAC", rhs[r(6)], 0.0, w)
+                W.bitwise("IAC", rhs[r(7)], 0.0, w)
+                W.arms.add(f"IAC: 0 in {mode}")
+        e.close()
+    W.need(SRC_ARMS + ["VAC: TR", "VAC: TROP", "IAC: 0 in DC", "IAC: 0 in OP", "sine: omega t ~ 1e6"], "time sources")
+    W.report(f"{label} time sources")
+    return W
+
+
+# ---- trapezoidal companions -----------------------------------------------------------------------------------------------------------------
+def check_companions(knobs, label=""):
+    """C, L, KL with k = 0 and k = 0.99 and a diode with tt > 0 through three steps dt, dt / 8, 3 dt / 8 (the analysis API refuses dt = 0).
+    Each step's reference takes the previous solution as the engine returned it (the doubles the device reads) and carries hist / prevg
+    with their bounds.  Instance b scales every parameter and the start vector by 1 + b / 8."""
+    dt1 = 1e-6
+    c = Cells()
+    d = c.deck
+    n1, n2 = c.pin(), c.pin()
+    d.add("C", (n1, n2), 1e-7)
+    n3 = c.pin()
+    n4 = d.new_node()
+    d.add("R", (n4, 0), 50.0)
+    li = d.add("L", (n3, n4), 1e-3)
+    kl = []
+    for kc in (0.0, 0.99):
+        p1 = c.pin()
+        p2, s1 = d.new_node(), d.new_node()
+        d.add("R", (p2, 0), 10.0)
+        d.add("R", (s1, 0), 20.0)
+        kl.append((d.add("KL", (p1, p2, s1, 0), 1e-3, 4e-3, kc), (p1, p2, s1, 0), kc))
+    a, k = c.pin(), c.pin()
+    dpar = D_DEFAULT[:9] + (1e-8,)
+    d.add("D", (a, k), *dpar)
+    # two time sources beside the diode: their values are x-independent, so the later (dynamic_only) iterations of the split schedule
+    # keep what the first iteration of the point wrote
+    PULSE, VAC = (5.0, -1.0, 3e5, 0.5, 0.2, 2e-7, 3e-7), (2.0, 2.0 * math.pi * 1e5, 0.3)
+    ng, nv = d.new_node(), d.new_node()
+    gi = d.add("PULSE", (ng, 0), *PULSE)
+    vi = d.add("VAC", (nv, 0), *VAC)
+    d.add("R", (ng, 0), 1e3)
+    d.add("R", (nv, 0), 1e3)
+    br = branch_rows(d)
+    B = 3
+    scale = 1.0 + np.arange(B) / 8.0
+    volts = np.zeros((B, d.n_nodes + 1))
+    for n, v in ((n1, 2.0), (n2, 0.5), (n3, 1.0), (kl[0][1][0], 1.5), (kl[1][1][0], -0.75), (a, 0.9), (k, 0.25)):
+        volts[:, n] = v * scale
+    volts[:, a] = 0.25 * scale + 0.65            # forward 0.65 V on every instance
+    _, vdc = c.tables(volts)
+    cap = (1e-7 * scale)[:, None, None]
+    ind = (1e-3 * scale)[:, None, None]
+    klp = np.array([[[1e-3 * s, 4e-3 / s, kc] for _, _, kc in kl] for s in scale])
+    e = engine(d, B, knobs, {"VDC": vdc, "C": cap, "L": ind, "KL": klp})
+    x0 = np.zeros((B, d.rows))
+    x0[:, :] = (0.1 + 0.05 * np.arange(d.rows))[None, :] * scale[:, None]      # start: nothing on its source, currents non-zero
+    e.set_solution(x0)
+    W = Worst()
+    st = [dict(c_hist=E(0.0), c_prevg=E(0.0), diode=DiodeRef(diode_prepared(dpar))) for _ in range(B)]
+    xp = x0
+    assert e.analyze_tr(0.0, 1, check=False)["rc"] == F.ERR_ARG      # a step of dt = 0 is refused: that arm of companion_update is not reachable
+    t = 0.0
+    for step, dt in enumerate((dt1, dt1 / 8.0, 3.0 * dt1 / 8.0)):
+        rs = e.analyze_tr(dt, 1, check=False)
+        assert rs["rc"] == 0, (step, rs)
+        t = t + dt
+        assert np.all(e.state()["t"] == t)
+        x = e.solution()
+        n_it = int(e.newton_trace()[-1])
+        assert n_it >= 2, n_it
+        for b in range(B):
+            A, rhs = stamped(e, b)
+            w = f"{label} companions, step {step} (dt {dt!r}), instance {b}"
+            vol = lambda n: xp[b, r(n)] if n else 0.0
+            s = st[b]
+            # capacitor: g = 2 C / dt is one rounding (2 C is exact): bitwise; hist = -(g + prevg) v - hist
+            g = E(2.0 * cap[b, 0, 0] / dt)
+            s["c_hist"] = -(g + s["c_prevg"]) * (vol(n1) - vol(n2)) - s["c_hist"]
+            s["c_prevg"] = g
+            W.bitwise("C 2C/dt", cell(A, n1, n1), g.d, w)
+            W.check("C hist", -rhs[r(n1)], s["c_hist"], w)
+            W.bitwise("C hist", rhs[r(n2)], -rhs[r(n1)], w)
+            # inductor: req = 2 L / dt bitwise; ueq = -v - req i
+            req = E(2.0 * ind[b, 0, 0] / dt)
+            ueq = -E(vol(n3) - vol(n4)) - req * xp[b, br[li]]
+            W.bitwise("L 2L/dt", A[br[li], br[li]], -req.d, w)
+            W.check("L ueq", rhs[br[li]], ueq, w)
+            # coupled inductors
+            for q, (di, nn, kc) in enumerate(kl):
+                L1, L2 = klp[b, q, 0], klp[b, q, 1]
+                M = kc * f_sqrt(E(L1) * L2)
+                sc = E(2.0) / dt
+                r11, r12, r22 = sc * L1, sc * M, sc * L2
+                i1, i2 = xp[b, br[di]], xp[b, br[di] + 1]
+                u1 = -E(vol(nn[0]) - vol(nn[1])) - (r11 * i1 + r12 * i2)
+                u2 = -E(vol(nn[2]) - vol(nn[3])) - (r12 * i1 + r22 * i2)
+                k0 = br[di]
+                nm = f"KL k={kc}"
+                W.check(nm + " r", -A[k0, k0], r11, w)
+                W.check(nm + " r", -A[k0, k0 + 1], r12, w)
+                W.bitwise(nm + " r", A[k0 + 1, k0], A[k0, k0 + 1], w)
+                W.check(nm + " r", -A[k0 + 1, k0 + 1], r22, w)
+                W.check(nm + " u", rhs[k0], u1, w)
+                W.check(nm + " u", rhs[k0 + 1], u2, w)
+            # diode with tt: the companion takes the previous solution, every iteration the sources' 0.65 V (Ud_last == Ud from the first on)
+            dio = s["diode"]
+            dio.companion(vol(a) - vol(k), dt)
+            for it in range(n_it):      # (from the second iteration on Ud_last == Ud: evaluating again changes nothing)
+                vd = (vol(a) - vol(k)) if it == 0 else (x[b, r(a)] - x[b, r(k)])
+                g_, ie, bg, bi = dio.eval(vd, True, W.arms)
+            W.check("PULSE after later iterations", rhs[br[gi]], ref_generator(3, PULSE, t, W.arms), w)
+            W.check("VAC after later iterations", rhs[br[vi]], ref_sine(VAC, t), w)
+            W.check("diode tt g", cell(A, a, a), E(0, g_), w, bg)
+            W.check("diode tt ie", -rhs[r(a)], E(0, ie), w, bi)
+        assert np.array_equal(x[:, r(a)], volts[:, a]) and np.array_equal(x[:, r(k)], volts[:, k])
+        xp = x
+    W.need(["diode: diffusion companion summed"], "companions")
+    e.close()
+    W.report(f"{label} companions")
+    return W
+
+
+# ---- strided loops that wrap, the 128-VGPR build, instance order ---------------------------------------------------------------------------
+def check_wrap(knobs, label=""):
+    """WRAP_CELLS diode cells (tt > 0) and as many NMOS cells (three more than the larger of PE_THREADS and k_m2_eval's workgroup, both read
+    from the kernel sources), batch 3, every cell and instance on a bias of its own: the device loops of the resident kernel and of
+    k_m2_eval at one workgroup wrap, and the companion fused into k_m2_eval writes the
+    state its own thread reads.  Two TR steps with max_newton = 1: the second stamps geq(x1) + prevg(geq(x0)) and Ieq + hist."""
+    N, B = WRAP_CELLS, 3
+    c = Cells()
+    d = c.deck
+    gate = c.pin()
+    dn, mn = [], []
+    dpar = D_DEFAULT[:9] + (1e-8,)
+    for i in range(N):
+        a = c.pin()
+        d.add("D", (a, 0), *dpar)
+        dn.append(a)
+    for i in range(N):
+        n = c.pin()
+        d.add("NMOS", (n, gate, 0))
+        mn.append(n)
+    assert d.rows == 4 * N + 2
+    u = pe.deck.uniform01(7, 4 * N * B).reshape(4, B, N)
+    mos = np.zeros((B, N, 3))
+    mos[:, :, 0], mos[:, :, 1], mos[:, :, 2] = 1e-3 * (1.0 + u[0]), 0.05 * u[1], 0.5 + 2.0 * u[2]     # Vth 0.5 .. 2.5 around the gate's 1.5 V
+    W = Worst()
+    steps = []
+    for s in range(2):
+        v = np.zeros((B, d.n_nodes + 1))
+        us = pe.deck.uniform01(11 + s, 2 * N * B).reshape(2, B, N)
+        v[:, gate] = 1.5
+        v[:, dn] = -0.5 + 1.2 * us[0]           # -0.5 .. 0.7 V
+        v[:, mn] = -0.5 + 3.0 * us[1]
+        steps.append(v)
+    _, vdc = c.tables(steps[1])
+    e = engine(d, B, knobs, {"VDC": vdc, "NMOS": mos}, max_newton=1)
+    dio = [[DiodeRef(diode_prepared(dpar)) for _ in range(N)] for _ in range(B)]
+    for s, v in enumerate(steps):
+        x, _ = c.tables(v)
+        e.set_solution(x)
+        e.analyze_tr(DT, 1, check=False)
+        statuses_ok(e, f"wrap, step {s}")
+        for b in range(B):
+            for i in range(N):
+                dio[b][i].companion(v[b, dn[i]], DT)
+                dio[b][i].out = dio[b][i].eval(v[b, dn[i]], True, W.arms)
+    for b in range(B):
+        A, rhs = stamped(e, b)
+        diag = A.diagonal()
+        col_gate = np.asarray(A[:, r(gate)].todense()).ravel()
+        v = steps[1][b]
+        for i in range(N):
+            w = f"{label} wrap, instance {b}, cell {i}"
+            g, ie, bg, bi = dio[b][i].out
+            W.check("diode geq", diag[r(dn[i])], E(0, g), w, bg)
+            W.check("diode Ieq", -rhs[r(dn[i])], E(0, ie), w, bi)
+            gds, gm, ieq = ref_mos(True, v[mn[i]], v[gate], 0.0, *mos[b, i], W.arms)
+            W.check("NMOS gds", diag[r(mn[i])], gds, w)
+            W.check("NMOS gm", col_gate[r(mn[i])], gm, w)
+            W.check("NMOS Ieq", -rhs[r(mn[i])], ieq, w)
+    W.need(["diode: diffusion companion summed", "NMOS lambda > 0: cut-off", "NMOS lambda > 0: triode", "NMOS lambda > 0: saturation", "NMOS lambda > 0: reversed"], "wrap")
+    info = e.info()
+    e.close()
+    W.report(f"{label} wrap")
+    return W, info
+
+
+def small_cells():
+    c = Cells()
+    a = c.pin()
+    c.deck.add("D", (a, 0), *D_BREAK)
+    dn, gn = c.pin(), c.pin()
+    c.deck.add("NMOS", (dn, gn, 0), *MOS_PAR["l1"])
+    return c, a, dn, gn
+
+
+def check_batch_384(knobs, label=""):
+    """a 6-row deck at batch 384: the resident kernels' 128-VGPR build (pe_engine_policy.cpp symbolic_options: batch >= 384 shares a CU
+    between two workgroups).  info() does not name the build; it shows the halved LDS share that goes with it, which is asserted against
+    a batch of 3 -- beyond that the test relies on the policy line `batch >= 384`.  Instance order: the bias of instance 0 again at 5, 200
+    and 383 gives bitwise-equal stamps."""
+    c, a, dn, gn = small_cells()
+    B = 384
+    ud = np.linspace(-5.0, 0.8, B)
+    volts = np.zeros((B, c.deck.n_nodes + 1))
+    volts[:, a], volts[:, dn], volts[:, gn] = ud, np.linspace(-0.5, 3.0, B)[::-1], 1.0 + 1.5 * pe.deck.uniform01(3, B)
+    same = (5, 200, 383)
+    for b in same:
+        volts[b] = volts[0]
+    x, vdc = c.tables(volts)
+    W = Worst()
+    e = engine(c.deck, B, knobs, {"VDC": vdc}, max_newton=1)
+    e.set_solution(x)
+    e.analyze_tr(DT, 1, check=False)
+    statuses_ok(e, "batch 384")
+    lds = e.info()["lds_bytes"]
+    A0 = None
+    for b in range(B):
+        A, rhs = stamped(e, b)
+        w = f"{label} batch 384, instance {b}"
+        dio = DiodeRef(diode_prepared(D_BREAK))
+        dio.companion(volts[b, a], DT)
+        g, ie, bg, bi = dio.eval(volts[b, a], True, W.arms)
+        W.check("diode geq", cell(A, a, a), E(0, g), w, bg)
+        W.check("diode Ieq", -rhs[r(a)], E(0, ie), w, bi)
+        gds, gm, ieq = ref_mos(True, volts[b, dn], volts[b, gn], 0.0, *MOS_PAR["l1"], W.arms)
+        W.check("NMOS gds", cell(A, dn, dn), gds, w)
+        W.check("NMOS gm", cell(A, dn, gn), gm, w)
+        W.check("NMOS Ieq", -rhs[r(dn)], ieq, w)
+        if b == 0:
+            A0 = (A.data.copy(), rhs.copy())
+        if b in same:
+            assert np.array_equal(A.data, A0[0]) and np.array_equal(rhs, A0[1]), f"{w}: differs from instance 0 on the same bias"
+    e.close()
+    e = engine(c.deck, 3, knobs, {"VDC": vdc[:3]}, max_newton=1)
+    e.set_solution(x[:3])
+    e.analyze_tr(DT, 1, check=False)
+    lds3 = e.info()["lds_bytes"]
+    e.close()
+    assert lds < lds3, f"batch 384 runs with the LDS share of a batch of 3 ({lds} / {lds3} bytes): not the shared-CU geometry"
+    W.report(f"{label} batch 384")
+    return W
+
+
+# ---- the float64 oracle as the second implementation ----------------------------------------------------------------------------------------
+def check_oracle_within_bound(oracle_mod, which):
+    """the bound is a condition on the inputs as well: oracle/pe_oracle.py's float64 formulas stay within it at every chosen point (a point
+    where they do not is a badly chosen point -- or a disagreement between two implementations).  which = "formulas": the diode and
+    generator functions called directly at the one-iteration points; any other: that check of this module on OracleEngine -- the same
+    decks, bias sets, forms and arms as on the device (the batch-384 deck is left out: its points are a subset of the kinds covered)."""
+    if which != "formulas":
+        return {"nonlinear": check_nonlinear, "relay": check_relay, "sources": check_sources, "companions": check_companions,
+                "wrap": lambda k, l: check_wrap(k, l)[0]}[which]({"ORACLE": oracle_mod}, "oracle")
+    W = Worst()
+    for par in (D_DEFAULT, D_BREAK, D_WIDE):
+        for form in ("DC1", "TR1"):
+            for ud in diode_points(par):
+                o = oracle_mod.Diodes([0], [-1], [par])
+                o.prepare_foundation(np.zeros(1))
+                assert [float(o.Is_eff[0]), float(o.Isr_eff[0]), float((o.N * o.Ut)[0]), float((o.Nr * o.Ut)[0]), float(o.Uth[0]), float(o.Bv_eff[0])] == diode_prepared(par)[:6]
+                ref = DiodeRef(diode_prepared(par))
+                if form == "TR1":
+                    o.step_changed_tr(np.array([ud]), DT, np.array([True]))
+                    ref.companion(ud, DT)
+                geq, Ieq = o.iterate_dc(np.array([ud]))
+                g, ie, bg, bi = ref.eval(ud, form == "TR1", W.arms)
+                W.check("oracle diode geq", geq[0], E(0, g), f"{form} Ud {ud!r}", bg)
+                W.check("oracle diode Ieq", Ieq[0], E(0, ie), f"{form} Ud {ud!r}", bi)
+    for t in (T0, float(np.nextafter(T0, 0.0)), 0.0123, 0.0):
+        for f, duty, ph, trise, tfall, _, _ in SRC_ROWS:
+            p = (5.0, -1.0, f, duty, ph, trise, tfall)
+            for k, name in enumerate(("SAW", "SQR", "PULSE", "TRI")):
+                op = {"SAW": (5.0, -1.0, f, ph), "SQR": (5.0, -1.0, f, duty, ph), "PULSE": p, "TRI": (5.0, -1.0, f, ph)}[name]
+                ref = ref_generator(k + 1, p, t, W.arms)
+                got = oracle_mod._generator_value(name, op, t)
+                W.check("oracle " + name, got, ref, f"t {t!r} {p}") if ref.e else W.bitwise("oracle " + name, got, ref.d, f"t {t!r} {p}")
+    W.report("oracle")
+    return W
