@@ -373,6 +373,80 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
 /* phasors of the last sweep, in the CALLER's point order: re / im [n_points][count][n_kept_rows]; a failed point reads NaN */
 int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* re, double* im);
 
+/* ---- DC sweep (.DC): the operating point at every value of one swept parameter, as one call.  The points become extra instances of the
+ * circuit on an engine of its own (batch = instances of the circuit x points per pass); the swept value is written on the device, the
+ * kept rows come back in one copy.  THE MAIN ENGINE IS READ, NEVER WRITTEN: its solution, parameters, time, status, counters, Newton
+ * trace, probes and any stored AC / noise sweep are the same bits before and after the call.
+ *   Swept parameter.  kind / index / column as pe_hip_update_param names them: PE_HIP_VDC column 0, PE_HIP_IDC column 0, or PE_HIP_R column
+ *   0 (the engine holds 1.0 / r, divided on the host exactly as pe_hip_update_param does).  Anything else: PE_HIP_ERR_ARG.  A device with
+ *   an unconnected pin sweeps nothing -- every point is then the same solve.  values: any order, duplicates and mixed signs allowed; the
+ *   same value goes to every instance of the batch.  Every call takes the main engine's CURRENT parameters, options and knobs (a
+ *   pe_hip_update_param between two sweeps takes effect; the sweep engine is rebuilt after one), its time and last step.
+ *   PE_HIP_DC_SWEEP_PARALLEL.  Every point starts from the main engine's current state of its instance (solution, junction state, relay
+ *   contacts, device value vector) and is the solve that pe_hip_update_param with that value followed by pe_hip_analyze_dc would make from
+ *   there.  Without continuation the result does not depend on the pass size but through the summation order of the launch geometry.
+ *   continuation = 1 (natural-parameter continuation).  After each solve a pair (point, instance) fails when its status is not PE_HIP_OK or its
+ *   solution is not finite.  Each failing pair is reseeded -- solution and junction state copied -- from the converged point of the SAME
+ *   instance that is nearest in sorted-value position within the pass, where equal values share a position (distance 0); a tie goes to the
+ *   lower position.  Only reseeded pairs are solved again; a converged pair is never solved twice.  The rounds of a pass end when nothing
+ *   fails, when a round converges no new pair, or after max_rounds (<= 0: the points of the pass).  Neighbours are searched inside the
+ *   pass only, so with continuation a point's status may depend on the pass size; it is deterministic for a given one.  The host reads one
+ *   small record per round and no solution.
+ *   PE_HIP_DC_SWEEP_TRACE.  The classical .DC: the points run one after another in the CALLER's order, each from the state the last
+ *   converged point left (the first from the main engine's state), so an up-down list traces a relay's hysteresis loop.  A failed point
+ *   reads NaN and the next one starts from the last converged state (a shadow copy per instance on the sweep engine).  continuation and
+ *   max_rounds are ignored.
+ *   Refusals (PE_HIP_ERR_ARG, nothing changed, a stored sweep stays readable): no circuit, n_points < 1, values or the control NULL, a
+ *   non-finite value, r == 0 for PE_HIP_R, a mode other than PE_HIP_MODE_OP / PE_HIP_MODE_DC, an unknown order, an index out of range, a
+ *   host-stamp overlay (pe_hip_set_overlay), PARALLEL on a circuit with a PE_HIP_RELAY (its result depends on history: use TRACE).
+ *   Points per pass P.  Knob DC_SWEEP_POINTS (pe_hip_set_knob / PHY_ENGINE_HIP_DC_SWEEP_POINTS, read at every sweep); 0 = automatic: the
+ *   memory budget of pe_hip_analyze_ac_sweep by pe_hip_info.bytes_per_instance of the main engine (four times its circuit arrays while it
+ *   has no symbolic analysis yet), never more than the points or than 65535 instances in all.  Passes take contiguous runs of the sorted
+ *   values; the unused slots of the last pass repeat its last point and are not gathered.  TRACE always runs one point at a time.
+ *   One symbolic analysis serves the sweep engine, on instance 0's values at the first sorted point (TRACE: the first point); the
+ *   residual safety net covers the rest as elsewhere (its re-analyses count in n_analyses).  A sweep engine that is still current -- same
+ *   P, no parameter, option or knob changed since -- is reused with its analysis (n_analyses = 0).
+ * The stored result stays readable until the next DC sweep, pe_hip_set_dc_sweep_rows or pe_hip_load_circuit.  There is no twin on the
+ * multi-device pe_hip_sweep_* handle. */
+#define PE_HIP_DC_SWEEP_PARALLEL 0
+#define PE_HIP_DC_SWEEP_TRACE    1
+typedef struct pe_hip_dc_sweep_control {
+    int kind, index, column; /* the swept parameter, named as pe_hip_update_param names it */
+    int mode;                /* PE_HIP_MODE_OP or PE_HIP_MODE_DC */
+    int order;               /* PE_HIP_DC_SWEEP_PARALLEL | PE_HIP_DC_SWEEP_TRACE */
+    int continuation;        /* PARALLEL only: 1 = reseed failed points (rule above) */
+    int max_rounds;          /* reseeding rounds per pass; <= 0: points of the pass */
+} pe_hip_dc_sweep_control;
+typedef struct pe_hip_dc_sweep_stats {
+    int n_points;             /* as passed */
+    int n_passes;             /* PARALLEL: passes; TRACE: points */
+    int points_per_pass;      /* largest number of points put into one pass */
+    int n_rounds;             /* reseeding rounds of the pass that took most */
+    long long n_failed_cold;  /* (point, instance) pairs not converged after round 0 (TRACE: after their one attempt) */
+    long long n_reseeded;     /* seed copies made by the rounds */
+    long long n_failed;       /* pairs still failing at the end */
+    long long newton_iters;   /* all attempts, summed; an attempt that did not converge counts max_newton */
+    int n_analyses;           /* symbolic analyses of the sweep engine during this call */
+    double gpu_ms;            /* HIP-event time of the passes on the sweep engine's stream */
+} pe_hip_dc_sweep_stats;
+
+/* rows of x = [node voltages ; branch currents] kept for every point of the following DC sweeps; n_rows = 0 / rows = NULL: all rows.
+ * Needs a loaded circuit; dropped by pe_hip_load_circuit.  PE_HIP_ERR_ARG (engine unchanged) for a row out of range.  A stored DC sweep
+ * becomes unreadable (its layout is that of the rows it was made with). */
+int pe_hip_set_dc_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows);
+
+/* The sweep described above.  point_status (may be NULL) receives a pe_hip_status per point: the first failing instance's.  Returns
+ * PE_HIP_OK when every pair converged, else the first failing point's status; the pairs that converged stay readable. */
+int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values, const pe_hip_dc_sweep_control* c, int* point_status,
+                            pe_hip_dc_sweep_stats* stats);
+
+/* results of the last DC sweep in the CALLER's point order: x [n_points][count][n_kept_rows], NaN where the pair failed */
+int pe_hip_get_dc_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* x);
+/* per pair [n_points][count] (each may be NULL): pe_hip_status of its last attempt; Newton iterations of that attempt when it converged
+ * (else 0); seed_point = the caller's index of the point its last attempt started from, -1: the main engine's own state */
+int pe_hip_get_dc_sweep_status(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, int* status, int* newton_iters,
+                               int* seed_point);
+
 /* ---- Small-signal noise analysis (.NOISE): the output noise spectral density of the circuit at its operating point, the share of every
  * device in it, and the integrated noise over the swept band -- by the ADJOINT method: one solve of the transposed small-signal system per
  * frequency point, whatever the number of sources.  With A the complex small-signal matrix of pe_hip_analyze_ac at omega and e the output

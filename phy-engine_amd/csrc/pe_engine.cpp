@@ -330,6 +330,7 @@ void pe_hip_destroy(pe_hip_engine* h)
     if(!h) return;
     (void)hipSetDevice(h->device);
     ac_sweep_drop(h);
+    dc_sweep_drop(h);
     if(h->ac.d_xacc) (void)hipFree(h->ac.d_xacc);
     if(h->ac.d_b0) (void)hipFree(h->ac.d_b0);
     if(h->ac.d_worst) (void)hipFree(h->ac.d_worst);
@@ -359,6 +360,7 @@ int pe_hip_set_options(pe_hip_engine* h, const pe_hip_options* o)
     bool const gmin_changed = o->g_min != h->opt.g_min;
     double const r_open_before = r_open_of(h);
     h->opt = *o;
+    ++h->param_epoch;
     apply_options(h, h->V);
     if(h->loaded && r_open_of(h) != r_open_before)
     {
@@ -394,6 +396,7 @@ int pe_hip_set_knob(pe_hip_engine* h, const char* name, int value)
     if(key.rfind("PHY_ENGINE_HIP_", 0) == 0) key.erase(0, 15);
     if(key.empty()) return fail(h, PE_HIP_ERR_ARG, "set_knob: empty name");
     h->knobs[key] = value;
+    ++h->param_epoch;
     h->sym_class = -1;  // the launch geometry and the symbolic analysis are chosen again at the next analysis
     return PE_HIP_OK;
 }
@@ -435,6 +438,7 @@ int pe_hip_set_overlay(pe_hip_engine* h, int n_cells, const int* rows, const int
 int pe_hip_set_digital_drives(pe_hip_engine* h, int count, const int* node, const double* volt)
 {
     if(!h || count < 0 || (count > 0 && (!node || !volt))) return PE_HIP_ERR_ARG;
+    ++h->param_epoch;
     if(h->loaded)
     {
         // same drives in the same order: only the voltages change; a different set needs pe_hip_load_circuit again
@@ -480,6 +484,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     h->n_refined = h->n_rematched = 0;
     h->sym_pool.release();
     ac_sweep_drop(h);
+    dc_sweep_drop(h);
     if(h->ac.eng)
     {
         if(h->ac.d_xacc) (void)hipFree(h->ac.d_xacc);
@@ -725,6 +730,7 @@ int pe_hip_update_param(pe_hip_engine* h, int kind, int index, int column, const
     if(!h || !h->loaded || !values || index < 0 || column < 0) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     ac_sweep_invalidate(h);
+    ++h->param_epoch;
     auto& hc = h->hc;
     int const B = hc.batch;
     auto val = [&](int b) { return batched ? values[b] : values[0]; };

@@ -79,6 +79,10 @@ namespace
         return PE_HIP_OK;
     }
 
+}  // namespace
+
+namespace pe_eng
+{
     // budget of the automatic pass size: half of the device's free memory, at most 4 GiB -- every band's symbolic analysis allocates the
     // factor storage of the whole batch again, and past a few hundred instances of a large circuit a pass gains nothing (the band's
     // host-side analysis dominates it; measured: DESIGN.md).  Builds without HIP have no such query and take a fixed budget.
@@ -90,11 +94,7 @@ namespace
 #endif
         return 256ll << 20;
     }
-    constexpr long long SWEEP_MAX_INSTANCES = 65535;  // instances of one engine: the y extent of a launch grid
-}  // namespace
 
-namespace pe_eng
-{
     void ac_sweep_drop(pe_hip_engine* h)
     {
         auto& W = h->ac.sweep;

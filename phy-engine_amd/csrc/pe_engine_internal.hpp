@@ -26,6 +26,7 @@
 #include "pe_ac.hpp"
 #include "pe_ac_sweep.hpp"
 #include "pe_circuit.hpp"
+#include "pe_dc_sweep.hpp"
 #include "pe_device.hpp"
 #include "pe_kernels.hpp"
 #include "pe_lte.hpp"
@@ -228,6 +229,27 @@ struct pe_hip_engine
         std::vector<double> res;          // [n_points][batch] densities, then [n_points][batch][n_src] contributions when kept
         std::vector<double> integrated;   // [batch]
     } noise;
+    // DC sweep (pe_hip_analyze_dc_sweep, pe_dc_sweep.hpp): an engine of its own holding this circuit with batch (circuit batch) x P -- the
+    // points of one pass are extra instances --, the buffers of its kernels and the stored result.  The main engine is only read.
+    struct DcSweep
+    {
+        pe_hip_engine* eng{};
+        int P{};                          // slots per pass the engine was built for
+        long long epoch{-1};              // param_epoch of the main engine it was built from (parameters, options, knobs)
+        Pool pass_pool;                   // sized by batch x P
+        Pool res_pool;                    // sized by the sweep: result and per-pair bookkeeping in the caller's order
+        size_t res_pairs{}, res_len{};
+        int* d_keep{};                    // device copy of `rows` (own allocation, reused while large enough)
+        size_t keep_cap{};
+        bool rows_on_device{};
+        pe::DcSweepView V{};
+        std::vector<int> rows;            // pe_hip_set_dc_sweep_rows; empty: all rows
+        bool valid{};
+        int n_points{}, n_keep{}, batch{};
+        std::vector<double> res;          // [n_points][batch][n_keep]
+        std::vector<int> status, iters, seed;  // [n_points][batch]
+    } dcs;
+    long long param_epoch{};  // bumped by whatever changes hc's parameters, the options or the knobs (the DC sweep engine is rebuilt after it)
     std::vector<double> sym_values_override;  // representative |A| values for the row matching (AC engine)
 
     // solve_csr_real seam (separate small state)
@@ -329,6 +351,14 @@ namespace pe_eng PE_ENG_HIDDEN
         h->ac.sweep.valid = false;
         h->noise.valid = false;
     }
+    // budget of a sweep engine's automatic pass size, and the most instances one engine takes (the y extent of a launch grid)
+    long long sweep_memory_budget();
+    constexpr long long SWEEP_MAX_INSTANCES = 65535;
+    // pe_engine_newton.cpp: the DC sweep
+    void dc_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy)
+    // the body of pe_hip_analyze_dc after its argument checks.  clear_status = false: the instances whose status is not OK are left alone
+    // (a subset solve: the DC sweep parks the others)
+    int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status);
     // pe_engine_newton.cpp
     bool has_overlay(pe_hip_engine const* h);
     int overlay_call(pe_hip_engine* h, int event, int mode, double t, double dt, int b = 0);

@@ -651,6 +651,27 @@ namespace pe
             if(S.bytes[p]) std::memcpy(S.dst[p], S.src[p], S.bytes[p]);
         return hipSuccess;
     }
+    // ... and those of the DC sweep (pe_dc_sweep.hpp)
+    hipError_t launch_dc_sweep_fill(hipStream_t, DevView const& V, DcSweepView const& S)
+    {
+        dc_sweep_fill(ProbeHostTeam{}, V, S);
+        return hipSuccess;
+    }
+    hipError_t launch_dc_sweep_seed(hipStream_t, DevView const& V, DcSweepView const& S, bool from_main)
+    {
+        for(int q = 0; q < V.batch; ++q) dc_sweep_seed(ProbeHostTeam{}, V, S, q, from_main);
+        return hipSuccess;
+    }
+    hipError_t launch_dc_sweep_classify(hipStream_t, DevView const& V, DcSweepView const& S, bool reseed)
+    {
+        dc_sweep_classify_serial(V, S, reseed);
+        return hipSuccess;
+    }
+    hipError_t launch_dc_sweep_gather(hipStream_t, DevView const& V, DcSweepView const& S)
+    {
+        for(int q = 0; q < V.batch; ++q) dc_sweep_gather(ProbeHostTeam{}, V, S, q);
+        return hipSuccess;
+    }
 }  // namespace pe
 #endif
 
@@ -1055,11 +1076,15 @@ int pe_hip_get_tr_step_log(pe_hip_engine* h, long long first, int capacity, doub
     return PE_HIP_OK;
 }
 
-int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
+}  // extern "C"
+
+namespace pe_eng
 {
-    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
-    if(mode != PE_HIP_MODE_OP && mode != PE_HIP_MODE_DC && mode != PE_HIP_MODE_TROP) return fail(h, PE_HIP_ERR_ARG, "analyze_dc: mode must be OP, DC or TROP");
-    HIPCHK(h, hipSetDevice(h->device));
+// The solving part of pe_hip_analyze_dc: one OP / DC / TROP point of every instance whose status is OK on the schedule in effect, then the
+// residual safety net's retries.  clear_status: every instance takes part (what pe_hip_analyze_dc does); else the instances that are not OK
+// stay as they are -- the DC sweep solves subsets that way, with the others parked.  Leaves the stream synchronised.
+int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status)
+{
     probe_disarm(h);  // (moves x: ends a probe window)
     ac_sweep_invalidate(h);
     if(st) std::memset(st, 0, sizeof(*st));
@@ -1068,7 +1093,7 @@ int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
     if(h->hc.rows == 0) return PE_HIP_OK;
     int rc = ensure_symbolic(h, false, 0.0);
     if(rc != PE_HIP_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(h->hc.batch) * sizeof(int), h->stream));  // no sticky failure (see analyze_tr)
+    if(clear_status) HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(h->hc.batch) * sizeof(int), h->stream));  // no sticky failure (see analyze_tr)
     std::vector<long long> s0, i0;
     rc = snapshot_counters(h, s0, i0);
     if(rc != PE_HIP_OK) return rc;
@@ -1111,6 +1136,408 @@ int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
         st->dominant_launches = split ? h->dominant_launches : 1;
     }
     return rc;
+}
+
+}  // namespace pe_eng
+
+extern "C" {
+
+int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(mode != PE_HIP_MODE_OP && mode != PE_HIP_MODE_DC && mode != PE_HIP_MODE_TROP) return fail(h, PE_HIP_ERR_ARG, "analyze_dc: mode must be OP, DC or TROP");
+    HIPCHK(h, hipSetDevice(h->device));
+    return dc_solve(h, mode, st, true);
+}
+
+}  // extern "C"
+
+// ---------------- DC sweep: the points of a pass as extra instances of an engine of its own (include/pe_hip.h, pe_dc_sweep.hpp)
+namespace pe_eng
+{
+    void dc_sweep_drop(pe_hip_engine* h)
+    {
+        auto& D = h->dcs;
+        if(D.eng) pe_hip_destroy(D.eng);  // (synchronises its stream first: nothing reads the buffers below any more)
+        D.pass_pool.release();
+        D.res_pool.release();
+        if(D.d_keep) (void)hipFree(D.d_keep);
+        D = pe_hip_engine::DcSweep{};
+    }
+}  // namespace pe_eng
+
+namespace
+{
+    // [batch][n] -> [batch * P][n]: instance b * P + p is a copy of instance b
+    template <class T>
+    void repeat_instances(std::vector<T>& v, int B, int P)
+    {
+        if(v.empty() || P == 1) return;
+        size_t const per = v.size() / static_cast<size_t>(B);
+        std::vector<T> o(v.size() * static_cast<size_t>(P));
+        for(int b = 0; b < B; ++b)
+            for(int p = 0; p < P; ++p) std::copy(v.begin() + b * per, v.begin() + (b + 1) * per, o.begin() + (static_cast<size_t>(b) * P + p) * per);
+        v.swap(o);
+    }
+
+    // the sweep engine: the main engine's circuit with every per-instance array repeated P times, loaded like any circuit (what
+    // sweep_engine_build of pe_engine_ac.cpp does for the AC system), and the buffers sized by its batch.  first_value: what the swept
+    // parameter of instance 0 holds for the symbolic analysis.
+    int dc_sweep_engine_build(pe_hip_engine* h, int P, int kind, int j, double first_value)
+    {
+        auto& D = h->dcs;
+        if(D.eng) pe_hip_destroy(D.eng);
+        D.eng = nullptr;
+        D.P = 0;
+        D.pass_pool.release();
+        if(pe_hip_create(h->device, &D.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_dc_sweep: " + std::string(pe_hip_last_error(nullptr)));
+        pe_hip_engine* const E = D.eng;
+        E->knobs = h->knobs;
+        E->opt = h->opt;
+        E->hc = h->hc;
+        auto& c = E->hc;
+        int const B = h->hc.batch;
+        repeat_instances(c.r_g, B, P);
+        repeat_instances(c.c_cap, B, P);
+        repeat_instances(c.l_ind, B, P);
+        repeat_instances(c.vdc_v, B, P);
+        repeat_instances(c.vac_par, B, P);
+        repeat_instances(c.idc_i, B, P);
+        repeat_instances(c.d_par, B, P);
+        repeat_instances(c.d_raw, B, P);
+        repeat_instances(c.gen_par, B, P);
+        repeat_instances(c.ts_par, B, P);
+        repeat_instances(c.cl_par, B, P);
+        repeat_instances(c.rl_par, B, P);
+        repeat_instances(c.n3_par, B, P);
+        c.batch = B * P;
+        if(j >= 0)
+        {
+            if(kind == PE_HIP_R) c.r_g[static_cast<size_t>(j)] = 1.0 / first_value;
+            else if(kind == PE_HIP_VDC)
+                c.vdc_v[static_cast<size_t>(j)] = first_value;
+            else
+                c.idc_i[static_cast<size_t>(j)] = first_value;
+        }
+        int const rc = finish_load(E);
+        if(rc != PE_HIP_OK) return fail(h, rc, "analyze_dc_sweep: " + E->err);
+        size_t const Q = static_cast<size_t>(B) * P;
+        auto& S = D.V;
+        HIPCHK(h, D.pass_pool.alloc(S.seed_of, Q));
+        HIPCHK(h, D.pass_pool.alloc(S.scan, Q));
+        HIPCHK(h, D.pass_pool.alloc(S.pair_status, Q));
+        HIPCHK(h, D.pass_pool.alloc(S.pair_iters, Q));
+        HIPCHK(h, D.pass_pool.alloc(S.pair_seed, Q));
+        HIPCHK(h, D.pass_pool.alloc(S.rec, 1));
+        D.P = P;
+        D.epoch = h->param_epoch;
+        return PE_HIP_OK;
+    }
+}  // namespace
+
+extern "C" {
+
+int pe_hip_set_dc_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows)
+{
+    if(!h || !h->loaded || n_rows < 0 || (n_rows > 0 && !rows)) return h ? fail(h, PE_HIP_ERR_ARG, "set_dc_sweep_rows: bad arguments or no circuit") : PE_HIP_ERR_ARG;
+    for(int k = 0; k < n_rows; ++k)
+        if(rows[k] < 0 || rows[k] >= h->hc.rows) return fail(h, PE_HIP_ERR_ARG, "set_dc_sweep_rows: row out of range");
+    auto& D = h->dcs;
+    D.rows.assign(rows, rows + n_rows);
+    D.rows_on_device = false;
+    D.valid = false;  // (the stored result has the layout of the rows it was made with)
+    return PE_HIP_OK;
+}
+
+int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values, const pe_hip_dc_sweep_control* c, int* point_status,
+                            pe_hip_dc_sweep_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(n_points < 1 || !values || !c) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: n_points < 1, no values or no control");
+    auto const& hc = h->hc;
+    if(c->mode != PE_HIP_MODE_OP && c->mode != PE_HIP_MODE_DC) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: mode must be OP or DC");
+    if(c->order != PE_HIP_DC_SWEEP_PARALLEL && c->order != PE_HIP_DC_SWEEP_TRACE) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: unknown order");
+    std::vector<int> const* map = c->kind == PE_HIP_R ? &hc.map_r : c->kind == PE_HIP_VDC ? &hc.map_vdc : c->kind == PE_HIP_IDC ? &hc.map_idc : nullptr;
+    if(!map || c->column != 0) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: the swept parameter must be column 0 of a PE_HIP_VDC, PE_HIP_IDC or PE_HIP_R");
+    if(c->index < 0 || c->index >= static_cast<int>(map->size())) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: index out of range");
+    for(int i = 0; i < n_points; ++i)
+        if(!std::isfinite(values[i]) || (c->kind == PE_HIP_R && values[i] == 0.0)) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: a non-finite value, or r == 0");
+    if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: a circuit with a host-stamp overlay cannot be swept on the device");
+    bool const trace = c->order == PE_HIP_DC_SWEEP_TRACE;
+    if(!trace && hc.nRl() > 0) return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: a relay's state depends on history -- use PE_HIP_DC_SWEEP_TRACE");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto& D = h->dcs;
+    D.valid = false;
+    int const B = hc.batch, N = hc.rows;
+    int const K = D.rows.empty() ? N : static_cast<int>(D.rows.size());
+    pe_hip_dc_sweep_stats T{};
+    T.n_points = n_points;
+    size_t const pairs = static_cast<size_t>(n_points) * B;
+    D.res.assign(pairs * K, std::nan(""));
+    D.status.assign(pairs, PE_HIP_OK);
+    D.iters.assign(pairs, 0);
+    D.seed.assign(pairs, -1);
+    auto finish = [&]() -> int
+    {
+        D.n_points = n_points;
+        D.n_keep = K;
+        D.batch = B;
+        D.valid = true;
+        if(stats) *stats = T;
+        int first = PE_HIP_OK;
+        for(int i = 0; i < n_points; ++i)
+        {
+            int st = PE_HIP_OK;
+            for(int b = 0; b < B && st == PE_HIP_OK; ++b) st = D.status[static_cast<size_t>(i) * B + b];
+            if(point_status) point_status[i] = st;
+            if(first == PE_HIP_OK) first = st;
+        }
+        if(first != PE_HIP_OK) return fail(h, first, "analyze_dc_sweep: not every point converged");
+        return PE_HIP_OK;
+    };
+    if(N == 0) return finish();
+
+    // ---- the slots: PARALLEL -- the values sorted ascending (ties in the caller's order), cut into passes of P, the last one padded with its
+    // last point; TRACE -- the caller's order, two slots per point (working copy, shadow)
+    int const j = (*map)[c->index];
+    int const slot = j < 0 ? -1 : (c->kind == PE_HIP_R ? hc.dv_r : c->kind == PE_HIP_VDC ? hc.dv_vdc : hc.dv_idc) + j;
+    auto slot_value = [&](double v) { return c->kind == PE_HIP_R ? 1.0 / v : v; };
+    std::vector<int> order(static_cast<size_t>(n_points));
+    for(int i = 0; i < n_points; ++i) order[i] = i;
+    if(!trace) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return values[a] < values[b]; });
+    int P = 2;
+    if(!trace)
+    {
+        long long cap = std::max(0, knob(h, "DC_SWEEP_POINTS", 0));
+        if(cap == 0)
+        {
+            // (the main engine's arrays per instance; its factor storage is part of them once it has been analysed)
+            long long bpi = static_cast<long long>((h->circ_pool.bytes + h->sym_pool.bytes) / static_cast<size_t>(std::max(1, B)));
+            if(h->sym_class < 0) bpi = 4 * static_cast<long long>(h->circ_pool.bytes / static_cast<size_t>(std::max(1, B)));
+            cap = sweep_memory_budget() / (std::max<long long>(1, bpi) * B);
+        }
+        cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
+        P = static_cast<int>(std::min<long long>(cap, n_points));
+    }
+    else if(2ll * B > SWEEP_MAX_INSTANCES)
+        return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: the batch is too large for a TRACE sweep");
+    int const n_passes = trace ? n_points : (n_points + P - 1) / P;
+    size_t const L = static_cast<size_t>(n_passes) * P;
+    std::vector<double> val_h(L);
+    std::vector<int> pt_h(L), rk_h(L, 0);
+    for(int s = 0; s < n_passes; ++s)
+    {
+        if(trace)
+        {
+            val_h[2 * s] = val_h[2 * s + 1] = slot_value(values[s]);
+            pt_h[2 * s] = s;
+            pt_h[2 * s + 1] = -1;
+            continue;
+        }
+        int const n = std::min(P, n_points - s * P);
+        for(int p = 0; p < P; ++p)
+        {
+            int const k = s * P + std::min(p, n - 1);
+            val_h[static_cast<size_t>(s) * P + p] = slot_value(values[order[k]]);
+            pt_h[static_cast<size_t>(s) * P + p] = p < n ? order[k] : -1;
+            rk_h[static_cast<size_t>(s) * P + p] = p == 0 ? 0 : rk_h[static_cast<size_t>(s) * P + p - 1] + (values[order[k]] != values[order[s * P + std::min(p - 1, n - 1)]] ? 1 : 0);
+        }
+    }
+
+    // ---- the sweep engine (rebuilt when P or anything it was built from has changed), its one symbolic analysis
+    if(!D.eng || D.P != P || D.epoch != h->param_epoch)
+        if(int const rc = dc_sweep_engine_build(h, P, c->kind, j, values[order[0]]); rc != PE_HIP_OK) return rc;
+    pe_hip_engine* const E = D.eng;
+    hipStream_t const es = E->stream;
+    long long const analyses0 = E->n_symbolic;
+    if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK) return fail(h, rc, "analyze_dc_sweep (symbolic analysis): " + E->err);
+    int const Q = B * P;
+
+    // ---- buffers sized by the call: the slot tables, the result in the caller's order, the kept rows
+    auto& S = D.V;
+    if(D.res_pairs != pairs || D.res_len != pairs * K || !S.res)
+    {
+        D.res_pool.release();
+        S.res = nullptr;
+        HIPCHK(h, D.res_pool.alloc(S.res, pairs * K, false));
+        HIPCHK(h, D.res_pool.alloc(S.res_status, pairs));
+        HIPCHK(h, D.res_pool.alloc(S.res_iters, pairs));
+        HIPCHK(h, D.res_pool.alloc(S.res_seed, pairs));
+        D.res_pairs = pairs;
+        D.res_len = pairs * K;
+    }
+    Pool slots;  // (value / point / rank of every slot of every pass: uploaded once per call)
+    double* d_val{};
+    int *d_pt{}, *d_rk{};
+    HIPCHK(h, slots.alloc(d_val, L, false));
+    HIPCHK(h, slots.alloc(d_pt, L, false));
+    HIPCHK(h, slots.alloc(d_rk, L, false));
+    HIPCHK(h, hipMemcpy(d_val, val_h.data(), L * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_pt, pt_h.data(), L * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_rk, rk_h.data(), L * sizeof(int), hipMemcpyHostToDevice));
+    if(!D.rows_on_device)
+    {
+        S.keep = nullptr;
+        if(D.rows.size() > D.keep_cap)
+        {
+            if(D.d_keep) (void)hipFree(D.d_keep);
+            D.d_keep = nullptr;
+            D.keep_cap = 0;
+            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&D.d_keep), D.rows.size() * sizeof(int)));
+            D.keep_cap = D.rows.size();
+        }
+        if(!D.rows.empty())
+        {
+            HIPCHK(h, hipMemcpy(D.d_keep, D.rows.data(), D.rows.size() * sizeof(int), hipMemcpyHostToDevice));
+            S.keep = D.d_keep;
+        }
+        D.rows_on_device = true;
+    }
+    S.P = P;
+    S.n_inst = B;
+    S.slot = slot;
+    S.trace = trace ? 1 : 0;
+    S.attempt_cap = hc.nonlinear ? E->V.max_newton : 1;
+    S.n_keep = K;
+    S.m_x = h->V.x;
+    S.m_udlast = h->V.d_udlast;
+    S.m_geq = h->V.d_geq;
+    S.m_dv = h->V.dv;
+    S.m_t_now = h->V.t_now;
+    S.m_last_step = h->V.last_step;
+    S.m_rl = h->V.rl_engaged;
+
+    // round 0 of every pass: every slot from the main engine's state of its circuit instance, everything open (TRACE: the shadows parked)
+    std::vector<int> seed0(static_cast<size_t>(Q)), status0(static_cast<size_t>(Q), PE_HIP_OK);
+    for(int q = 0; q < Q; ++q) seed0[q] = q / P;
+    if(trace)
+        for(int b = 0; b < B; ++b) status0[2 * b + 1] = pe::DC_SWEEP_PARKED;
+    auto start_from_main = [&]() -> int
+    {
+        HIPCHK(h, hipMemcpyAsync(S.seed_of, seed0.data(), static_cast<size_t>(Q) * sizeof(int), hipMemcpyHostToDevice, es));
+        HIPCHK(h, hipMemcpyAsync(E->V.status, status0.data(), static_cast<size_t>(Q) * sizeof(int), hipMemcpyHostToDevice, es));
+        HIPCHK(h, pe::launch_dc_sweep_seed(es, E->V, S, true));
+        return PE_HIP_OK;
+    };
+    // one batched solve of the instances whose status is OK; a numerical failure (or the parked status of the others) is theirs alone
+    auto solve = [&]() -> int
+    {
+        int const rc = dc_solve(E, c->mode, nullptr, false);
+        if(rc == PE_HIP_OK || rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE || rc == pe::DC_SWEEP_PARKED) return PE_HIP_OK;
+        return fail(h, rc, "analyze_dc_sweep: " + E->err);
+    };
+    pe::DcSweepRecord rec{};
+    auto classify = [&](bool reseed, bool read) -> int
+    {
+        HIPCHK(h, pe::launch_dc_sweep_classify(es, E->V, S, reseed));
+        if(!read) return PE_HIP_OK;
+        HIPCHK(h, hipMemcpyAsync(&rec, S.rec, sizeof(rec), hipMemcpyDeviceToHost, es));
+        HIPCHK(h, hipStreamSynchronize(es));
+        return PE_HIP_OK;
+    };
+    HIPCHK(h, hipEventRecord(h->ev0, es));
+    if(trace)
+    {
+        if(int const rc = start_from_main(); rc != PE_HIP_OK) return rc;
+        HIPCHK(h, hipMemsetAsync(S.rec, 0, sizeof(rec), es));
+        S.n_valid = 1;
+        for(int i = 0; i < n_points; ++i)
+        {
+            S.value = d_val + 2 * static_cast<size_t>(i);
+            S.point = d_pt + 2 * static_cast<size_t>(i);
+            S.rank = d_rk + 2 * static_cast<size_t>(i);
+            HIPCHK(h, pe::launch_dc_sweep_fill(es, E->V, S));
+            if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+            // bookkeeping, result of the point, then shadow <- working copy (converged) or working copy <- shadow (failed): nothing is read here
+            if(int const rc = classify(false, i == n_points - 1); rc != PE_HIP_OK) return rc;
+            HIPCHK(h, pe::launch_dc_sweep_gather(es, E->V, S));
+            HIPCHK(h, pe::launch_dc_sweep_seed(es, E->V, S, false));
+        }
+        T.n_passes = n_points;
+        T.points_per_pass = 1;
+        T.n_failed_cold = T.n_failed = rec.n_failing;
+        T.newton_iters = rec.iters;
+    }
+    else
+        for(int s = 0; s < n_passes; ++s)
+        {
+            int const n = std::min(P, n_points - s * P);
+            S.value = d_val + static_cast<size_t>(s) * P;
+            S.point = d_pt + static_cast<size_t>(s) * P;
+            S.rank = d_rk + static_cast<size_t>(s) * P;
+            S.n_valid = n;
+            ++T.n_passes;
+            T.points_per_pass = std::max(T.points_per_pass, n);
+            if(int const rc = start_from_main(); rc != PE_HIP_OK) return rc;
+            HIPCHK(h, pe::launch_dc_sweep_fill(es, E->V, S));
+            if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+            HIPCHK(h, hipMemsetAsync(S.rec, 0, sizeof(rec), es));
+            if(int const rc = classify(c->continuation != 0, true); rc != PE_HIP_OK) return rc;
+            T.n_failed_cold += rec.n_failing;
+            T.newton_iters += rec.iters;
+            int const max_rounds = c->max_rounds > 0 ? c->max_rounds : n;
+            int rounds = 0;
+            while(c->continuation != 0 && rec.n_failing > 0 && rec.n_reseeded > 0 && rounds < max_rounds)
+            {
+                T.n_reseeded += rec.n_reseeded;
+                HIPCHK(h, pe::launch_dc_sweep_seed(es, E->V, S, false));
+                if(int const rc = solve(); rc != PE_HIP_OK) return rc;
+                HIPCHK(h, hipMemsetAsync(S.rec, 0, sizeof(rec), es));
+                if(int const rc = classify(true, true); rc != PE_HIP_OK) return rc;
+                ++rounds;
+                T.newton_iters += rec.iters;
+                if(rec.n_newly_converged == 0) break;  // (the round converged no new pair: the same seeds would be tried again)
+            }
+            T.n_rounds = std::max(T.n_rounds, rounds);
+            T.n_failed += rec.n_failing;
+            HIPCHK(h, pe::launch_dc_sweep_gather(es, E->V, S));
+        }
+    HIPCHK(h, hipEventRecord(h->ev1, es));
+    HIPCHK(h, hipStreamSynchronize(es));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    T.gpu_ms = ms;
+    T.n_analyses = static_cast<int>(E->n_symbolic - analyses0);
+    // ---- the one copy of the results, and the pairs' bookkeeping beside it
+    if(pairs * K) HIPCHK(h, hipMemcpy(D.res.data(), S.res, pairs * K * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(D.status.data(), S.res_status, pairs * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(D.iters.data(), S.res_iters, pairs * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(D.seed.data(), S.res_seed, pairs * sizeof(int), hipMemcpyDeviceToHost));
+    return finish();
+}
+
+int pe_hip_get_dc_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* x)
+{
+    if(!h || !h->loaded || !x) return PE_HIP_ERR_ARG;
+    auto const& D = h->dcs;
+    if(!D.valid || D.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep: no DC sweep yet");
+    if(first_point < 0 || n_points < 0 || first_point > D.n_points - n_points || first_instance < 0 || count < 0 || first_instance > D.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep: points or instances out of range");
+    size_t const K = static_cast<size_t>(D.n_keep);
+    for(int i = 0; i < n_points && count * K != 0; ++i)
+        std::memcpy(x + static_cast<size_t>(i) * count * K, &D.res[(static_cast<size_t>(first_point + i) * D.batch + first_instance) * K],
+                    static_cast<size_t>(count) * K * sizeof(double));
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_dc_sweep_status(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, int* status, int* newton_iters,
+                               int* seed_point)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    auto const& D = h->dcs;
+    if(!D.valid || D.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep_status: no DC sweep yet");
+    if(first_point < 0 || n_points < 0 || first_point > D.n_points - n_points || first_instance < 0 || count < 0 || first_instance > D.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep_status: points or instances out of range");
+    for(int i = 0; i < n_points; ++i)
+        for(int b = 0; b < count; ++b)
+        {
+            size_t const src = static_cast<size_t>(first_point + i) * D.batch + first_instance + b, dst = static_cast<size_t>(i) * count + b;
+            if(status) status[dst] = D.status[src];
+            if(newton_iters) newton_iters[dst] = D.iters[src];
+            if(seed_point) seed_point[dst] = D.seed[src];
+        }
+    return PE_HIP_OK;
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 
 #include "pe_front.hpp"
 #include "pe_ac_sweep.hpp"
+#include "pe_dc_sweep.hpp"
 #include "pe_noise.hpp"
 #include "pe_lte.hpp"
 #include "pe_kernels.hpp"
@@ -1722,6 +1723,161 @@ namespace pe
         // (a circuit without sources still writes its zero densities: one chunk)
         hipLaunchKernelGGL(k_noise_accumulate, dim3(Z.n_chunks, V.batch), dim3(NOISE_THREADS), 0, st, Z, V.rows);
         if(Z.n_chunks > 1) hipLaunchKernelGGL(k_noise_finish, dim3((V.batch + 255) / 256), dim3(256), 0, st, Z, V.batch);
+        return hipGetLastError();
+    }
+
+    // ---- DC sweep (pe_dc_sweep.hpp, pe_engine_newton.cpp pe_hip_analyze_dc_sweep): sweep-engine instance q = b * P + p is circuit instance b
+    // at slot p of the pass.  Streaming kernels without LDS but for the classification's scans.
+    __global__ void __launch_bounds__(256) k_dc_sweep_fill(DevView V, DcSweepView S)
+    {
+        dc_sweep_fill(GridTeam{}, V, S);
+    }
+    // blockIdx.y = destination instance; the workgroups of one instance share its rows.  One launch instead of one copy command per array.
+    __global__ void __launch_bounds__(256) k_dc_sweep_seed(DevView V, DcSweepView S, int from_main)
+    {
+        dc_sweep_seed(GridTeam{}, V, S, static_cast<int>(blockIdx.y), from_main != 0);
+    }
+    __global__ void __launch_bounds__(256) k_dc_sweep_gather(DevView V, DcSweepView S)
+    {
+        dc_sweep_gather(GridTeam{}, V, S, static_cast<int>(blockIdx.y));
+    }
+    // inclusive scans of 64-bit keys in lane order
+    __device__ __forceinline__ unsigned long long dc_wave_scan_max(unsigned long long v, int lane)
+    {
+#pragma unroll
+        for(int o = 1; o < 64; o <<= 1)
+        {
+            unsigned long long const t = __shfl_up(v, o);
+            if(lane >= o && t > v) v = t;
+        }
+        return v;
+    }
+    __device__ __forceinline__ unsigned long long dc_wave_scan_min(unsigned long long v, int lane)
+    {
+#pragma unroll
+        for(int o = 1; o < 64; o <<= 1)
+        {
+            unsigned long long const t = __shfl_up(v, o);
+            if(lane >= o && t < v) v = t;
+        }
+        return v;
+    }
+    // One workgroup of four wavefronts per circuit instance b.  (1) a wavefront per slot: status + finiteness of the instances solved since
+    // the last classification, into the pair's bookkeeping; (2) nearest converged slot to the left of every slot: 256 slots at a time, a
+    // max-scan per wavefront, the four totals and the carry of the earlier chunks combined through LDS; (3) the same from the right as a
+    // min-scan over descending slots, then the rule (dc_sweep_choose) and the statuses of the next round.  Integer atomics only, on the record.
+    __global__ void __launch_bounds__(256) k_dc_sweep_classify(DevView V, DcSweepView S, int reseed)
+    {
+        __shared__ unsigned long long wave_tot[4];
+        int const b = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x), lane = tid & 63, w = tid >> 6;
+        int n_newly = 0, n_failing = 0, n_reseeded = 0;
+        long long iters = 0;
+        WaveTeam wt;
+        wt.lane_ = lane;
+        if(S.trace)
+        {
+            if(w == 0)
+            {
+                int const bad = __any(dc_sweep_nonfinite(wt, V, 2 * b));
+                if(lane == 0)
+                {
+                    int const conv = dc_sweep_book(V, S, 2 * b, bad, n_newly, iters);
+                    dc_sweep_trace_decide(V, S, b, conv);
+                    n_failing = conv ? 0 : 1;
+                }
+            }
+        }
+        else
+        {
+            for(int p = w; p < S.n_valid; p += 4)
+            {
+                int const q = b * S.P + p;
+                int const bad = __any(dc_sweep_nonfinite(wt, V, q));
+                if(lane == 0 && !dc_sweep_book(V, S, q, bad, n_newly, iters)) ++n_failing;
+            }
+            __syncthreads();  // (pair_status of this instance's slots: written above by lane 0 of each wavefront, read below by every thread)
+            unsigned long long carry = 0ull;
+            for(int base = 0; base < S.n_valid; base += 256)
+            {
+                int const p = base + tid;
+                bool const in = p < S.n_valid;
+                unsigned long long v = in ? dc_sweep_key_left(S.pair_status[b * S.P + p] == 0, S.rank[p], p) : 0ull;
+                v = dc_wave_scan_max(v, lane);
+                if(lane == 63) wave_tot[w] = v;
+                __syncthreads();
+                unsigned long long pre = carry;
+                for(int j = 0; j < 4; ++j)
+                {
+                    if(j < w && wave_tot[j] > pre) pre = wave_tot[j];
+                    if(wave_tot[j] > carry) carry = wave_tot[j];
+                }
+                if(in) S.scan[b * S.P + p] = v > pre ? v : pre;
+                __syncthreads();
+            }
+            carry = ~0ull;
+            for(int base = 0; base < S.P; base += 256)
+            {
+                int const p = S.P - 1 - (base + tid);  // descending slots in thread order: the prefix scan is a suffix scan over the slots
+                bool const in = p >= 0, valid = in && p < S.n_valid;
+                int const q = b * S.P + (in ? p : 0);
+                int const conv = valid && S.pair_status[q] == 0;
+                unsigned long long v = valid ? dc_sweep_key_right(conv, S.rank[p], p) : ~0ull;
+                v = dc_wave_scan_min(v, lane);
+                if(lane == 63) wave_tot[w] = v;
+                __syncthreads();
+                unsigned long long pre = carry;
+                for(int j = 0; j < 4; ++j)
+                {
+                    if(j < w && wave_tot[j] < pre) pre = wave_tot[j];
+                    if(wave_tot[j] < carry) carry = wave_tot[j];
+                }
+                if(in)
+                {
+                    int const seed = valid && !conv ? dc_sweep_choose(S.scan[q], v < pre ? v : pre, S.rank[p]) : -1;
+                    n_reseeded += dc_sweep_decide(V, S, b, p, conv, seed, reseed != 0);
+                }
+                __syncthreads();
+            }
+        }
+        unsigned long long it = static_cast<unsigned long long>(iters);
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1)
+        {
+            n_newly += __shfl_xor(n_newly, o);
+            n_failing += __shfl_xor(n_failing, o);
+            n_reseeded += __shfl_xor(n_reseeded, o);
+            it += __shfl_xor(it, o);
+        }
+        if(lane == 0)
+        {
+            if(n_failing) atomicAdd(&S.rec->n_failing, n_failing);
+            if(n_newly) atomicAdd(&S.rec->n_newly_converged, n_newly);
+            if(n_reseeded) atomicAdd(&S.rec->n_reseeded, n_reseeded);
+            if(it) atomicAdd(reinterpret_cast<unsigned long long*>(&S.rec->iters), it);
+        }
+    }
+    hipError_t launch_dc_sweep_fill(hipStream_t st, DevView const& V, DcSweepView const& S)
+    {
+        if(V.batch <= 0 || S.slot < 0) return hipSuccess;
+        hipLaunchKernelGGL(k_dc_sweep_fill, dim3((V.batch + 255) / 256), dim3(256), 0, st, V, S);
+        return hipGetLastError();
+    }
+    hipError_t launch_dc_sweep_seed(hipStream_t st, DevView const& V, DcSweepView const& S, bool from_main)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_dc_sweep_seed, dim3(sweep_grid(std::max(V.rows, from_main ? V.dv_len : 0)), V.batch), dim3(256), 0, st, V, S, from_main ? 1 : 0);
+        return hipGetLastError();
+    }
+    hipError_t launch_dc_sweep_classify(hipStream_t st, DevView const& V, DcSweepView const& S, bool reseed)
+    {
+        if(S.n_inst <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_dc_sweep_classify, dim3(S.n_inst), dim3(256), 0, st, V, S, reseed ? 1 : 0);
+        return hipGetLastError();
+    }
+    hipError_t launch_dc_sweep_gather(hipStream_t st, DevView const& V, DcSweepView const& S)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_dc_sweep_gather, dim3(sweep_grid(S.n_keep), V.batch), dim3(256), 0, st, V, S);
         return hipGetLastError();
     }
 

@@ -78,4 +78,16 @@ namespace pe
     hipError_t launch_tr_lte(hipStream_t st, DevView const& V, LteView const& L);
     hipError_t launch_tr_history_push(hipStream_t st, DevView const& V, double* hist, int slot);
     hipError_t launch_tr_state_copy(hipStream_t st, StateCopy const& S);
+    // DC sweep (pe_dc_sweep.hpp): V is the view of the sweep engine, whose instance b * S.P + p is circuit instance b at slot p of the pass.
+    // fill: the swept slot of every instance from S.value.  seed: solution and junction / relay state of every destination with
+    // S.seed_of[q] >= 0 from that source -- a circuit instance of the main engine (from_main: round 0) or an instance of the sweep engine.
+    // classify: one workgroup per circuit instance -- bookkeeping of the pairs solved since the last classification, nearest converged slot
+    // of every failing one, S.seed_of and the statuses of the next round (reseed: else everything is parked), counts into S.rec.
+    // gather: the kept rows of every valid pair into S.res at the caller's index, NaN where it failed.  Builds without HIP: serial host
+    // definitions in pe_engine_newton.cpp.
+    struct DcSweepView;
+    hipError_t launch_dc_sweep_fill(hipStream_t st, DevView const& V, DcSweepView const& S);
+    hipError_t launch_dc_sweep_seed(hipStream_t st, DevView const& V, DcSweepView const& S, bool from_main);
+    hipError_t launch_dc_sweep_classify(hipStream_t st, DevView const& V, DcSweepView const& S, bool reseed);
+    hipError_t launch_dc_sweep_gather(hipStream_t st, DevView const& V, DcSweepView const& S);
 }  // namespace pe

@@ -33,7 +33,9 @@ EXPORTS = [
     "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
     "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
+    "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
 ]
+DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
 # pe_hip_measure_kind
 MEAS_MIN, MEAS_MAX, MEAS_AVG, MEAS_RMS, MEAS_INTEG, MEAS_CROSS = 1, 2, 3, 4, 5, 6
 _MEAS_NAMES = {"min": MEAS_MIN, "max": MEAS_MAX, "avg": MEAS_AVG, "rms": MEAS_RMS, "integ": MEAS_INTEG, "cross": MEAS_CROSS}
@@ -166,6 +168,19 @@ class AcSweepStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DcSweepControl(C.Structure):
+    _fields_ = [("kind", C.c_int), ("index", C.c_int), ("column", C.c_int), ("mode", C.c_int), ("order", C.c_int), ("continuation", C.c_int),
+                ("max_rounds", C.c_int)]
+
+
+class DcSweepStats(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_passes", C.c_int), ("points_per_pass", C.c_int), ("n_rounds", C.c_int), ("n_failed_cold", C.c_longlong),
+                ("n_reseeded", C.c_longlong), ("n_failed", C.c_longlong), ("newton_iters", C.c_longlong), ("n_analyses", C.c_int), ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class NoiseControl(C.Structure):
     _fields_ = [("out_pos", C.c_int), ("out_neg", C.c_int), ("temp_k", C.c_double), ("keep_contributions", C.c_int)]
 
@@ -228,6 +243,10 @@ def lib():
         l.pe_hip_get_noise_sources.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 6
         l.pe_hip_get_noise_source_density.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         l.pe_hip_get_noise_integrated.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        l.pe_hip_set_dc_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.pe_hip_analyze_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(DcSweepControl), C.POINTER(C.c_int), C.POINTER(DcSweepStats)]
+        l.pe_hip_get_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        l.pe_hip_get_dc_sweep_status.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
         l.pe_hip_analyze_tr_adaptive.argtypes = [C.c_void_p, C.c_double, C.POINTER(TrControl), C.POINTER(TrAdaptiveStats)]
         l.pe_hip_get_tr_step_log.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         _lib = l
@@ -389,6 +408,7 @@ class Engine(_Probes):
         self.batch = batch
         self._probe_cfg = (0, 0, 0)  # (a load drops the probe configuration)
         self._ac_rows = None         # (... and the row selection of AC sweeps)
+        self._dc_rows = None         # (... and of DC sweeps)
 
     def load_deck(self, deck, batch=1, overrides=None, n_drives=0):
         n_nodes, n_br, tables = deck_tables(deck, batch, overrides, n_drives)
@@ -572,6 +592,42 @@ class Engine(_Probes):
         d = st.asdict()
         d["rc"] = rc
         return re + 1j * im, status[:n], d
+
+    def set_dc_sweep_rows(self, rows=None):
+        """rows of x kept for every point of the following analyze_dc_sweep calls; None / empty: all rows"""
+        r = np.ascontiguousarray([] if rows is None else rows, dtype=np.int32).reshape(-1)
+        self._chk(lib().pe_hip_set_dc_sweep_rows(self._h, len(r), _ip(r) if len(r) else None))
+        self._dc_rows = len(r) if len(r) else None
+
+    def analyze_dc_sweep(self, values, kind, index, column=0, mode=MODE_OP, order=DC_SWEEP_PARALLEL, continuation=1, max_rounds=0, check=True):
+        """The operating point at every value of `values` (any order) of parameter (kind, index, column) in batched passes on the device
+        (pe_hip_analyze_dc_sweep); this engine's own state is read, never written.  Returns (x [n_points][batch][n_kept] in the caller's
+        order -- NaN where a pair failed --, status [n_points], stats dict with the return code under 'rc')."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        n = len(v)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        st = DcSweepStats()
+        ctl = DcSweepControl(int(kind), int(index), int(column), int(mode), int(order), int(continuation), int(max_rounds))
+        rc = lib().pe_hip_analyze_dc_sweep(self._h, n, _dp(v), C.byref(ctl), _ip(status), C.byref(st))
+        if check:
+            self._chk(rc)
+        kept = self._dc_rows if getattr(self, "_dc_rows", None) else self.rows
+        x = np.full((n, self.batch, kept), np.nan)
+        if rc not in (ERR_ARG, ERR_NO_DEVICE, ERR_INTERNAL) and n:
+            self._chk(lib().pe_hip_get_dc_sweep(self._h, 0, n, 0, self.batch, _dp(x)))
+            self._dc_n = n
+        d = st.asdict()
+        d["rc"] = rc
+        return x, status[:n], d
+
+    def dc_sweep_status(self):
+        """per pair of the last DC sweep, each [n_points][batch]: status of its last attempt, Newton iterations of that attempt when it
+        converged, and the caller's index of the point it was seeded from (-1: this engine's own state)"""
+        n = getattr(self, "_dc_n", 0)
+        out = [np.zeros((n, self.batch), dtype=np.int32) for _ in range(3)]
+        if n:
+            self._chk(lib().pe_hip_get_dc_sweep_status(self._h, 0, n, 0, self.batch, _ip(out[0]), _ip(out[1]), _ip(out[2])))
+        return tuple(out)
 
     def analyze_noise(self, omegas, out_pos, out_neg=-1, temp_k=0.0, contributions=False, check=True):
         """Output noise density of x[out_pos] - x[out_neg] (rows of x, -1: ground) at every omega of `omegas` (rad/s, any order) by the
