@@ -228,7 +228,12 @@ namespace pe_eng PE_ENG_HIDDEN
     // exactly those); their flags are then the Newton / finiteness bits of the corrected x.  What refinement cannot repair leaves
     // the iteration as PE_HIP_ERR_INACCURATE (the caller re-matches on that instance's values and retries the step).
     // `published`: the norms of this iteration as k_m2_publish handed them over (empty: read them from the device)
-    int m2_check_residuals(pe_hip_engine* h, M2State& S, std::vector<int>& result, int& n_active, std::vector<double> const& published)
+    // `owes`: instances whose solve needed a refinement earlier at this solve point.  Where the corrected x then violated the Newton test,
+    // the iterates that follow come from the same pivot order and are as inaccurate as the flagged one -- but an iterate that violates
+    // is not checked, and its step back from the corrected x is the size of the correction: the violation would repeat until max_newton
+    // runs out.  So every further solve of such an instance is refined before its Newton bits count.
+    int m2_check_residuals(pe_hip_engine* h, M2State& S, std::vector<int>& result, int& n_active, std::vector<double> const& published,
+                           std::vector<char>& owes)
     {
         int const B = h->hc.batch;
         std::vector<double> eta(static_cast<size_t>(B) * 4);
@@ -253,14 +258,17 @@ namespace pe_eng PE_ENG_HIDDEN
         };
         // only iterates about to be accepted were checked on the device (k_m2_residual): nothing to read while every active instance
         // still shows a Newton violation
+        auto checked = [&](int b) { return S.active[b] && !(S.flags[b] & 5) && !(h->hc.nonlinear && (S.flags[b] & 2)); };
+        auto owed = [&](int b) { return S.active[b] && !(S.flags[b] & 5) && h->hc.nonlinear && (S.flags[b] & 2) && owes[static_cast<size_t>(b)]; };
         bool any = false;
-        for(int b = 0; b < B && !any; ++b) any = S.active[b] && !(S.flags[b] & 5) && !(h->hc.nonlinear && (S.flags[b] & 2));
+        for(int b = 0; b < B && !any; ++b) any = checked(b) || owed(b);
         if(!any) return PE_HIP_OK;
         if(int const rc = pull_eta(); rc != PE_HIP_OK) return rc;
         std::vector<int> todo;
         for(int b = 0; b < B; ++b)
-            if(S.active[b] && !(S.flags[b] & 5) && !(h->hc.nonlinear && (S.flags[b] & 2)) && bad(b)) todo.push_back(b);
+            if((checked(b) && bad(b)) || owed(b)) todo.push_back(b);
         if(todo.empty()) return PE_HIP_OK;
+        for(int b: todo) owes[static_cast<size_t>(b)] = 1;
         std::vector<int> mask(B);
         for(int round = 0; round < 2 && !todo.empty(); ++round)
         {
@@ -307,6 +315,7 @@ namespace pe_eng PE_ENG_HIDDEN
             n_active += S.active[b];
         }
         int const max_it = h->hc.nonlinear ? h->V.max_newton : 1;
+        std::vector<char> owes_refinement(static_cast<size_t>(B), 0);  // (m2_check_residuals)
         // Small sweeps replay a captured launch sequence per iteration (pe_kernels.hip launch_m2_iteration_graph): the 15-20 launches of an
         // iteration cost more host time than some of them run.  Large sweeps keep the plain launches -- their iteration is milliseconds,
         // and the HIP events around the dominant pair (bench.py's roofline) live there.  Knob GRAPH = 0 / 1 forces either.
@@ -361,7 +370,7 @@ namespace pe_eng PE_ENG_HIDDEN
                 }
             }
             if(h->V.residual_tol > 0.0)
-                if(int const rrc = m2_check_residuals(h, S, result, n_active, eta_now); rrc != PE_HIP_OK) return rrc;
+                if(int const rrc = m2_check_residuals(h, S, result, n_active, eta_now, owes_refinement); rrc != PE_HIP_OK) return rrc;
             for(int b = 0; b < B; ++b)
             {
                 if(!S.active[b]) continue;
@@ -558,7 +567,9 @@ namespace pe_eng PE_ENG_HIDDEN
             }
         if(failed.empty() || attempt >= 2) return PE_HIP_OK;
         if(!any_inaccurate) h->singular_rematched = true;  // (once per resident circuit: a structurally singular system stays singular)
-        if(any_inaccurate && attempt == 0 && !h->careful) h->careful = true;
+        // (knob SPLIT = 0 keeps the first attempt of every call on the resident kernel, which only detects: the first retry of such a call
+        //  is the one that refines, whether an earlier call had tripped the net already or not)
+        if(any_inaccurate && attempt == 0 && (!h->careful || !split_launch(h))) h->careful = true;
         else
         {
             // re-match on the failing instance's own assembled values (device order = front-assembly order -> CSR slots)
