@@ -196,13 +196,20 @@ int pe_hip_get_info(pe_hip_engine* h, pe_hip_info* out);
  * 3 chain link continued in LDS), n_children[s], n_own[s] (entries of A assembled into the front). */
 int pe_hip_get_front_table(pe_hip_engine* h, int which, int capacity, int* pivots, int* updates, int* parent, int* kind, int* quad, int* mode,
                            int* n_children, int* n_own, int* n_fronts);
+/* is_static[s] (array of `capacity` ints, same `which` and postorder as pe_hip_get_front_table): 1 = no x-dependent entry or row in the front's whole subtree. */
+int pe_hip_get_static_fronts(pe_hip_engine* h, int which, int capacity, int* is_static, int* n_fronts);
+/* Launches of the lane-group factor kernel since the circuit was loaded: those that skipped the static fronts (knob STATIC_SKIP, default 1) and the others. */
+int pe_hip_get_static_skip_stats(pe_hip_engine* h, long long* skipped_launches, long long* full_launches);
+/* Of those launches, the Newton iterations issued after a refinement round of their own solve point, and how many of them skipped (always 0: a refinement ends the skip for its point). */
+int pe_hip_get_static_skip_refinement_stats(pe_hip_engine* h, long long* launches_after_refinement, long long* skipped_after_refinement);
 
 /* Tuning knobs of ONE engine: the launch-geometry / symbolic-analysis parameters INTEGRATION.md lists as the PHY_ENGINE_HIP_* environment
  * family (the counterpart of the reference's cuda_policy / cuda_node_threshold members plus its PHY_ENGINE_CUDA_* variables,
  * circuit.h:63-68, benchmark/README.md:11-21), set per engine instead of per process: `name` with or without the PHY_ENGINE_HIP_
  * prefix ("PARTS", "ABSORB_M", "SPLIT", ...).  A knob set here wins over the environment variable of the same name, which wins over the
  * measured default; it takes effect at the next analysis of the resident circuit (the symbolic analysis is redone).  Test-only
- * variables (…_TEST_*, …_FULL_STAMP, …_DUMP_SCHEDULE, …_LDS_BYTES) stay environment-only. */
+ * variables (…_TEST_*, …_FULL_STAMP, …_DUMP_SCHEDULE, …_LDS_BYTES) stay environment-only.
+ * Knob "STATIC_SKIP" (default 1): 0 = every Newton iteration factors the static fronts of the lane-group kernel again (bit-identical results). */
 int pe_hip_set_knob(pe_hip_engine* h, const char* name, int value);
 int pe_hip_get_knob(pe_hip_engine* h, const char* name, int* value, int* is_set); /* what is set (engine, else environment); is_set may be NULL */
 

@@ -216,6 +216,36 @@ namespace pe
     // (the kernel argument of the probe-less kernels must keep its size: a larger DevView changes the register allocation of k_tr_steps)
     static_assert(offsetof(DevView, v_abstol) == offsetof(DevView, probe_armed) + sizeof(int), "probe_armed must fill the padding before v_abstol");
 
+    // Static fronts of the lane-group kernel across the Newton iterations of one solve point (pe_symbolic.hpp "static fronts").
+    // These tables ride next to the view, never in it (a larger DevView changes the register allocation of the resident kernels).
+    //   save: a first iteration that later ones may build on -- after the forward pass, wy[k] = w[k] for the rows with row_keep[k] (the
+    //         forward-substituted pivots of the static quad fronts; the backward pass is about to overwrite them with x);
+    //   skip: a later iteration (stamp mode 1) -- k_m2_factor_quads walks q_prog_dyn / q_lists_dyn, the stamp puts wy back into w.
+    struct StaticSkip
+    {
+        int const *q_prog_dyn{}, *q_lists_dyn{};
+        unsigned char const* row_keep{};  // [rows], permuted row order
+        double* wy{};                     // [batch][rows]
+        int save{}, skip{};
+    };
+    // What a launch sequence really does with `sk` (one predicate for the HIP launcher m2_sequence and for the host emulation): static fronts
+    // are skipped only behind the x-dependent-only stamp of a factorising, non-refining sequence on the plain lane-group launch, and the
+    // forward-substituted pivots are kept only where such a factorisation ran without skipping.
+    inline StaticSkip static_skip_effective(DevView const& V, bool do_factor, int stamp_mode, bool refine, StaticSkip const* sk)
+    {
+        StaticSkip eff = sk ? *sk : StaticSkip{};
+        bool const have_lists = V.dyn_a && V.dyn_b;
+        eff.skip = (sk && sk->skip && !refine && do_factor && stamp_mode == 1 && have_lists && V.quad && V.n_mid == 0 && V.q_lds_stride == 0) ? 1 : 0;
+        eff.save = (sk && sk->save && !eff.skip && !refine && do_factor && V.quad && V.n_quads > 0) ? 1 : 0;
+        return eff;
+    }
+#if !defined(__HIPCC__)
+    // Builds without HIP (the host emulation of the kernels): the emulation's launcher runs a whole iteration as one call with the view alone,
+    // so the iteration's StaticSkip reaches the team-generic code it walks -- stamp_dynamic_chunk, quad_factor_list, quad_backward_list --
+    // through this pointer, set around that call by launch_m2_iteration_static (pe_engine_newton.cpp).  Never compiled into the HIP library.
+    inline thread_local StaticSkip const* host_static_skip = nullptr;
+#endif
+
     // The view of the launches that record into an armed probe window (k_tr_steps<MINW, true>, k_probe_arm, k_probe_record): the engine's
     // view + the window.  The engine's own view, which captured launch sequences are keyed by, never carries it.
     struct ProbedView : DevView

@@ -482,6 +482,9 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     h->sym_dt = 0.0;
     h->careful = false;  // (a false alarm on the previous circuit must not pin this one to the host-driven schedule)
     h->n_refined = h->n_rematched = 0;
+    h->quad_skipped_launches = h->quad_full_launches = 0;
+    h->quad_launches_after_refinement = h->quad_skipped_after_refinement = 0;
+    h->static_skip = pe::StaticSkip{};
     h->sym_pool.release();
     ac_sweep_drop(h);
     dc_sweep_drop(h);
@@ -568,6 +571,35 @@ int pe_hip_get_front_table(pe_hip_engine* h, int which, int capacity, int* pivot
         if(n_children) n_children[s] = S->f_child_ptr[s + 1] - S->f_child_ptr[s];
         if(n_own) n_own[s] = S->f_asm_ptr[s + 1] - S->f_asm_ptr[s];
     }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_static_fronts(pe_hip_engine* h, int which, int capacity, int* is_static, int* n_fronts)
+{
+    if(!h || !n_fronts || capacity < 0) return PE_HIP_ERR_ARG;
+    pe::Symbolic const* S = nullptr;
+    if(which == 0 && h->loaded && h->sym_class >= 0) S = &h->sym;
+    else if(which == 1 && h->csr.have) S = &h->csr.sym;
+    else if(which == 2 && h->csrz.have) S = &h->csrz.sym;
+    if(!S) return fail(h, PE_HIP_ERR_ARG, "get_static_fronts: no such analysis");
+    *n_fronts = S->nfronts;
+    for(int s = 0; s < S->nfronts && s < capacity && is_static; ++s) is_static[s] = static_cast<size_t>(s) < S->f_static.size() ? S->f_static[static_cast<size_t>(s)] : 0;
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_static_skip_stats(pe_hip_engine* h, long long* skipped_launches, long long* full_launches)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(skipped_launches) *skipped_launches = h->quad_skipped_launches;
+    if(full_launches) *full_launches = h->quad_full_launches;
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_static_skip_refinement_stats(pe_hip_engine* h, long long* launches_after_refinement, long long* skipped_after_refinement)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(launches_after_refinement) *launches_after_refinement = h->quad_launches_after_refinement;
+    if(skipped_after_refinement) *skipped_after_refinement = h->quad_skipped_after_refinement;
     return PE_HIP_OK;
 }
 

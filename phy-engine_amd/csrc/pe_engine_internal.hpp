@@ -170,6 +170,14 @@ struct pe_hip_engine
     std::vector<char> a_static;
     double a_static_dt{-1.0};
     double analyze_ms{};
+    // static fronts of the lane-group kernel (pe_device.hpp StaticSkip): the tables of the current analysis (sym_pool; all null when
+    // it has no static quad front) and the quad factor launches since the circuit was loaded, by program
+    pe::StaticSkip static_skip{};
+    long long quad_skipped_launches{}, quad_full_launches{};
+    // iteration launches of the lane-group factor kernel issued after a refinement round of their own solve point, and those of them that
+    // skipped the static fronts (must stay 0: pe_hip_get_static_skip_refinement_stats)
+    long long quad_launches_after_refinement{}, quad_skipped_after_refinement{};
+    bool refined_in_point{};  // a refinement round has run since the first iteration of the current solve point (m2_point)
 
     // small-signal AC: a second engine holding the real-equivalent 2N system (pe_ac.hpp), built on first use
     struct Ac
@@ -327,7 +335,7 @@ namespace pe_eng PE_ENG_HIDDEN
     int upload_symbolic(pe_hip_engine* h, Pool& pool, pe::Symbolic& S, pe::SymbolicOptions const& so, pe::DevView& V, int batch);
     pe::SymbolicOptions symbolic_options(pe_hip_engine const* h, int batch_in, int rows, int panel_reserve = 384, int force_resident = 0);
     int analyze_fitting(pe_hip_engine* h, int batch, int geometry_rows, int n, int const* rp, int const* ci, double const* vals, pe::Symbolic& S,
-                        pe::SymbolicOptions& so);
+                        pe::SymbolicOptions& so, std::vector<char> const* dyn_slots = nullptr, std::vector<char> const* dyn_rows = nullptr);
     int ensure_symbolic(pe_hip_engine* h, bool tr, double dt);
     // pe_engine.cpp: transient probes
     pe::ProbedView probe_view(pe_hip_engine const* h);  // the engine's view + its armed window (probe_armed set)

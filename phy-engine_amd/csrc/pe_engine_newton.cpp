@@ -276,6 +276,10 @@ namespace pe_eng PE_ENG_HIDDEN
             for(int b: todo) mask[b] = 1;
             if(int const urc = upload_active(h, mask); urc != PE_HIP_OK) return urc;
             HIPCHK(h, pe::launch_m2_refine(h->stream, h->V));
+            // (a refactorisation with the residual riding along: the update vectors of the static roots and the kept forward-substituted
+            //  pivots no longer belong to this point's right-hand side -- no later iteration of the point may skip the static fronts)
+            h->refined_in_point = true;
+            if(h->V.quad && h->V.n_quads > 0) ++h->quad_full_launches;
             HIPCHK(h, hipStreamSynchronize(h->stream));
             if(int const rc = pull_eta(); rc != PE_HIP_OK) return rc;
             std::vector<int> fl(B);
@@ -329,6 +333,11 @@ namespace pe_eng PE_ENG_HIDDEN
             h->active_dev.clear();  // (the quad list behind the mask is laid out differently)
         }
         if(graph_mode && !h->graphs) h->graphs = pe::m2_graphs_create();
+        // Static fronts of the lane-group kernel: the iterations after the first of this point skip them -- unless anything but the
+        // x-dependent stamp may have touched the matrix, the right-hand side or what the first iteration left behind.  Knob STATIC_SKIP = 0: never.
+        h->refined_in_point = false;
+        bool const may_skip_static = h->static_skip.q_prog_dyn && h->hc.nonlinear && do_factor && !has_overlay(h) && h->V.quad && h->V.n_mid == 0 &&
+                                     h->V.q_lds_stride == 0 && h->V.dyn_a && h->V.dyn_b && knob(h, "STATIC_SKIP", 1) != 0;
         for(int it = 0; it < max_it && n_active > 0; ++it)
         {
             if(has_overlay(h))
@@ -338,21 +347,33 @@ namespace pe_eng PE_ENG_HIDDEN
             static bool const full_stamp = env_int0("PHY_ENGINE_HIP_FULL_STAMP", 0) != 0;
             int const dyn = full_stamp ? 0 : (it > 0 ? 1 : (a_static_ok ? 2 : 0));
             bool const comp = it == 0 && companion_dt != nullptr;
+            pe::StaticSkip sk = h->static_skip;
+            sk.save = (may_skip_static && !full_stamp && it == 0) ? 1 : 0;
+            sk.skip = (may_skip_static && !full_stamp && it > 0 && dyn == 1 && !h->refined_in_point) ? 1 : 0;
+            if(do_factor && h->V.quad && h->V.n_quads > 0)
+            {
+                ++(sk.skip ? h->quad_skipped_launches : h->quad_full_launches);
+                if(it > 0 && h->refined_in_point)  // (counted whatever the knob says: the second must stay 0)
+                {
+                    ++h->quad_launches_after_refinement;
+                    if(sk.skip) ++h->quad_skipped_after_refinement;
+                }
+            }
             std::vector<double> eta_now;
             if(graph_mode)
             {
                 if(int const prc = ensure_published(h, static_cast<size_t>(B)); prc != PE_HIP_OK) return prc;
                 auto const dev = pub_view(h->pub_dev, static_cast<size_t>(B));
                 unsigned long long const seq = ++h->pub_seq;
-                HIPCHK(h, pe::launch_m2_iteration_graph(h->stream, h->graphs, h->V, mode, t, last_step, do_factor, dyn, comp, companion_dt ? *companion_dt : 0.0, dev.flags,
-                                                        dev.eta, dev.seq, seq));
+                HIPCHK(h, pe::launch_m2_iteration_graph_static(h->stream, h->graphs, h->V, mode, t, last_step, do_factor, dyn, comp, companion_dt ? *companion_dt : 0.0,
+                                                               dev.flags, dev.eta, dev.seq, seq, sk));
                 ++launches;
                 if(int const prc = wait_published(h, S.flags, &eta_now, seq); prc != PE_HIP_OK) return prc;
             }
             else
             {
-                HIPCHK(h, pe::launch_m2_iteration(h->stream, h->V, mode, t, last_step, do_factor, h->evk0, h->evk1, /*stamp_mode=*/dyn, /*companion=*/comp,
-                                                  companion_dt ? *companion_dt : 0.0));
+                HIPCHK(h, pe::launch_m2_iteration_static(h->stream, h->V, mode, t, last_step, do_factor, h->evk0, h->evk1, /*stamp_mode=*/dyn, /*companion=*/comp,
+                                                         companion_dt ? *companion_dt : 0.0, sk));
                 ++launches;
                 // flags + residual norms of this iteration: published into pinned host memory by the iteration's last launch and polled
                 // (no copy command, no stream synchronisation); PHY_ENGINE_HIP_PUBLISH=0: the copy + synchronise of rounds 1-2
@@ -621,6 +642,33 @@ namespace pe
             void sync() const {}
         };
     }  // namespace
+    // the iteration with the static fronts of the lane-group kernel kept / skipped: the emulation's launcher runs the whole iteration from the
+    // view alone, so the tables reach the code it walks through pe::host_static_skip (pe_device.hpp) -- under m2_sequence's own conditions
+    namespace
+    {
+        struct HostStaticSkip
+        {
+            StaticSkip eff;
+            HostStaticSkip(DevView const& V, bool do_factor, int stamp_mode, StaticSkip const& sk) : eff(static_skip_effective(V, do_factor, stamp_mode, false, &sk))
+            {
+                host_static_skip = (eff.skip || eff.save) ? &eff : nullptr;
+            }
+            ~HostStaticSkip() { host_static_skip = nullptr; }
+        };
+    }  // namespace
+    hipError_t launch_m2_iteration_static(hipStream_t st, DevView const& V, int mode, double t, double last_step, bool do_factor, hipEvent_t ev0, hipEvent_t ev1,
+                                          int stamp_mode, bool companion, double companion_dt, StaticSkip const& sk)
+    {
+        HostStaticSkip const scope(V, do_factor, stamp_mode, sk);
+        return launch_m2_iteration(st, V, mode, t, last_step, do_factor, ev0, ev1, stamp_mode, companion, companion_dt);
+    }
+    hipError_t launch_m2_iteration_graph_static(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor,
+                                                int stamp_mode, bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq,
+                                                unsigned long long seq, StaticSkip const& sk)
+    {
+        HostStaticSkip const scope(V, do_factor, stamp_mode, sk);
+        return launch_m2_iteration_graph(st, cache, V, mode, t, last_step, do_factor, stamp_mode, companion, companion_dt, pub_flags, pub_eta, pub_seq, seq);
+    }
     hipError_t launch_probe_arm(hipStream_t, ProbedView const& V)
     {
         for(int b = 0; b < V.batch; ++b) probe_arm(ProbeHostTeam{}, V, b);

@@ -417,10 +417,13 @@ namespace pe_eng PE_ENG_HIDDEN
     // right-hand-side column (m doubles) must fit the reserve behind its panels, and the top of the tree the launch table.
     // (1) a larger reserve; (2) the whole LDS of a CU for one workgroup; else give up loudly.  `geometry_rows`: row count the
     // launch geometry is chosen by (0: the resident single-workgroup kernel, as the solver seam runs).
+    // `dyn_slots` / `dyn_rows` (may be null): the x-dependent CSR slots / rows of the resident circuit, for the static-front classification
     int analyze_fitting(pe_hip_engine* h, int batch, int geometry_rows, int n, int const* rp, int const* ci, double const* vals, pe::Symbolic& S,
-                        pe::SymbolicOptions& so)
+                        pe::SymbolicOptions& so, std::vector<char> const* dyn_slots, std::vector<char> const* dyn_rows)
     {
         so = symbolic_options(h, batch, geometry_rows);
+        so.dyn_slots = dyn_slots;
+        so.dyn_rows = dyn_rows;
         for(int attempt = 0;; ++attempt)
         {
             if(!pe::analyze(n, rp, ci, vals, so, S))
@@ -434,6 +437,8 @@ namespace pe_eng PE_ENG_HIDDEN
             }
             if(attempt == 2) return fail(h, PE_HIP_ERR_INTERNAL, "symbolic analysis: a front of order " + std::to_string(S.max_m) + " does not fit the LDS of a CU");
             so = symbolic_options(h, batch, geometry_rows, std::max(384, S.max_m + 72), attempt == 1 ? 1 : 0);
+            so.dyn_slots = dyn_slots;
+            so.dyn_rows = dyn_rows;
             if(too_deep) so.n_parts = 1;
         }
     }
@@ -456,9 +461,24 @@ namespace pe_eng PE_ENG_HIDDEN
             // static order the residual safety net is tested against; a re-match on an instance's own values is not affected
             if(char const* k = std::getenv("PHY_ENGINE_HIP_TEST_BLIND_MATCH"); k && *k == '1') std::fill(av.begin(), av.end(), 1.0);
         }
+        // x-dependent CSR slots of A / rows of the right-hand side: ONE pair of flag vectors feeds the static-front classification of the
+        // analysis and, below, the lists of the x-dependent-only stamp -- the two can never disagree
+        std::vector<char> dyn_slots, dyn_rows;
+        if(h->hc.nonlinear)
+        {
+            auto const& hc = h->hc;
+            std::vector<char> const dyn = pe::dynamic_dv_mask(hc);
+            dyn_slots.assign(hc.ci.size(), 0);
+            dyn_rows.assign(static_cast<size_t>(hc.rows), 0);
+            for(size_t e = 0; e < hc.ci.size(); ++e)
+                for(int k = hc.a_ptr[e]; k < hc.a_ptr[e + 1] && !dyn_slots[e]; ++k) dyn_slots[e] = dyn[static_cast<size_t>(hc.a_src[k] >> 1)];
+            for(int r = 0; r < hc.rows; ++r)
+                for(int k = hc.b_ptr[r]; k < hc.b_ptr[r + 1] && !dyn_rows[static_cast<size_t>(r)]; ++k) dyn_rows[static_cast<size_t>(r)] = dyn[static_cast<size_t>(hc.b_src[k] >> 1)];
+        }
         pe::SymbolicOptions so{};
         {
-            int const rc = analyze_fitting(h, h->hc.batch, h->hc.rows, h->hc.rows, h->hc.rp.data(), h->hc.ci.data(), av.data(), h->sym, so);
+            int const rc = analyze_fitting(h, h->hc.batch, h->hc.rows, h->hc.rows, h->hc.rp.data(), h->hc.ci.data(), av.data(), h->sym, so,
+                                           h->hc.nonlinear ? &dyn_slots : nullptr, h->hc.nonlinear ? &dyn_rows : nullptr);
             if(rc != PE_HIP_OK)
             {
                 h->sym_class = -1;
@@ -475,6 +495,9 @@ namespace pe_eng PE_ENG_HIDDEN
             if(S.quad)
                 std::fprintf(stderr, "[pe_hip]   lane-group kernel: LDS stack %d doubles per instance holds %lld of %lld update-matrix doubles of the wave fronts\n",
                              S.q_lds_doubles, S.q_lds_kept, S.q_lds_total);
+            if(S.quad)
+                std::fprintf(stderr, "[pe_hip]   lane-group kernel: %d static fronts, the persistent slots of their roots add %lld doubles to an arena of %lld\n", S.n_static_quad,
+                             S.static_root_doubles, S.arena_doubles);
             if(S.quad)
             {
                 std::fprintf(stderr, "[pe_hip]   wave-front lists (fronts):");
@@ -519,6 +542,7 @@ namespace pe_eng PE_ENG_HIDDEN
         }
         pe::m2_graphs_clear(h->graphs);  // (captured sequences hold the old view: its tables are about to be freed)
         h->sym_pool.release();
+        h->static_skip = pe::StaticSkip{};
         int const rc = upload_symbolic(h, h->sym_pool, h->sym, so, h->V, h->hc.batch);
         if(rc != PE_HIP_OK) return rc;
         h->active_dev.clear();  // (the quad list behind the mask depends on this analysis' strides)
@@ -582,22 +606,11 @@ namespace pe_eng PE_ENG_HIDDEN
             h->V.n_dyn_a = h->V.n_dyn_b = 0;
             if(hc.nonlinear)
             {
-                std::vector<char> const dyn = pe::dynamic_dv_mask(hc);
                 std::vector<int> da, db;
                 for(size_t e = 0; e < nnz; ++e)
-                    for(int k = ptr2[e]; k < ptr2[e + 1]; ++k)
-                        if(dyn[static_cast<size_t>(src2[k] >> 1)])
-                        {
-                            da.push_back(static_cast<int>(e));
-                            break;
-                        }
+                    if(dyn_slots[static_cast<size_t>(S.asm_slot[e])]) da.push_back(static_cast<int>(e));
                 for(int r = 0; r < hc.rows; ++r)
-                    for(int k = hc.b_ptr[r]; k < hc.b_ptr[r + 1]; ++k)
-                        if(dyn[static_cast<size_t>(hc.b_src[k] >> 1)])
-                        {
-                            db.push_back(r);
-                            break;
-                        }
+                    if(dyn_rows[static_cast<size_t>(r)]) db.push_back(r);
                 h->V.n_dyn_a = static_cast<int>(da.size());
                 h->V.n_dyn_b = static_cast<int>(db.size());
                 if(da.empty()) da.push_back(0);
@@ -607,6 +620,15 @@ namespace pe_eng PE_ENG_HIDDEN
                 std::vector<unsigned char> rd(static_cast<size_t>(std::max(1, hc.rows)), 0);
                 for(int k = 0; k < h->V.n_dyn_b; ++k) rd[static_cast<size_t>(db[static_cast<size_t>(k)])] = 1;
                 HIPCHK(h, h->sym_pool.upload(h->V.row_dyn, rd));
+                // static fronts of the lane-group kernel: the program without them, the rows whose forward-substituted value is kept
+                // across the later iterations of a point, and that vector (arena_doubles has grown by S.static_root_doubles for their roots)
+                if(S.quad && S.n_static_quad > 0)
+                {
+                    HIPCHK(h, h->sym_pool.upload(h->static_skip.q_prog_dyn, S.q_prog_dyn));
+                    HIPCHK(h, h->sym_pool.upload(h->static_skip.q_lists_dyn, S.q_lists_dyn));
+                    HIPCHK(h, h->sym_pool.upload(h->static_skip.row_keep, S.row_keep));
+                    HIPCHK(h, h->sym_pool.alloc(h->static_skip.wy, static_cast<size_t>(hc.rows) * hc.batch));
+                }
             }
             h->V.asm_slot = nullptr;  // identity (pe_front.hpp front_factor); the solve_csr_real seam keeps CSR order + the map
             std::vector<int> slot_e(nnz, 0);  // CSR slot -> position in aval (residual check walks A row by row in original order)

@@ -475,10 +475,20 @@ namespace pe
     // rhs_full (first Newton iteration of a transient step whose matrix is known to hold the stamp of this dt, round 4): the matrix takes the
     // x-dependent slots only -- everything else in A (conductances, companion conductances 2C/dt, 2L/dt, incidence, g_min) is the same from one
     // time point to the next while dt and the parameters stay -- and the right-hand side (histories, sources at the new t) is gathered in full
-    PE_DEV void stamp_dynamic_chunk(DevView const& V, int b, int g, int G, int t0, int T, bool with_w = false, bool rhs_full = false)
+    // wy / row_keep (both or neither; launches that skip the static fronts of the lane-group kernel, pe_device.hpp StaticSkip): the rows with
+    // row_keep[k] take the forward-substituted value the first iteration left in wy -- their fronts are not factored again
+    PE_DEV void stamp_dynamic_chunk(DevView const& V, int b, int g, int G, int t0, int T, bool with_w = false, bool rhs_full = false, double const* wy = nullptr,
+                                    unsigned char const* row_keep = nullptr)
     {
         double const* dv = V.dv + static_cast<long long>(b) * V.dv_len;
         double* w = with_w ? V.w + static_cast<long long>(b) * V.rows : nullptr;
+#if !defined(__HIPCC__)
+        if(host_static_skip && host_static_skip->skip && with_w && !rhs_full)  // (host emulation: pe_device.hpp host_static_skip)
+        {
+            wy = host_static_skip->wy;
+            row_keep = host_static_skip->row_keep;
+        }
+#endif
         auto range = [&](int n, int& lo, int& hi)
         {
             int const c = (n + G - 1) / G;
@@ -503,7 +513,7 @@ namespace pe
             for(int k = lo + t0; k < hi; k += T)
             {
                 int const r = V.row_src[k];
-                if(!V.row_dyn[r]) w[k] = rhs[r];
+                if(!V.row_dyn[r]) w[k] = (row_keep && row_keep[k]) ? wy[static_cast<long long>(b) * V.rows + k] : rhs[r];
             }
         }
     }
@@ -1467,6 +1477,13 @@ namespace pe
     PE_DEV void backward_part(Team const& tm, DevView const& V, int b, int part, double* lds)
     {
         int const* wp = V.wave_ptr + part * (V.n_waves + 1);
+#if !defined(__HIPCC__)
+        // (host emulation of k_m2_keep_y, pe_device.hpp host_static_skip: the forward-substituted pivots of the static quad fronts, before any
+        //  backward pass of a wave or quad front of this instance has run)
+        if(host_static_skip && host_static_skip->save && part == 0)
+            for(int k = 0; k < V.rows; ++k)
+                if(host_static_skip->row_keep[k]) host_static_skip->wy[static_cast<long long>(b) * V.rows + k] = V.w[static_cast<long long>(b) * V.rows + k];
+#endif
         long long const cbw0 = tm.clock();
         for(int q = V.coop_ptr[part + 1] - 1; q >= V.coop_ptr[part]; --q) front_backward(tm, V, b, V.coop_list[q], lds, V.max_m, V.lds_coop_stage);
         tm.sync();

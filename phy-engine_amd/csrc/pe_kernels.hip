@@ -653,12 +653,15 @@ namespace pe
     }
 
     // (also initialises the permuted work vector w = P rhs: k_m2_winit remains for the refinement solve, whose right-hand side is a residual)
-    __global__ void __launch_bounds__(256) k_m2_stamp(DevView V, int dynamic_only)
+    // wy / row_keep: non-null in the launches that skip the static fronts of the lane-group kernel (pe_device.hpp StaticSkip, dynamic_only == 1 only)
+    __global__ void __launch_bounds__(256) k_m2_stamp(DevView V, int dynamic_only, double const* __restrict__ wy, unsigned char const* __restrict__ row_keep)
     {
         int const b = static_cast<int>(blockIdx.y);
         if(!V.active[b]) return;
         // dynamic_only: 0 everything, 1 the x-dependent slots and rows, 2 the x-dependent slots of the matrix + the whole right-hand side
-        if(dynamic_only) stamp_dynamic_chunk(V, b, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), static_cast<int>(threadIdx.x), static_cast<int>(blockDim.x), true, dynamic_only == 2);
+        if(dynamic_only)
+            stamp_dynamic_chunk(V, b, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), static_cast<int>(threadIdx.x), static_cast<int>(blockDim.x), true, dynamic_only == 2, wy,
+                                row_keep);
         else
             stamp_chunk(V, b, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), static_cast<int>(threadIdx.x), static_cast<int>(blockDim.x), true);
     }
@@ -768,6 +771,19 @@ namespace pe
         double const* rhs = V.rhs + static_cast<long long>(b) * V.rows;
         double* w = V.w + static_cast<long long>(b) * V.rows;
         for(int k = tm.tid(); k < V.rows; k += tm.size()) w[k] = rhs[V.row_src[k]];
+    }
+
+    // first Newton iteration of a solve point whose later ones may skip the static fronts of the lane-group kernel (StaticSkip): the
+    // forward-substituted pivots of those fronts, before the backward pass overwrites them with x
+    __global__ void __launch_bounds__(256) k_m2_keep_y(DevView V, double* __restrict__ wy, unsigned char const* __restrict__ row_keep)
+    {
+        int const b = static_cast<int>(blockIdx.y);
+        if(!V.active[b]) return;
+        GridTeam tm;
+        double const* w = V.w + static_cast<long long>(b) * V.rows;
+        double* y = wy + static_cast<long long>(b) * V.rows;
+        for(int k = tm.tid(); k < V.rows; k += tm.size())
+            if(row_keep[k]) y[k] = w[k];
     }
 
     template <int MINW>
@@ -1123,9 +1139,12 @@ namespace pe
     // stamp_mode: 0 full stamp, 1 x-dependent slots / rows only (later Newton iterations of a point), 2 x-dependent matrix slots + full right-hand
     // side (first iteration of a transient step at an unchanged dt: the rest of the matrix is last step's)
     static hipError_t m2_sequence(hipStream_t st, DevView const& V, int mode, double t, double last_step, bool do_factor, hipEvent_t ev0, hipEvent_t ev1, bool refine,
-                                  int stamp_mode = 0, bool companion = false, double companion_dt = 0.0)
+                                  int stamp_mode = 0, bool companion = false, double companion_dt = 0.0, StaticSkip const* sk = nullptr)
     {
         bool const have_lists = V.dyn_a && V.dyn_b;
+        // static fronts of the lane-group kernel (pe_device.hpp StaticSkip; the predicate is shared with the host emulation)
+        StaticSkip const eff = static_skip_effective(V, do_factor, stamp_mode, refine, sk);
+        bool const skip_static = eff.skip != 0, keep_y = eff.save != 0;
         int const eval_dyn = (stamp_mode == 1 && have_lists) ? 1 : 0, stamp_dyn = have_lists ? stamp_mode : 0;
         size_t const lds = static_cast<size_t>(V.lds_doubles) * sizeof(double);
         size_t const lds_s = static_cast<size_t>(V.lds_solve_doubles) * sizeof(double);
@@ -1155,7 +1174,8 @@ namespace pe
         if(!refine)
         {
             hipLaunchKernelGGL(k_m2_eval, dim3(G, B), dim3(256), 0, st, V, mode, t, last_step, eval_dyn, companion ? 1 : 0, companion_dt);
-            hipLaunchKernelGGL(k_m2_stamp, dim3(G, B), dim3(256), 0, st, V, stamp_dyn);  // (+ w = P rhs)
+            hipLaunchKernelGGL(k_m2_stamp, dim3(G, B), dim3(256), 0, st, V, stamp_dyn, skip_static ? static_cast<double const*>(sk->wy) : nullptr,
+                               skip_static ? sk->row_keep : nullptr);  // (+ w = P rhs)
         }
         else  // (refinement: V arrives with rhs = the residual of the solve being corrected; the matrix values are still assembled)
             hipLaunchKernelGGL(k_m2_winit, dim3(G, B), dim3(256), 0, st, V);
@@ -1173,11 +1193,21 @@ namespace pe
                     hipError_t const e = set_lds(reinterpret_cast<void const*>(&k_m2_factor_quads), qlds);
                     if(e != hipSuccess) return e;
                 }
-                hipLaunchKernelGGL(k_m2_factor_quads, dim3(V.n_quads * V.n_parts * V.n_waves), dim3(64), qlds, st, V);
+                if(skip_static)
+                {
+                    // (the same kernel on the program without the static fronts; every other launch of the sequence keeps the full lists)
+                    DevView Vd = V;
+                    Vd.q_prog = sk->q_prog_dyn;
+                    Vd.q_lists = sk->q_lists_dyn;
+                    hipLaunchKernelGGL(k_m2_factor_quads, dim3(V.n_quads * V.n_parts * V.n_waves), dim3(64), qlds, st, Vd);
+                }
+                else
+                    hipLaunchKernelGGL(k_m2_factor_quads, dim3(V.n_quads * V.n_parts * V.n_waves), dim3(64), qlds, st, V);
                 if(V.n_mid > 0) hipLaunchKernelGGL(k_m2_factor_mid, dim3(V.n_quads * V.n_parts * V.n_waves), dim3(64), 0, st, V);
             }
             hipLaunchKernelGGL(k_m2_factor_parts<MINW>, dim3(B, V.n_parts), dim3(T), lds, st, V);
             if(ev1) (void)hipEventRecord(ev1, st);
+            if(keep_y) hipLaunchKernelGGL(k_m2_keep_y, dim3(G, B), dim3(256), 0, st, V, sk->wy, sk->row_keep);
             // 16 wavefronts per front where a level leaves most CUs without a workgroup anyway: always in the one-workgroup-per-CU
             // geometry (few instances), and on the under-filled levels near the root of a sweep (fronts x instances <= CUs + 25 %);
             // the rule lives in upload_symbolic (the fronts' LDS layout depends on it), the plan in pe_top_plan.hpp
@@ -1233,6 +1263,12 @@ namespace pe
         return V.high_occupancy ? m2_sequence<4>(st, V, mode, t, last_step, do_factor, ev0, ev1, false, stamp_mode, companion, companion_dt)
                                 : m2_sequence<2>(st, V, mode, t, last_step, do_factor, ev0, ev1, false, stamp_mode, companion, companion_dt);
     }
+    hipError_t launch_m2_iteration_static(hipStream_t st, DevView const& V, int mode, double t, double last_step, bool do_factor, hipEvent_t ev0, hipEvent_t ev1,
+                                          int stamp_mode, bool companion, double companion_dt, StaticSkip const& sk)
+    {
+        return V.high_occupancy ? m2_sequence<4>(st, V, mode, t, last_step, do_factor, ev0, ev1, false, stamp_mode, companion, companion_dt, &sk)
+                                : m2_sequence<2>(st, V, mode, t, last_step, do_factor, ev0, ev1, false, stamp_mode, companion, companion_dt, &sk);
+    }
 
     // One round of iterative refinement of the active instances' last solve (same matrix values, same pivot order):
     // r = b - A x -> correction solve A d = r (a full refactorisation with r riding along: the fused path keeps no L21) -> x += d,
@@ -1286,6 +1322,7 @@ namespace pe
         hipGraphNode_t eval_node{}, publish_node{};
         DevView V{};
         int mode{}, do_factor{}, dyn{}, companion{};
+        int static_bits{};  // StaticSkip: bit 0 save, bit 1 skip (the tables themselves belong to the analysis, like the view's)
         int* pub_flags{};
         double* pub_eta{};
         unsigned long long* pub_seq{};
@@ -1311,13 +1348,29 @@ namespace pe
         if(c) c->clear();
     }
 
+    static hipError_t m2_iteration_graph(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor, int stamp_mode,
+                                         bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq, unsigned long long seq,
+                                         StaticSkip const* sk);
     hipError_t launch_m2_iteration_graph(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor, int stamp_mode,
                                          bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq, unsigned long long seq)
     {
+        return m2_iteration_graph(st, cache, V, mode, t, last_step, do_factor, stamp_mode, companion, companion_dt, pub_flags, pub_eta, pub_seq, seq, nullptr);
+    }
+    hipError_t launch_m2_iteration_graph_static(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor,
+                                                int stamp_mode, bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq,
+                                                unsigned long long seq, StaticSkip const& sk)
+    {
+        return m2_iteration_graph(st, cache, V, mode, t, last_step, do_factor, stamp_mode, companion, companion_dt, pub_flags, pub_eta, pub_seq, seq, &sk);
+    }
+    static hipError_t m2_iteration_graph(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor, int stamp_mode,
+                                         bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq, unsigned long long seq,
+                                         StaticSkip const* sk)
+    {
         int const dyn = (V.dyn_a && V.dyn_b) ? stamp_mode : 0;
+        int const static_bits = sk ? ((sk->save ? 1 : 0) | (sk->skip ? 2 : 0)) : 0;
         M2GraphEntry* hit = nullptr;
         for(auto& e: cache->entries)
-            if(e.mode == mode && e.do_factor == (do_factor ? 1 : 0) && e.dyn == dyn && e.companion == (companion ? 1 : 0) && e.pub_flags == pub_flags && e.pub_eta == pub_eta &&
+            if(e.mode == mode && e.do_factor == (do_factor ? 1 : 0) && e.dyn == dyn && e.companion == (companion ? 1 : 0) && e.static_bits == static_bits && e.pub_flags == pub_flags && e.pub_eta == pub_eta &&
                e.pub_seq == pub_seq && std::memcmp(&e.V, &V, sizeof(DevView)) == 0)
             {
                 hit = &e;
@@ -1332,13 +1385,14 @@ namespace pe
             e.do_factor = do_factor ? 1 : 0;
             e.dyn = dyn;
             e.companion = companion ? 1 : 0;
+            e.static_bits = static_bits;
             e.pub_flags = pub_flags;
             e.pub_eta = pub_eta;
             e.pub_seq = pub_seq;
             hipError_t rc = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
             if(rc != hipSuccess) return rc;
-            rc = V.high_occupancy ? m2_sequence<4>(st, V, mode, t, last_step, do_factor, nullptr, nullptr, false, stamp_mode, companion, companion_dt)
-                                  : m2_sequence<2>(st, V, mode, t, last_step, do_factor, nullptr, nullptr, false, stamp_mode, companion, companion_dt);
+            rc = V.high_occupancy ? m2_sequence<4>(st, V, mode, t, last_step, do_factor, nullptr, nullptr, false, stamp_mode, companion, companion_dt, sk)
+                                  : m2_sequence<2>(st, V, mode, t, last_step, do_factor, nullptr, nullptr, false, stamp_mode, companion, companion_dt, sk);
             hipError_t const rp = launch_m2_publish(st, V, pub_flags, pub_eta, pub_seq, seq);
             hipError_t const re = hipStreamEndCapture(st, &e.graph);
             if(rc != hipSuccess) return rc;

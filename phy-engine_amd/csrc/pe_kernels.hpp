@@ -22,6 +22,10 @@ namespace pe
     // companion: first iteration of a transient step -- the companion update of that step (dt = companion_dt) runs inside the evaluation launch
     hipError_t launch_m2_iteration(hipStream_t st, DevView const& V, int mode, double t, double last_step, bool do_factor, hipEvent_t ev0 = nullptr,
                                    hipEvent_t ev1 = nullptr, int stamp_mode = 0, bool companion = false, double companion_dt = 0.0);
+    // the same iteration with the static fronts of the lane-group kernel kept (sk.save) or skipped (sk.skip): pe_device.hpp StaticSkip.  Builds
+    // without HIP (the emulation library): host definitions in pe_engine_newton.cpp on top of launch_m2_iteration / launch_m2_iteration_graph.
+    hipError_t launch_m2_iteration_static(hipStream_t st, DevView const& V, int mode, double t, double last_step, bool do_factor, hipEvent_t ev0, hipEvent_t ev1,
+                                          int stamp_mode, bool companion, double companion_dt, StaticSkip const& sk);
     // the same sequence + the publication of its results (launch_m2_publish) as ONE captured graph launch, built on first use per (mode,
     // do_factor, stamp_dynamic, companion, V) and replayed afterwards; small sweeps only (pe_engine_newton.cpp).  No HIP events around the
     // dominant launch in this path.  The cache belongs to an engine (created / destroyed with it, cleared when its view changes for good).
@@ -31,6 +35,9 @@ namespace pe
     void m2_graphs_clear(M2GraphCache* c);
     hipError_t launch_m2_iteration_graph(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor, int stamp_mode,
                                          bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq, unsigned long long seq);
+    hipError_t launch_m2_iteration_graph_static(hipStream_t st, M2GraphCache* cache, DevView const& V, int mode, double t, double last_step, bool do_factor,
+                                                int stamp_mode, bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq,
+                                                unsigned long long seq, StaticSkip const& sk);
     // device-to-device stream copy of `bytes` (multiple of 16): the kernel behind pe_hip_measure_hbm_ceiling
     hipError_t launch_stream_copy(hipStream_t st, void const* src, void* dst, size_t bytes);
     // one round of iterative refinement of the active instances' last solve + re-check (residual safety net, pe_front.hpp)

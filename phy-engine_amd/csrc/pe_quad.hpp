@@ -749,6 +749,13 @@ namespace pe
 #endif
         int const* lp = V.q_lists + 2 * list;
         int const* blk = V.q_prog + lp[0];
+#if !defined(__HIPCC__)
+        if(host_static_skip && host_static_skip->skip)  // (host emulation: the launch that skips the static fronts gets its view with these two swapped)
+        {
+            lp = host_static_skip->q_lists_dyn + 2 * list;
+            blk = host_static_skip->q_prog_dyn + lp[0];
+        }
+#endif
         int const nfr = lp[1];
         vm bad = X::none();
         long long clkv[6] = {0, 0, 0, 0, 0, 0};

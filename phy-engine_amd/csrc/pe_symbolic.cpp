@@ -773,6 +773,20 @@ namespace pe
             }
         }
 
+        // static fronts (pe_symbolic.hpp): own x-dependent entry / pivot row, or a dynamic child (postorder: children come first)
+        S.f_static.assign(nf, 0);
+        if(opt.dyn_slots && opt.dyn_rows && static_cast<int>(opt.dyn_slots->size()) == rp[n] && static_cast<int>(opt.dyn_rows->size()) == n)
+        {
+            std::vector<char> dynamic(nf, 0);
+            for(int s = 0; s < nf; ++s)
+            {
+                for(int e = S.f_asm_ptr[s]; e < S.f_asm_ptr[s + 1] && !dynamic[s]; ++e) dynamic[s] = (*opt.dyn_slots)[S.asm_slot[e]] != 0;
+                for(int k = S.f_col0[s]; k < S.f_col0[s] + S.f_p[s] && !dynamic[s]; ++k) dynamic[s] = (*opt.dyn_rows)[S.row_src[k]] != 0;
+                S.f_static[s] = dynamic[s] ? 0 : 1;
+                if(dynamic[s] && S.f_parent[s] >= 0) dynamic[S.f_parent[s]] = 1;
+            }
+        }
+
         // ---------------- schedule
         // Two nested proportional cuts of the assembly tree (from the roots downwards):
         //   level 1 (only when n_parts > 1, the multi-workgroup mode for one or few instances): subtrees costing at most
@@ -1010,14 +1024,20 @@ namespace pe
             // the tree depth: a front writes its Schur tiles while later tiles still gather from its children's, so a parent
             // must never overlap its children -- children always sit on the other stack.
             long long base = 0;
-            auto persistent = [&](int s)
+            auto on_stacks = [&](int s)
             {
                 int const P = S.f_parent[s];
                 // (a MID front is factored by its own launch, before and in another order than the cooperative list it belongs to:
-                //  its update matrix cannot live on that executor's LIFO stacks)
                 //  its update matrix cannot live on that executor's LIFO stacks; likewise a QUAD front under a wave front of the per-instance path)
-                return exec_of[s] < 0 || P < 0 || exec_of[P] != exec_of[s] || S.f_kind[s] == 3 || (S.f_quad[s] && !S.f_quad[P]);
+                return !(exec_of[s] < 0 || P < 0 || exec_of[P] != exec_of[s] || S.f_kind[s] == 3 || (S.f_quad[s] && !S.f_quad[P]));
             };
+            // a static root of the lane-group kernel: the launches that skip the static fronts still assemble its update matrix + vector into
+            // the (dynamic) parent -- on the LIFO stacks a later front of the same launch would have overwritten them
+            auto static_quad_root = [&](int s) { return S.f_quad[s] && S.f_static[s] && S.f_parent[s] >= 0 && !S.f_static[S.f_parent[s]]; };
+            auto persistent = [&](int s) { return !on_stacks(s) || static_quad_root(s); };
+            S.static_root_doubles = 0;
+            for(int s = 0; s < nf; ++s)
+                if(on_stacks(s) && static_quad_root(s)) S.static_root_doubles += static_cast<long long>(S.f_u[s]) * (S.f_u[s] + 1);
             for(int s = 0; s < nf; ++s)
                 if(persistent(s))
                 {
@@ -1193,6 +1213,44 @@ namespace pe
                 for(int i = S.wave_ptr[part * (W + 1) + w]; i < S.wave_ptr[part * (W + 1) + w + 1]; ++i)
                     if(S.f_quad[S.wave_list[i]]) lists[static_cast<size_t>(part) * W + w].push_back(S.wave_list[i]);
         build_quad_program(S, lists, S.q_lds_doubles, S.q_prog, S.q_lists, S.q_lane);
+        // the same program without the static fronts (pe_symbolic.hpp "static fronts"): the blocks of the dynamic fronts copied list by
+        // list -- a child block keeps pointing at its child's arena slot, persistent for a static root --, the look-ahead of a block
+        // (row sets and per-lane data of the NEXT front of the list) rebuilt for the shortened list
+        S.n_static_quad = 0;
+        S.q_prog_dyn.clear();
+        S.q_lists_dyn.assign(2 * lists.size(), 0);
+        S.row_keep.assign(static_cast<size_t>(S.n), 0);
+        for(size_t L = 0; L < lists.size(); ++L)
+        {
+            S.q_lists_dyn[2 * L] = static_cast<int>(S.q_prog_dyn.size());
+            size_t h = static_cast<size_t>(S.q_lists[2 * L]), prev = 0;
+            int kept = 0;
+            for(int const s: lists[L])
+            {
+                size_t const len = Symbolic::Q_HDR + static_cast<size_t>(S.q_prog[h + 4]) * Symbolic::Q_CHILD;
+                if(S.f_static[s])
+                {
+                    ++S.n_static_quad;
+                    for(int k = S.f_col0[s]; k < S.f_col0[s] + S.f_p[s]; ++k) S.row_keep[static_cast<size_t>(k)] = 1;
+                }
+                else
+                {
+                    size_t const d = S.q_prog_dyn.size();
+                    S.q_prog_dyn.insert(S.q_prog_dyn.end(), S.q_prog.begin() + static_cast<long>(h), S.q_prog.begin() + static_cast<long>(h + len));
+                    S.q_prog_dyn[d + 11] = S.q_prog_dyn[d + 12] = 0;
+                    if(kept > 0)
+                    {
+                        S.q_prog_dyn[prev + 11] = S.q_prog_dyn[d + 5];
+                        S.q_prog_dyn[prev + 12] = S.q_prog_dyn[d + 10];
+                    }
+                    prev = d;
+                    ++kept;
+                }
+                h += len;
+            }
+            S.q_lists_dyn[2 * L + 1] = kept;
+        }
+        if(S.q_prog_dyn.empty()) S.q_prog_dyn.push_back(0);
         S.q_bprog.clear();
         // owner front of every pivot column: a front of the backward walk reads the unknowns of its update rows, i.e. of the fronts that
         // own those columns.  It needs the wavefront's fence only if one of them was written by this wavefront since its last fence

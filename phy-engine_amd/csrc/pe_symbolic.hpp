@@ -61,6 +61,10 @@ namespace pe
         int max_pivots_top{64};
         long long panel_doubles_top{0};
         long long panel_doubles_mid{0};
+        // Static fronts (Symbolic::f_static): per CSR slot of A / per original row, != 0 where a contribution depends on x -- what the stamp of
+        // the later Newton iterations of a solve point gathers again.  Null (or of another size): nothing is known, every front is dynamic.
+        std::vector<char> const* dyn_slots{nullptr};
+        std::vector<char> const* dyn_rows{nullptr};
     long long panel_reserve{384};    // LDS doubles kept free behind the panels of a large front (right-hand-side column, staged child maps)
     long long panel_doubles{18000};  // LDS doubles available for the L (m x p) and U (p x u) panels of a cooperative front
     };
@@ -167,6 +171,19 @@ namespace pe
         std::vector<unsigned char> q2_lane;
         int n_mid{};
         long long q_zero_off{};                 // offset of the zero region in the arena (doubles)
+
+        // ---- static fronts (SymbolicOptions::dyn_slots / dyn_rows).  Front s is DYNAMIC when one of its own assembled entries is an
+        // x-dependent slot, one of its pivot rows an x-dependent row, or a child is dynamic; otherwise STATIC: in the Newton iterations after the
+        // first of a solve point it would recompute, bit for bit, the panels, update matrix, update vector and forward-substituted pivots of the
+        // first.  A static ROOT is a static front with a dynamic parent (or none): what it hands upward must survive the launch, so a static
+        // root of the lane-group kernel keeps its update matrix + vector in a persistent arena slot.  q_prog_dyn / q_lists_dyn are q_prog /
+        // q_lists without the static fronts (same blocks, same q_lane offsets, the look-ahead of hdr[11] / hdr[12] rebuilt); row_keep[k] = 1
+        // for the permuted rows k that are pivots of a static quad front (their forward-substituted value is kept across those iterations).
+        std::vector<int> f_static;              // per front: 1 = static (all 0 without dyn_slots / dyn_rows)
+        int n_static_quad{};                    // static fronts of the lane-group kernel (0: q_prog_dyn is not built)
+        long long static_root_doubles{};        // arena doubles the persistent slots of static quad roots added (they lived on the LIFO stacks)
+        std::vector<int> q_prog_dyn, q_lists_dyn;
+        std::vector<unsigned char> row_keep;
 
         // statistics
         long long nnz_LU{};      // structural nnz(L)+nnz(U) (diagonal counted once) of the supernodal pattern WITHOUT relaxation zeros

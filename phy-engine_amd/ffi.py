@@ -34,6 +34,7 @@ EXPORTS = [
     "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
+    "pe_hip_get_static_fronts", "pe_hip_get_static_skip_stats", "pe_hip_get_static_skip_refinement_stats",
 ]
 DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
 # pe_hip_measure_kind
@@ -211,6 +212,9 @@ def lib():
         l.pe_hip_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
         l.pe_hip_get_info.argtypes = [C.c_void_p, C.POINTER(Info)]
         l.pe_hip_get_front_table.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 9
+        l.pe_hip_get_static_fronts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        l.pe_hip_get_static_skip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        l.pe_hip_get_static_skip_refinement_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         l.pe_hip_set_digital_drives.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         l.pe_hip_update_param.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
         l.pe_hip_reset.argtypes = [C.c_void_p]
@@ -428,6 +432,22 @@ class Engine(_Probes):
         out = {k: np.zeros(n.value, dtype=np.int32) for k in names}
         self._chk(lib().pe_hip_get_front_table(self._h, int(which), n.value, *[_ip(out[k]) for k in names], C.byref(n)))
         return out
+
+    def static_fronts(self, which=0):
+        """int32 array in the order of front_table(which): 1 = the front's whole subtree holds no x-dependent entry or row (pe_hip_get_static_fronts)"""
+        n = C.c_int()
+        self._chk(lib().pe_hip_get_static_fronts(self._h, int(which), 0, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.int32)
+        self._chk(lib().pe_hip_get_static_fronts(self._h, int(which), n.value, _ip(out), C.byref(n)))
+        return out
+
+    def static_skip_stats(self):
+        """lane-group factor launches since load: {'skipped_launches': without the static fronts, 'full_launches': the others}"""
+        a, b = C.c_longlong(), C.c_longlong()
+        self._chk(lib().pe_hip_get_static_skip_stats(self._h, C.byref(a), C.byref(b)))
+        c, d = C.c_longlong(), C.c_longlong()
+        self._chk(lib().pe_hip_get_static_skip_refinement_stats(self._h, C.byref(c), C.byref(d)))
+        return {"skipped_launches": a.value, "full_launches": b.value, "launches_after_refinement": c.value, "skipped_after_refinement": d.value}
 
     def reset(self):
         self._chk(lib().pe_hip_reset(self._h))
