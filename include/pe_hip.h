@@ -328,7 +328,10 @@ int pe_hip_checkpoint_load(pe_hip_engine* h, const void* buffer, size_t size);
 /* Small-signal AC at angular frequency omega [rad/s] (circult::solve_once with the models' iterate_ac hooks; one call per
  * sweep point of run_ac_analysis, circuit.h:389-431).  Non-linear devices are stamped at their last linearisation: run
  * pe_hip_analyze_dc(PE_HIP_MODE_OP) first, as the reference's AC / ACOP cases do (circuit.h:192-232).  The complex system
- * is solved in real-equivalent form [Ar -Ai; Ai Ar] by the same kernels.  pe_hip_get_solution_ac returns the phasors. */
+ * is solved in real-equivalent form [Ar -Ai; Ai Ar] by the same kernels.  pe_hip_get_solution_ac returns the phasors.
+ * Up to three rounds of iterative refinement while the componentwise backward error is above 4e-16 or not a number, then one closing
+ * residual evaluation: PE_HIP_ERR_INACCURATE when that final backward error is not finite (the sweep below applies the same rule per
+ * instance). */
 int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* stats);
 int pe_hip_get_solution_ac(pe_hip_engine* h, int first_instance, int count, double* re, double* im);
 
@@ -379,6 +382,25 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
 
 /* phasors of the last sweep, in the CALLER's point order: re / im [n_points][count][n_kept_rows]; a failed point reads NaN */
 int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, double* re, double* im);
+
+/* Read-back of a small-signal system as the device last assembled it (pe_hip_get_matrix reads the main engine only): the 2N x 2N
+ * real-equivalent system [Ar -Ai; Ai Ar] in CSR with sorted columns (explicit zeros included), N = rows of the circuit.
+ *   which  0: the single-point engine of pe_hip_analyze_ac;  1: the batched engine of the last pass of pe_hip_analyze_ac_sweep, instance
+ *          q = b * P + p (circuit instance b, point p of that pass; unused points of a pass repeat its last omega);  2 / 3: the
+ *          single-point and the batched engine of pe_hip_analyze_noise (the adjoint, i.e. transposed, system).  Engine 2 only sizes the
+ *          automatic pass: it never assembles values, so asking it for vals is PE_HIP_ERR_ARG.
+ *   vals   the values of the last assembly (vals may be NULL).
+ *   rhs    [2N] the right-hand side AS STAMPED -- the copy the refinement keeps, not the residual a refinement round leaves in the value
+ *          vector (may be NULL).  PE_HIP_ERR_ARG when the last solve on that engine failed before the copy was taken.
+ * Capacity-0-first like pe_hip_get_front_table: with nnz_capacity == 0 only *n_rows (2N) and *nnz are written; else nnz_capacity >= nnz,
+ * row_ptr holds 2N + 1 ints, col_ind / vals nnz entries.  PE_HIP_ERR_ARG when that engine does not exist yet.  Launches nothing.
+ * pe_hip_get_ac_pass_size: P of engine 1 or 3.  pe_hip_get_ac_analysis_omega: the omega whose values the pivot order of engine 0 was last
+ * matched on (-1: none yet) -- pe_hip_analyze_ac matches again when there is none, when omega == 0 and that one are not both zero, or when
+ * omega > 10 x or < 0.1 x that one. */
+int pe_hip_get_matrix_ac(pe_hip_engine* h, int which, int instance, int nnz_capacity, int* row_ptr, int* col_ind, double* vals, double* rhs, int* n_rows,
+                         int* nnz);
+int pe_hip_get_ac_pass_size(pe_hip_engine* h, int which, int* points_per_pass);
+int pe_hip_get_ac_analysis_omega(pe_hip_engine* h, double* omega);
 
 /* ---- DC sweep (.DC): the operating point at every value of one swept parameter, as one call.  The points become extra instances of the
  * circuit on an engine of its own (batch = instances of the circuit x points per pass); the swept value is written on the device, the

@@ -255,7 +255,8 @@ namespace pe
                     A_set_re(k[2], n[4], DV_ONE, true);
                     A_re(k[2], n[0], v, true, false);
                     A_re(k[2], n[1], v, false, false);
-                    A_set_re(k[0], k[0], DV_ONE, false);
+                    // transformer_center_tap.h:124-130: D(kP, kP) = 1 only under n_half != 0 (v is 0 otherwise: the row stays empty)
+                    A_set_re(k[0], k[0], slot(AcSlot::XCT_ON, g), false);
                     A_set_re(k[0], k[1], v, false);
                     A_set_re(k[0], k[2], v, false);
                     break;
@@ -409,6 +410,7 @@ namespace pe
                     (void)gen_static_value(d.kind, &hc.gen_par[B * hc.gen_par_len + d.par], r_open, v);
                     break;
                 }
+                case AcSlot::XCT_ON: v = hc.gen_par[B * hc.gen_par_len + hc.gen[s.idx].par] != 0.0 ? 1.0 : 0.0; break;
                 case AcSlot::RELAY_R: v = op.rl_engaged[B * hc.nRl() + s.idx] ? 0.0 : r_open; break;
                 case AcSlot::IAC_RE:
                 case AcSlot::IAC_IM:

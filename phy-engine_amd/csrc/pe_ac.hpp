@@ -28,7 +28,8 @@ namespace pe
             N3_0, N3_1,  // MOSFET / BJT aux idx: gds, gm | geq, gm of its last linearisation (dv of the main engine)
             DRIVE,      // digital drive idx: its voltage (circuit.h:1015-1022 stamps it in every mode)
             OV_A_RE, OV_A_IM,  // host-stamp overlay cell idx: real / imaginary part of what the models' iterate_ac hooks stamped there
-            OV_B_RE, OV_B_IM   // ... right-hand-side row idx
+            OV_B_RE, OV_B_IM,  // ... right-hand-side row idx
+            XCT_ON      // generic device idx (centre-tapped transformer): 1 when n_total != 0, else 0 -- the ampere-turns row is stamped only then
         };
         int kind, idx;
     };

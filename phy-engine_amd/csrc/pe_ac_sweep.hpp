@@ -97,7 +97,8 @@ namespace pe
 
     // NaN-keeping maximum of non-negative values (fmax would drop the NaN a broken instance must show)
     PE_DEV double ac_nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
-    PE_DEV bool ac_needs_refinement(double worst) { return !(worst <= AC_REFINE_TOL); }
+    // (also the host's test in pe_hip_analyze_ac: one rule on both paths, a NaN needs refinement)
+    PE_AC_HD bool ac_needs_refinement(double worst) { return !(worst <= AC_REFINE_TOL); }
 
     // ac_residual (pe_front.hpp) of instance q with a NaN-keeping maximum: r = b0 - A xacc into the right-hand-side value slots, returns
     // this thread's worst componentwise backward error

@@ -48,6 +48,7 @@ namespace
         if(W.eng) pe_hip_destroy(W.eng);  // (synchronises its stream first: nothing reads the buffers below any more)
         W.eng = nullptr;
         W.P = 0;
+        W.b0_valid = false;
         W.pass_pool.release();
     }
 
@@ -216,6 +217,7 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
         HIPCHK(h, hipMemset(A.eng->V.status, 0, static_cast<size_t>(B) * sizeof(int)));
         return pe_hip_analyze_dc(A.eng, PE_HIP_MODE_DC, st);
     };
+    A.b0_valid = false;
     int rc = solve(true);
     if(rc == PE_HIP_ERR_SINGULAR && A.sym_omega != omega)
     {
@@ -227,19 +229,24 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
     // complex pivot: entries like r_open = 1e12 next to j omega C leave errors far above rounding): r = b - A x in fp64 from the
     // system as the device assembled it (k_ac_residual), A dx = r with the same pivot order, x += dx (k_ac_accumulate); at most
     // three rounds, stops once the componentwise backward error is at rounding level.  The host reads one double per round.
+    // One rule with the sweep (run_pass below): a backward error that is not a number needs refinement like one above the threshold
+    // (pe::ac_needs_refinement), the iterate the last correction produced gets a residual evaluation of its own, and phasors whose final
+    // backward error is not finite are not returned as PE_HIP_OK.
     hipStream_t const es = A.eng->stream;
     HIPCHK(h, pe::launch_ac_accumulate(es, A.eng->V, A.d_xacc, A.d_b0, true));
-    for(int round = 0; round < 3; ++round)
+    A.b0_valid = true;
+    double worst = 0.0;
+    for(int round = 0;; ++round)
     {
         HIPCHK(h, pe::launch_ac_residual(es, A.eng->V, A.d_xacc, A.d_b0, A.rhs0, A.d_worst));
-        double worst = 0.0;
         HIPCHK(h, hipMemcpyAsync(&worst, A.d_worst, sizeof(double), hipMemcpyDeviceToHost, es));
         HIPCHK(h, hipStreamSynchronize(es));
-        if(!(worst > 4.0e-16)) break;
+        if(!pe::ac_needs_refinement(worst) || round == 3) break;
         rc = solve(false);
         if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac (refinement): " + A.eng->err);
         HIPCHK(h, pe::launch_ac_accumulate(es, A.eng->V, A.d_xacc, A.d_b0, false));
     }
+    if(!std::isfinite(worst)) return fail(h, PE_HIP_ERR_INACCURATE, "analyze_ac: the backward error of the refined solution is not finite");
     A.x.resize(A.d_len);
     HIPCHK(h, hipMemcpyAsync(A.x.data(), A.d_xacc, A.d_len * sizeof(double), hipMemcpyDeviceToHost, es));
     HIPCHK(h, hipStreamSynchronize(es));
@@ -469,17 +476,20 @@ namespace
             HIPCHK(h, hipMemcpy(const_cast<int*>(W.V.point), point_h.data(), static_cast<size_t>(P) * sizeof(int), hipMemcpyHostToDevice));
             std::fill(inst_status.begin(), inst_status.end(), 0);
             HIPCHK(h, hipEventRecord(h->ev0, es));
+            W.b0_valid = false;
             HIPCHK(h, pe::launch_ac_sweep_fill(es, E->V, W.V));
             if(int const rc = solve(); rc != PE_HIP_OK) return rc;
             HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
-            // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds), decided per instance: the host reads one int per round
+            W.b0_valid = true;
+            // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds, then one closing residual evaluation of the iterate the
+            // third correction produced), decided per instance: the host reads one int per round
             int above = 0;
-            for(int round = 0; round < 3; ++round)
+            for(int round = 0;; ++round)
             {
                 HIPCHK(h, pe::launch_ac_residual_each(es, E->V, W.V));
                 HIPCHK(h, hipMemcpyAsync(&above, W.V.n_above, sizeof(int), hipMemcpyDeviceToHost, es));
                 HIPCHK(h, hipStreamSynchronize(es));
-                if(above == 0) break;
+                if(above == 0 || round == 3) break;
                 if(int const rc = solve(); rc != PE_HIP_OK) return rc;
                 HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, false));
                 ++S.n_refine_rounds;
@@ -697,6 +707,51 @@ int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
         std::memcpy(re + dst, &W.res[src], static_cast<size_t>(count) * K * sizeof(double));
         std::memcpy(im + dst, &W.res[plane + src], static_cast<size_t>(count) * K * sizeof(double));
     }
+    return PE_HIP_OK;
+}
+
+/* Read-back of a small-signal system (include/pe_hip.h): the inner engine's pe_hip_get_matrix for pattern and values, the refinement's copy
+ * of the right-hand side as stamped for rhs.  Launches nothing. */
+int pe_hip_get_matrix_ac(pe_hip_engine* h, int which, int instance, int nnz_capacity, int* row_ptr, int* col_ind, double* vals, double* rhs, int* n_rows,
+                         int* nnz)
+{
+    if(!h || !h->loaded || which < 0 || which > 3 || nnz_capacity < 0) return PE_HIP_ERR_ARG;
+    auto& A = which < 2 ? h->ac : h->noise.sys;
+    bool const batched = (which & 1) != 0;
+    pe_hip_engine* const E = batched ? A.sweep.eng : A.eng;
+    if(!A.built || !E || !E->loaded) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: that engine does not exist yet");
+    int const R2 = E->hc.rows, nz = static_cast<int>(E->hc.ci.size());
+    if(n_rows) *n_rows = R2;
+    if(nnz) *nnz = nz;
+    if(nnz_capacity == 0) return PE_HIP_OK;
+    if(nnz_capacity < nz) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: nnz_capacity below the system's nnz");
+    if(instance < 0 || instance >= E->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: instance out of range");
+    if(int const rc = pe_hip_get_matrix(E, instance, row_ptr, col_ind, vals, nullptr); rc != PE_HIP_OK) return fail(h, rc, "get_matrix_ac: " + E->err);
+    if(rhs)
+    {
+        double const* b0 = batched ? A.sweep.V.b0 : A.d_b0;
+        bool const valid = batched ? A.sweep.b0_valid : (A.b0_valid && A.d_len == static_cast<size_t>(E->hc.batch) * R2);
+        if(!b0 || !valid) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: no right-hand side has been stamped on that engine (its last solve failed, or none ran)");
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemcpy(rhs, b0 + static_cast<size_t>(instance) * R2, static_cast<size_t>(R2) * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_ac_analysis_omega(pe_hip_engine* h, double* omega)
+{
+    if(!h || !h->loaded || !omega) return PE_HIP_ERR_ARG;
+    if(!h->ac.built) return fail(h, PE_HIP_ERR_ARG, "get_ac_analysis_omega: that engine does not exist yet");
+    *omega = h->ac.sym_omega;
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_ac_pass_size(pe_hip_engine* h, int which, int* points_per_pass)
+{
+    if(!h || !h->loaded || !points_per_pass || (which != 1 && which != 3)) return PE_HIP_ERR_ARG;
+    auto const& W = (which == 1 ? h->ac : h->noise.sys).sweep;
+    if(!W.eng) return fail(h, PE_HIP_ERR_ARG, "get_ac_pass_size: that engine does not exist yet");
+    *points_per_pass = W.P;
     return PE_HIP_OK;
 }
 

@@ -191,12 +191,14 @@ struct pe_hip_engine
         std::vector<double> x;            // refined solution [batch][2N]
         double *d_xacc{}, *d_b0{}, *d_worst{};  // device: accumulated solution, the point's right-hand side, worst backward error (refinement)
         size_t d_len{};
+        bool b0_valid{};  // d_b0 holds the right-hand side of the last pe_hip_analyze_ac as stamped (pe_hip_get_matrix_ac)
         // frequency-batched sweep (pe_hip_analyze_ac_sweep): a third engine holding the same system with batch (circuit batch) x P -- the
         // points of one pass are extra instances --, the buffers of its kernels (pe_ac_sweep.hpp) and the stored result
         struct Sweep
         {
             pe_hip_engine* eng{};
             int P{};                          // points per pass the engine was built for
+            bool b0_valid{};                  // V.b0 holds the right-hand sides of the last pass as stamped (pe_hip_get_matrix_ac)
             Pool pass_pool;                   // sized by batch x P: xacc, b0, worst, omega, point, n_above
             Pool circ_pool;                   // sized by the circuit: base vectors, scale flags, right-hand-side lists
             Pool res_pool;                    // sized by the sweep: the result planes

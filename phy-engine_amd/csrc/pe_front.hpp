@@ -1585,7 +1585,7 @@ namespace pe
     // Refinement residual of a small-signal AC point (pe_engine_ac.cpp pe_hip_analyze_ac; the complex system in real-equivalent form):
     // r = b0 - A xacc with A as the last stamp assembled it, written into the instance's right-hand-side VALUE SLOTS
     // dv[rhs0 + row] -- the correction solve that follows gathers its right-hand side from there.  Returns this thread's worst
-    // componentwise backward error |r_i| / (|b_i| + sum_j |a_ij x_j|).
+    // componentwise backward error |r_i| / (|b_i| + sum_j |a_ij x_j|), NaN if any row's is.
     template <class Team>
     PE_DEV double ac_residual(Team const& tm, DevView const& V, int b, double const* xacc_all, double const* b0_all, int rhs0)
     {
@@ -1605,7 +1605,8 @@ namespace pe
                 mag += fabs(t);
             }
             dv[rhs0 + r] = acc;
-            worst = fmax(worst, fabs(acc) / (mag > 0.0 ? mag : 1.0));
+            double const w = fabs(acc) / (mag > 0.0 ? mag : 1.0);
+            worst = (w > worst || w != w) ? w : worst;  // (keeps a NaN: fmax would drop the one a broken instance must show)
         }
         return worst;
     }

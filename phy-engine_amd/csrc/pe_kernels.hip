@@ -1630,9 +1630,15 @@ namespace pe
     __global__ void __launch_bounds__(256) k_ac_residual(DevView V, double const* __restrict__ xacc, double const* __restrict__ b0, int rhs0, double* worst)
     {
         int const b = static_cast<int>(blockIdx.y);
-        double const w = WaveOps{}.wave_max(ac_residual(GridTeam{}, V, b, xacc, b0, rhs0));
-        // (non-negative doubles order like their bit patterns; a NaN residual has the largest pattern: the host sees it)
-        if((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(worst), static_cast<unsigned long long>(__double_as_longlong(fabs(w))));
+        // (non-negative doubles order like their bit patterns and a NaN has the largest pattern: reduced as integers, nothing drops it)
+        unsigned long long u = static_cast<unsigned long long>(__double_as_longlong(fabs(ac_residual(GridTeam{}, V, b, xacc, b0, rhs0))));
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1)
+        {
+            unsigned long long const t = __shfl_xor(u, o);
+            u = t > u ? t : u;
+        }
+        if((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(worst), u);
     }
     __global__ void __launch_bounds__(256) k_ac_accumulate(DevView V, double* __restrict__ xacc, double* __restrict__ b0, int first)
     {

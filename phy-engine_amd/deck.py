@@ -642,3 +642,63 @@ def ac_nmos_amp() -> Deck:
     d.add("NMOS", (5, 3, 0), 2e-3, 0.02, 1.0)
     d.add("C", (5, 0), 1e-9)
     return d
+
+
+def ac_controlled_rest() -> Deck:
+    """The kinds no other AC fixture has, linear side: CCCS, CCVS, op-amp (follower), centre-tapped transformer, a relay held engaged by a
+    coil source and a time generator (an AC short), driven by one VAC; ACOP (the relay takes its state from the operating point)."""
+    d = Deck()
+    d.n_nodes = 12
+    d.add("VAC", (1, 0), 1.0, 1e4, 0.2)
+    d.add("R", (1, 2), 1000.0)
+    d.add("C", (2, 0), 1e-7)
+    d.add("CCCS", (3, 0, 2, 4), 2.0)
+    d.add("R", (4, 0), 300.0)
+    d.add("R", (3, 0), 150.0)
+    d.add("CCVS", (5, 0, 3, 6), 500.0)
+    d.add("R", (6, 0), 1000.0)
+    d.add("R", (5, 0), 1000.0)
+    d.add("OPAMP", (5, 7, 7, 0), 1e3)
+    d.add("R", (7, 0), 1000.0)
+    d.add("XCT", (7, 0, 8, 0, 9), 2.0)
+    d.add("R", (8, 0), 100.0)
+    d.add("R", (9, 0), 100.0)
+    d.add("VDC", (10, 0), 6.0)
+    d.add("RELAY", (10, 0, 8, 11), 5.0, 3.0)
+    d.add("R", (11, 0), 1000.0)
+    d.add("C", (11, 0), 1e-8)
+    d.add("SAW", (12, 0), 5.0, 0.0, 1e3, 0.0)
+    d.add("R", (12, 11), 2000.0)
+    return d
+
+
+def ac_transistors() -> Deck:
+    """The kinds no other AC fixture has, non-linear side: PMOS, NPN, PNP and a diode with tt at an operating point (junctions of the BJTs
+    held by sources: their models have no junction limiting), each stage driven through a coupling capacitor; ACOP."""
+    d = Deck()
+    d.n_nodes = 15
+    d.add("VDC", (1, 0), 5.0)
+    d.add("VAC", (2, 0), 0.01, 1e4, 0.0)
+    d.add("R", (2, 3), 100.0)
+    d.add("R", (1, 4), 1000.0)
+    d.add("D", (4, 5), 1e-14, 1.0, 0.0, 2.0, 27.0, 1e-3, 40.0, 1.0, 1.0, 1e-8)
+    d.add("R", (5, 0), 100.0)
+    d.add("C", (3, 4), 1e-7)
+    d.add("PMOS", (6, 7, 1), 1e-3, 0.05, 1.0)
+    d.add("R", (6, 0), 500.0)
+    d.add("R", (1, 7), 1e5)
+    d.add("R", (7, 0), 1e5)
+    d.add("C", (3, 7), 1e-7)
+    d.add("VDC", (8, 0), 0.85)      # base bias through 1 kOhm, emitter on 0.25 V: Vbe = 0.6 V less the base current's drop
+    d.add("R", (8, 9), 1000.0)
+    d.add("VDC", (11, 0), 0.25)
+    d.add("NPN", (9, 10, 11), 1e-15, 1.0, 150.0, 27.0, 1.0)
+    d.add("R", (1, 10), 2200.0)
+    d.add("C", (3, 9), 1e-7)
+    d.add("VDC", (12, 0), 4.15)
+    d.add("R", (12, 13), 1000.0)
+    d.add("VDC", (15, 0), 4.75)
+    d.add("PNP", (13, 14, 15), 1e-15, 1.0, 150.0, 27.0, 1.0)
+    d.add("R", (14, 0), 2200.0)
+    d.add("C", (3, 13), 1e-7)
+    return d

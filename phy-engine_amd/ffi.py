@@ -35,6 +35,7 @@ EXPORTS = [
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
     "pe_hip_get_static_fronts", "pe_hip_get_static_skip_stats", "pe_hip_get_static_skip_refinement_stats",
+    "pe_hip_get_matrix_ac", "pe_hip_get_ac_pass_size", "pe_hip_get_ac_analysis_omega",
 ]
 DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
 # pe_hip_measure_kind
@@ -242,6 +243,9 @@ def lib():
         l.pe_hip_set_ac_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(AcSweepStats)]
         l.pe_hip_get_ac_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_get_matrix_ac.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        l.pe_hip_get_ac_pass_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_noise.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(NoiseControl), C.POINTER(C.c_int), C.POINTER(NoiseStats)]
         l.pe_hip_get_noise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.pe_hip_get_noise_sources.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 6
@@ -612,6 +616,34 @@ class Engine(_Probes):
         d = st.asdict()
         d["rc"] = rc
         return re + 1j * im, status[:n], d
+
+    def matrix_ac(self, which=0, instance=0, rhs=True):
+        """(row_ptr, col_ind, vals, rhs) of a small-signal system as the device last assembled it (pe_hip_get_matrix_ac): the 2N
+        real-equivalent system of the single-point engine (which 0), of instance q = b * P + p of the sweep's last pass (1), of the noise
+        analysis' adjoint engines (2 / 3).  rhs: as stamped, or None with rhs=False."""
+        n, nz = C.c_int(), C.c_int()
+        self._chk(lib().pe_hip_get_matrix_ac(self._h, int(which), int(instance), 0, None, None, None, None, C.byref(n), C.byref(nz)))
+        rp = np.empty(n.value + 1, dtype=np.int32)
+        ci = np.empty(nz.value, dtype=np.int32)
+        va = np.empty(nz.value)
+        b = np.empty(n.value) if rhs else None
+        self._chk(lib().pe_hip_get_matrix_ac(self._h, int(which), int(instance), nz.value, _ip(rp), _ip(ci), _dp(va), _dp(b) if rhs else None,
+                                             C.byref(n), C.byref(nz)))
+        return rp, ci, va, b
+
+    def ac_analysis_omega(self):
+        """omega whose values the single-point AC engine's pivot order was last matched on (-1.0: none yet)"""
+        w = C.c_double()
+        fn = lib().pe_hip_get_ac_analysis_omega
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._chk(fn(self._h, C.byref(w)))
+        return w.value
+
+    def ac_pass_size(self, which=1):
+        """points per pass P of the batched engine of the last analyze_ac_sweep (which 1) or analyze_noise (3)"""
+        p = C.c_int()
+        self._chk(lib().pe_hip_get_ac_pass_size(self._h, int(which), C.byref(p)))
+        return p.value
 
     def set_dc_sweep_rows(self, rows=None):
         """rows of x kept for every point of the following analyze_dc_sweep calls; None / empty: all rows"""

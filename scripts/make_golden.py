@@ -89,11 +89,18 @@ CASES["relay_ramp_tr"] = (("relay_ramp", {}), "TR", 1e-4, 200, 0.0, "1,30,62,63,
 
 # small-signal AC: snapshots are [Re x ; Im x] per frequency point
 AC_OMEGAS = {"ac_rc_lowpass": [10.0, 1000.0, 1e5], "ac_rlc_diode_acop": [0.0, 1e3, 2e4, 1e6], "ac_linear_mix": [100.0, 6283.185307179586, 1e5],
-             "ac_nmos_amp": [1e2, 6.283185307179586e4, 1e7]}
+             "ac_nmos_amp": [1e2, 6.283185307179586e4, 1e7],
+             "ac_controlled_rest_acop": [0.0, 1e3, 1e4, 1e6], "ac_transistors_acop": [6.283185307179586e4], "ac_transistors_hf_acop": [1e7]}
 CASES["ac_rc_lowpass"] = (("ac_rc_lowpass", {}), "AC", 0.0, 0, 0.0, "", True)
 CASES["ac_rlc_diode_acop"] = (("ac_rlc_diode", {}), "ACOP", 0.0, 0, 0.0, "", True)
 CASES["ac_linear_mix"] = (("ac_linear_mix", {}), "AC", 0.0, 0, 0.0, "", True)
 CASES["ac_nmos_amp"] = (("ac_nmos_amp", {}), "AC", 0.0, 0, 0.0, "", True)
+# the kinds no fixture above solves in AC: CCCS, CCVS, OPAMP, XCT, relay, a time generator | PMOS, NPN, PNP, a diode with tt
+CASES["ac_controlled_rest_acop"] = (("ac_controlled_rest", {}), "ACOP", 0.0, 0, 0.0, "", True)
+# (one point per fixture: the driver runs OP + AC per point, and from the second point on its OP starts from the node voltages the previous
+# AC solve left, not from zero -- the diode's last linearisation then differs within the Newton tolerance, 5e-4 in these phasors)
+CASES["ac_transistors_acop"] = (("ac_transistors", {}), "ACOP", 0.0, 0, 0.0, "", True)
+CASES["ac_transistors_hf_acop"] = (("ac_transistors", {}), "ACOP", 0.0, 0, 0.0, "", True)
 
 
 # fine-step references of the variable-step transient's accuracy tests (tests/test_tr_adaptive_emu.py): every 100th step of a run whose

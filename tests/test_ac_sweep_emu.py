@@ -87,7 +87,7 @@ def run(emu, body, **env):
     return r.stdout
 
 
-@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_linear_mix", "ac_nmos_amp", "ac_rlc_diode_acop"])
+@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_linear_mix", "ac_nmos_amp", "ac_rlc_diode_acop", "ac_controlled_rest_acop", "ac_transistors_acop", "ac_transistors_hf_acop"])
 def test_reference_goldens_in_one_sweep(emu, name):
     run(emu, r'''
 meta, gx, deck = golden(%r)

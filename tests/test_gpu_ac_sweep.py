@@ -51,7 +51,7 @@ def loop(e, omegas):
     return np.array(out)
 
 
-@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_linear_mix", "ac_nmos_amp", "ac_rlc_diode_acop"])
+@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_linear_mix", "ac_nmos_amp", "ac_rlc_diode_acop", "ac_controlled_rest_acop", "ac_transistors_acop", "ac_transistors_hf_acop"])
 def test_reference_goldens_in_one_sweep(name):
     meta, gx, deck = golden(name)
     e = engine(deck, op=meta["analysis"] == "ACOP" or deck.has_nonlinear(), g_min=meta["gmin"], r_open=meta.get("r_open", 0.0))

@@ -459,7 +459,7 @@ def test_reuse_factor_multi_workgroup():
 
 
 # ---- small-signal AC (complex system solved in real-equivalent form by the same kernels) ----------
-@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_rlc_diode_acop", "ac_linear_mix", "ac_nmos_amp"])
+@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_rlc_diode_acop", "ac_linear_mix", "ac_nmos_amp", "ac_controlled_rest_acop", "ac_transistors_acop", "ac_transistors_hf_acop"])
 def test_ac_golden_parity(eng, name):
     meta, gx, deck = golden(name)
     xs = run_ac_case(eng, meta, deck)

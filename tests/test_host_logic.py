@@ -241,7 +241,7 @@ assert eng.info()['n_wavefronts'] == 4 and eng.info()['n_parts'] == 4
     subprocess.run(["python3", "-c", code], check=True, timeout=300)
 
 
-@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_rlc_diode_acop", "ac_linear_mix", "ac_nmos_amp"])
+@pytest.mark.parametrize("name", ["ac_rc_lowpass", "ac_rlc_diode_acop", "ac_linear_mix", "ac_nmos_amp", "ac_controlled_rest_acop", "ac_transistors_acop", "ac_transistors_hf_acop"])
 def test_ac_real_equivalent_system_under_host_emulation(emu_lib, name):
     """The AC path's host logic (real-equivalent 2N system, value vector per omega, operating-point hand-over) with the
     kernels emulated; compared with the reference's complex phasors."""

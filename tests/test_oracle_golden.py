@@ -51,7 +51,7 @@ def test_oracle_unlimited_exponential_fails_like_reference(oracle_mod, name):
     assert o.newton_iters[0] < 0
 
 
-AC_CASES = ["ac_rc_lowpass", "ac_rlc_diode_acop", "ac_linear_mix", "ac_nmos_amp"]
+AC_CASES = ["ac_rc_lowpass", "ac_rlc_diode_acop", "ac_linear_mix", "ac_nmos_amp", "ac_controlled_rest_acop", "ac_transistors_acop", "ac_transistors_hf_acop"]
 
 
 @pytest.mark.parametrize("name", AC_CASES)
