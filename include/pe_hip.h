@@ -388,8 +388,9 @@ int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
  *   which  0: the single-point engine of pe_hip_analyze_ac;  1: the batched engine of the last pass of pe_hip_analyze_ac_sweep, instance
  *          q = b * P + p (circuit instance b, point p of that pass; unused points of a pass repeat its last omega);  2 / 3: the
  *          single-point and the batched engine of pe_hip_analyze_noise (the adjoint, i.e. transposed, system).  Engine 2 only sizes the
- *          automatic pass: it never assembles values, so asking it for vals is PE_HIP_ERR_ARG.
- *   vals   the values of the last assembly (vals may be NULL).
+ *          automatic pass: it never assembles values, so asking it for vals is PE_HIP_ERR_ARG.  4: the batched engine of the last pass of
+ *          pe_hip_analyze_sens (the adjoint system at omega = 0), instance q = b * P + p, rhs the selector of the output in slot p.
+ *   vals  the values of the last assembly (vals may be NULL).
  *   rhs    [2N] the right-hand side AS STAMPED -- the copy the refinement keeps, not the residual a refinement round leaves in the value
  *          vector (may be NULL).  PE_HIP_ERR_ARG when the last solve on that engine failed before the copy was taken.
  * Capacity-0-first like pe_hip_get_front_table: with nnz_capacity == 0 only *n_rows (2N) and *nnz are written; else nnz_capacity >= nnz,
@@ -546,6 +547,78 @@ int pe_hip_get_noise_sources(pe_hip_engine* h, int capacity, int* kind, int* ind
 int pe_hip_get_noise_source_density(pe_hip_engine* h, int first_instance, int count, double* s);
 /* integrated output noise of the last call over its band, [count], V^2 (A^2) */
 int pe_hip_get_noise_integrated(pe_hip_engine* h, int first_instance, int count, double* v2);
+
+/* ---- DC sensitivity analysis (.SENS): the first-order sensitivity of one or more outputs of the resident operating point to EVERY device
+ * parameter of every instance, by the ADJOINT method: one solve per output, whatever the number of parameters.  With the residual
+ * f(x, p) = A(x; p) x - b(x; p) of the operating point, J its Jacobian and e the output selector, J^T y = e gives
+ * d out / d p_k = -y^T d f / d p_k.  J^T is the adjoint small-signal system of pe_hip_analyze_noise at omega = 0 (the AC stamp at
+ * omega = 0 is the Newton Jacobian cell for cell); the outputs are the "points" of that sweep body, all in one band.
+ *   Output o.  x[out_pos[o]] - x[out_neg[o]] (rows 0-based as everywhere, -1 = ground).  out_pos[o] == out_neg[o] is PE_HIP_ERR_ARG.
+ *   Operating point.  The last linearisation, exactly as pe_hip_analyze_ac / _noise use it: the Jacobian is the one of the last stamp, and
+ *   d f / d p is evaluated at the resident x with the arm of the model that the device evaluation takes there.  The Jacobian therefore
+ *   belongs to the iterate BEFORE the accepted one: the result is exact to first order in the last Newton step.  A caller who wants it
+ *   tighter runs pe_hip_analyze_dc once more from the converged point.  Whatever mode produced the resident point (OP, DC, TROP, a TR step)
+ *   is taken as it is; reactive elements are at omega = 0 (capacitors open, inductors shorted), and the diffusion-capacitance companion a
+ *   transient stamp folds into a junction is taken out, as in the noise analysis.  An instance whose last analysis failed has no
+ *   operating point: the call returns that status, every output carries it and everything reads NaN.
+ *   The Jacobian is the STAMPED matrix.  Two arms of the models stamp a conductance that is not the slope of the current they stamp: a
+ *   PMOS (gds and gm carry the opposite sign, as in the reference's pmosfet.h) and a junction on the linear continuation of the limited
+ *   exponential (Ud / (N Ut) > 50: Is limexp / Ute instead of Is exp(50) / Ute).  Newton's fixed point is the same, but on those arms the
+ *   result is not the derivative of the converged output (figures: DESIGN.md 8).
+ *   Parameters.  Named as pe_hip_update_param names them -- raw columns (kind, index in its table, column) -- in a table that is fixed per
+ *   circuit and readable without an analysis (pe_hip_get_sens_params), in this order:
+ *     1. PE_HIP_R column 0, in table order;  2. PE_HIP_VDC column 0;  3. PE_HIP_IDC column 0;
+ *     4. every entry of the diode table, in table order, each with columns Is, N, Isr, Nr, Temp, Ibv, Bv, Area (0-6 and 8; not Bv_set, tt,
+ *        tt_in_tr);
+ *     5. the remaining kinds table by table in the order the tables were passed to pe_hip_load_circuit, each in table order: VCCS g, VCVS mu,
+ *        CCCS alpha, CCVS r, OPAMP mu, XFMR n, XFMR_CT n_total (one column each); MOSFETs Kp, lambda, Vth; BJTs Is, N, BetaF, Temp, Area.
+ *   A device with an unconnected pin keeps its place and reads 0.  Everything else is a constant of the analysis: C, L, coupled inductors,
+ *   VAC / IAC, generators, switch, relay, digital drives, g_min, r_open.  The raw columns reach the device as derived ones (a junction's
+ *   Is Area, N Ut, Nr Ut, Bv_eff = Bv - N Ut ln(Ibv / (Is Area)); a BJT's Is Area, N Ut): the chain rule through that derivation is part of
+ *   the result, the breakdown arm and the linear continuation of the limited exponential included.  A centre-tapped transformer with
+ *   n_total = 0 reads 0.
+ *   Results.  s[o][b][k] = d out_o / d p_k of instance b.  normalized = 1: p_k d out_o / d p_k, and a parameter that is 0 reads 0 (a
+ *   resistor's p_k is the reciprocal of its resident conductance).  weight (NULL: none; [n_params], shared by the batch, finite): the call
+ *   also forms rss[o][b] = sum_k (w_k s[o][b][k])^2 over the returned (normalised when asked) values; with w_k = sigma_k this is the
+ *   first-order variance of the output.  keep_sensitivities = 0 returns only rss: nothing of size n_params comes back to the host
+ *   (keep_sensitivities = 0 without weights asks for nothing: PE_HIP_ERR_ARG).
+ *   Passes.  P outputs x batch instances per pass.  Knob SENS_OUTPUTS (pe_hip_set_knob / PHY_ENGINE_HIP_SENS_OUTPUTS, read at every call);
+ *   0 = automatic by the memory rule of pe_hip_analyze_ac_sweep.  One symbolic analysis, on the values of instance 0.  An output with a
+ *   failing or non-finite instance in its pass is retried ALONE under an analysis of its own (counted in n_retried_outputs and
+ *   n_analyses); if it fails again it carries that status and reads NaN, the others stay readable.  Returns PE_HIP_OK or the first failing
+ *   output's status.
+ *   Determinism.  No floating-point atomics; the rss sum is formed on the device in an order that depends on n_params only.  Results do not
+ *   depend on P, the batch or the pass an output fell into.
+ *   The main engine is read and never written.  The call has state of its own (adjoint system, engines, buffers): a stored AC sweep, noise
+ *   result and DC sweep read the same bits before and after.  The calls that make the stored noise result unreadable make this one
+ *   unreadable too (PE_HIP_ERR_ARG, "no sensitivity analysis yet").
+ *   PE_HIP_ERR_ARG, engine unchanged: no circuit, n_outputs < 1, c or its row arrays NULL, a row out of range, equal rows, a non-finite
+ *   weight, a circuit with a host-stamp overlay.  There is no twin on the multi-device pe_hip_sweep_* handle. */
+typedef struct pe_hip_sens_control {
+    int n_outputs;
+    const int* out_pos;       /* [n_outputs] rows of x; -1: ground */
+    const int* out_neg;
+    int normalized;           /* 1: p_k d out / d p_k */
+    int keep_sensitivities;   /* 1: keep s: n_outputs x batch x n_params doubles, device and host */
+    const double* weight;     /* NULL, or [n_params] */
+} pe_hip_sens_control;
+typedef struct pe_hip_sens_stats {
+    int n_outputs;            /* as passed */
+    int n_params;             /* parameters of the circuit */
+    int n_passes;             /* batched factor+solve passes, retries included */
+    int outputs_per_pass;     /* largest number of outputs put into one pass */
+    int n_analyses;           /* symbolic analyses: one + one per retried output */
+    int n_refine_rounds;      /* correction solves, summed over passes */
+    int n_retried_outputs;    /* outputs that failed in their pass and were solved again alone */
+    double gpu_ms;            /* HIP-event time of the passes */
+} pe_hip_sens_stats;
+/* the parameter table of the resident circuit (no analysis needed): kind (pe_hip_kind), index of the device in its table, raw column;
+ * *n_params receives the count, at most `capacity` entries are written; any pointer may be NULL */
+int pe_hip_get_sens_params(pe_hip_engine* h, int capacity, int* kind, int* index, int* column, int* n_params);
+int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* c, int* output_status, pe_hip_sens_stats* stats);
+/* results of the last call: s NULL or [n_outputs][count][n_params] (needs keep_sensitivities); rss NULL or [n_outputs][count] (needs
+ * weights); a failed output reads NaN */
+int pe_hip_get_sens(pe_hip_engine* h, int first_output, int n_outputs, int first_instance, int count, double* s, double* rss);
 
 /* x = [node voltages ; branch currents], instance-major [count][rows] */
 int pe_hip_get_solution(pe_hip_engine* h, int first_instance, int count, double* x);

@@ -206,6 +206,7 @@ namespace pe
                     return false;
                 }
                 if(t.kind >= PE_HIP_NMOS && t.kind <= PE_HIP_BJT_PNP && t.count > 0) hc.n3_tables.push_back(t.kind);
+                if(t.count > 0) hc.gen_tables.push_back(t.kind);
                 for(int i = 0; i < t.count; ++i)
                 {
                     bool connected = true;

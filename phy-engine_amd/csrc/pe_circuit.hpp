@@ -68,6 +68,7 @@ namespace pe
         std::vector<int> n3_kind, n3_n, n3_dv;
         std::vector<double> n3_par;    // [batch][nN3][3]
         std::vector<int> n3_tables;    // kinds of the three-pin tables in the order the caller passed them (the order n3 is filled in)
+        std::vector<int> gen_tables;   // kinds of all generic tables (PE_HIP_IAC ..) in the order the caller passed them
         int nN3() const { return static_cast<int>(n3_kind.size()); }
         int nTs() const { return static_cast<int>(ts_kind.size()); }
         int nCl() const { return static_cast<int>(cl_dv.size()); }

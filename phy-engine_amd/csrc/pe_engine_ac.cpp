@@ -1,7 +1,8 @@
 // pe_engine_ac.cpp -- small-signal AC on the device: pe_hip_analyze_ac / pe_hip_get_solution_ac (the real-equivalent system of pe_ac.hpp
 // solved by a second engine, iterative refinement on the device) and pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep (a whole frequency
 // sweep as batches of that system on a third engine, pe_ac_sweep.hpp), and pe_hip_analyze_noise / pe_hip_get_noise* (the same sweep body
-// on the adjoint system, pe_noise.hpp).
+// on the adjoint system, pe_noise.hpp), and pe_hip_analyze_sens / pe_hip_get_sens* (the same body on the adjoint system at omega = 0, one
+// point per output, pe_sens.hpp).
 #include "pe_engine_internal.hpp"
 
 #include <functional>
@@ -113,6 +114,16 @@ namespace pe_eng
         Z.pass_pool.release();
         Z.res_pool.release();
         Z = pe_hip_engine::Noise{};
+        // the sensitivity analysis likewise
+        auto& Y = h->sens;
+        sweep_engine_drop(Y.sys.sweep);
+        if(Y.sys.eng) pe_hip_destroy(Y.sys.eng);
+        Y.sys.sweep.circ_pool.release();
+        Y.tab_pool.release();
+        Y.out_pool.release();
+        Y.pass_pool.release();
+        Y.res_pool.release();
+        Y = pe_hip_engine::Sens{};
     }
 }  // namespace pe_eng
 
@@ -295,6 +306,8 @@ namespace
         std::function<int(std::vector<char>& failed)> collect;  // after the passes: the one device-to-host copy; marks the points that are not finite
         std::function<int(int i)> single;                       // forward sweep: failed point i on the single-point path (sets its status)
         std::function<int(int i, bool& finite)> reread;         // noise (no `single`): point i was retried alone in a pass of its own -- read it back
+        std::function<int(pe_hip_engine* E)> after_fill;        // sensitivity only (else empty): the value vectors of a pass stand -- its own right-hand sides
+        char const* pass_knob = "AC_SWEEP_POINTS";              // the knob that sets the points per pass
     };
 
     // The body of a frequency sweep on the real-equivalent system A (forward: h->ac, adjoint: h->noise.sys): base vectors, bands,
@@ -394,7 +407,7 @@ namespace
         };
 
         // ---- points per pass: the knob, else what fits the memory budget; never more than the largest band needs
-        int const knob_p = knob(h, "AC_SWEEP_POINTS", 0);
+        int const knob_p = knob(h, K.pass_knob, 0);
         long long cap = knob_p > 0 ? knob_p : 0;
         if(cap == 0)
         {
@@ -478,6 +491,8 @@ namespace
             HIPCHK(h, hipEventRecord(h->ev0, es));
             W.b0_valid = false;
             HIPCHK(h, pe::launch_ac_sweep_fill(es, E->V, W.V));
+            if(K.after_fill)
+                if(int const rc = K.after_fill(E); rc != PE_HIP_OK) return rc;
             if(int const rc = solve(); rc != PE_HIP_OK) return rc;
             HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
             W.b0_valid = true;
@@ -715,9 +730,9 @@ int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
 int pe_hip_get_matrix_ac(pe_hip_engine* h, int which, int instance, int nnz_capacity, int* row_ptr, int* col_ind, double* vals, double* rhs, int* n_rows,
                          int* nnz)
 {
-    if(!h || !h->loaded || which < 0 || which > 3 || nnz_capacity < 0) return PE_HIP_ERR_ARG;
-    auto& A = which < 2 ? h->ac : h->noise.sys;
-    bool const batched = (which & 1) != 0;
+    if(!h || !h->loaded || which < 0 || which > 4 || nnz_capacity < 0) return PE_HIP_ERR_ARG;
+    auto& A = which < 2 ? h->ac : which < 4 ? h->noise.sys : h->sens.sys;
+    bool const batched = (which & 1) != 0 || which == 4;
     pe_hip_engine* const E = batched ? A.sweep.eng : A.eng;
     if(!A.built || !E || !E->loaded) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: that engine does not exist yet");
     int const R2 = E->hc.rows, nz = static_cast<int>(E->hc.ci.size());
@@ -1101,6 +1116,334 @@ int pe_hip_get_noise_integrated(pe_hip_engine* h, int first_instance, int count,
 
 }  // extern "C"
 
+namespace
+{
+    static_assert(pe::SENS_DIODE_NRAW == PE_HIP_DIODE_NPARAM && pe::SENS_KIND_NMOS == PE_HIP_NMOS && pe::SENS_KIND_BJT_NPN == PE_HIP_BJT_NPN,
+                  "pe_sens.hpp names these without including the C header");
+
+    // the parameter table of the resident circuit in the definition order of include/pe_hip.h, and the stamps of every value slot (host only)
+    void sens_table_build(pe_hip_engine* h)
+    {
+        auto& Y = h->sens;
+        if(Y.table_built) return;
+        auto const& hc = h->hc;
+        Y.par.clear();
+        Y.kind.clear();
+        Y.index.clear();
+        Y.column.clear();
+        auto add = [&](int type, int idx, int col, int aux, int kind, int index)
+        {
+            Y.par.push_back({type, idx, col, aux});
+            Y.kind.push_back(kind);
+            Y.index.push_back(index);
+            Y.column.push_back(col);
+        };
+        auto two_pin = [&](std::vector<int> const& map, int kind, int type, int dv0)
+        {
+            for(size_t i = 0; i < map.size(); ++i)
+            {
+                if(map[i] < 0) add(pe::SENS_NONE, 0, 0, 0, kind, static_cast<int>(i));
+                else
+                    add(type, map[i], 0, dv0 + map[i], kind, static_cast<int>(i));
+            }
+        };
+        two_pin(hc.map_r, PE_HIP_R, pe::SENS_R, hc.dv_r);
+        two_pin(hc.map_vdc, PE_HIP_VDC, pe::SENS_UNIT, hc.dv_vdc);
+        two_pin(hc.map_idc, PE_HIP_IDC, pe::SENS_UNIT, hc.dv_idc);
+        static constexpr int diode_cols[] = {0, 1, 2, 3, 4, 5, 6, 8};
+        for(size_t i = 0; i < hc.map_d.size(); ++i)
+            for(int const col : diode_cols)
+            {
+                int const c = hc.map_d[i];
+                if(c < 0) add(pe::SENS_NONE, 0, col, 0, PE_HIP_DIODE, static_cast<int>(i));
+                else
+                    add(pe::SENS_DIODE, c, col, hc.dv_di + c, PE_HIP_DIODE, static_cast<int>(i));
+            }
+        for(int const kind : hc.gen_tables)
+        {
+            bool const mos = kind == PE_HIP_NMOS || kind == PE_HIP_PMOS, bjt = kind == PE_HIP_BJT_NPN || kind == PE_HIP_BJT_PNP;
+            bool const unit = kind == PE_HIP_VCCS || kind == PE_HIP_VCVS || kind == PE_HIP_CCCS || kind == PE_HIP_CCVS || kind == PE_HIP_OPAMP || kind == PE_HIP_XFMR;
+            if(!mos && !bjt && !unit && kind != PE_HIP_XFMR_CT) continue;
+            int const ncol = mos ? 3 : bjt ? 5 : 1;
+            auto const& map = hc.map_gen[static_cast<size_t>(kind)];
+            for(size_t p = 0; p < map.size(); ++p)
+                for(int col = 0; col < ncol; ++col)
+                {
+                    int const index = static_cast<int>(p);
+                    if(map[p] < 0)
+                    {
+                        add(pe::SENS_NONE, 0, col, 0, kind, index);
+                        continue;
+                    }
+                    auto const& d = hc.gen[static_cast<size_t>(map[p])];
+                    if(mos) add(pe::SENS_MOS, d.aux, col, 0, kind, index);
+                    else if(bjt)
+                        add(pe::SENS_BJT, d.aux, col, d.par, kind, index);
+                    else
+                        add(unit ? pe::SENS_UNIT : pe::SENS_XCT, 0, col, d.dv, kind, index);
+                }
+        }
+        // the contribution lists by value slot, in list order: A entries (row of the CSR slot, its column), then right-hand-side entries
+        std::vector<int> cnt(static_cast<size_t>(hc.dv_len) + 1, 0);
+        for(int const e : hc.a_src) ++cnt[static_cast<size_t>(e >> 1) + 1];
+        for(int const e : hc.b_src) ++cnt[static_cast<size_t>(e >> 1) + 1];
+        for(int j = 0; j < hc.dv_len; ++j) cnt[static_cast<size_t>(j) + 1] += cnt[static_cast<size_t>(j)];
+        Y.sl_ptr = cnt;
+        Y.sl_ent.assign(static_cast<size_t>(cnt[static_cast<size_t>(hc.dv_len)]), pe::SensEnt{0, -1});
+        std::vector<int> cur(cnt.begin(), cnt.end() - 1);
+        for(int r = 0; r < hc.rows; ++r)
+            for(int sl = hc.rp[r]; sl < hc.rp[r + 1]; ++sl)
+                for(int e = hc.a_ptr[sl]; e < hc.a_ptr[sl + 1]; ++e) Y.sl_ent[static_cast<size_t>(cur[static_cast<size_t>(hc.a_src[e] >> 1)]++)] = {(r << 1) | (hc.a_src[e] & 1), hc.ci[sl]};
+        for(int r = 0; r < hc.rows; ++r)
+            for(int e = hc.b_ptr[r]; e < hc.b_ptr[r + 1]; ++e) Y.sl_ent[static_cast<size_t>(cur[static_cast<size_t>(hc.b_src[e] >> 1)]++)] = {(r << 1) | (hc.b_src[e] & 1), -1};
+        Y.table_built = true;
+        Y.table_on_device = false;
+    }
+}  // namespace
+
+extern "C" {
+
+int pe_hip_get_sens_params(pe_hip_engine* h, int capacity, int* kind, int* index, int* column, int* n_params)
+{
+    if(!h || !h->loaded || capacity < 0) return PE_HIP_ERR_ARG;
+    sens_table_build(h);
+    auto const& Y = h->sens;
+    int const n = static_cast<int>(Y.par.size());
+    if(n_params) *n_params = n;
+    for(int k = 0; k < std::min(n, capacity); ++k)
+    {
+        if(kind) kind[k] = Y.kind[static_cast<size_t>(k)];
+        if(index) index[k] = Y.index[static_cast<size_t>(k)];
+        if(column) column[k] = Y.column[static_cast<size_t>(k)];
+    }
+    return PE_HIP_OK;
+}
+
+/* DC sensitivities by the adjoint method: one solve of the transposed small-signal system at omega = 0 per output -- the sweep body of
+ * pe_hip_analyze_ac_sweep on the adjoint system with state of its own (h->sens), every slot of a pass with the selector of its own output
+ * (k_sens_rhs) --, then d f / d p against the adjoint solution and the weighted sum of squares on the device (k_sens_accumulate).
+ * Definitions: include/pe_hip.h. */
+int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* ctl, int* output_status, pe_hip_sens_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(!ctl || ctl->n_outputs < 1 || !ctl->out_pos || !ctl->out_neg) return fail(h, PE_HIP_ERR_ARG, "analyze_sens: no control, n_outputs < 1 or no output rows");
+    auto& hc = h->hc;
+    int const B = hc.batch, N = hc.rows, n_out = ctl->n_outputs;
+    for(int o = 0; o < n_out; ++o)
+    {
+        int const pos = ctl->out_pos[o], neg = ctl->out_neg[o];
+        if(pos < -1 || pos >= N || neg < -1 || neg >= N) return fail(h, PE_HIP_ERR_ARG, "analyze_sens: output row out of range");
+        if(pos == neg) return fail(h, PE_HIP_ERR_ARG, "analyze_sens: an output needs two different rows (-1: ground)");
+    }
+    if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_sens: host-stamped overlay models have no parameter description");
+    sens_table_build(h);
+    auto& Y = h->sens;
+    int const n_par = static_cast<int>(Y.par.size());
+    bool const keep = ctl->keep_sensitivities != 0, weighted = ctl->weight != nullptr;
+    if(!keep && !weighted) return fail(h, PE_HIP_ERR_ARG, "analyze_sens: neither sensitivities nor a weighted sum asked for");
+    for(int k = 0; weighted && k < n_par; ++k)
+        if(!std::isfinite(ctl->weight[k])) return fail(h, PE_HIP_ERR_ARG, "analyze_sens: non-finite weight");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto& A = Y.sys;
+    auto& W = A.sweep;
+    Y.valid = false;
+    size_t const n_rss = weighted ? static_cast<size_t>(n_out) * B : 0;
+    size_t const total = n_rss + (keep ? static_cast<size_t>(n_out) * B * n_par : 0);
+    auto publish = [&](std::vector<int> const* pst, pe_hip_ac_sweep_stats const& S)
+    {
+        Y.n_outputs = n_out;
+        Y.batch = B;
+        Y.kept = keep;
+        Y.weighted = weighted;
+        Y.valid = true;
+        if(output_status && pst) std::copy(pst->begin(), pst->end(), output_status);
+        if(stats)
+        {
+            stats->n_outputs = n_out;
+            stats->n_params = n_par;
+            stats->n_passes = S.n_passes;
+            stats->outputs_per_pass = S.points_per_pass;
+            stats->n_analyses = S.n_analyses;
+            stats->n_refine_rounds = S.n_refine_rounds;
+            stats->n_retried_outputs = S.n_fallback_points;
+            stats->gpu_ms = S.gpu_ms;
+        }
+    };
+
+    // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
+    {
+        std::vector<int> inst(static_cast<size_t>(B), 0);
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+        for(int b = 0; b < B; ++b)
+        {
+            if(inst[static_cast<size_t>(b)] == PE_HIP_OK) continue;
+            Y.res.assign(total, std::nan(""));
+            std::vector<int> const pst(static_cast<size_t>(n_out), inst[static_cast<size_t>(b)]);
+            publish(&pst, pe_hip_ac_sweep_stats{});
+            return fail(h, inst[static_cast<size_t>(b)], "analyze_sens: instance " + std::to_string(b) + " has no operating point (its last analysis failed)");
+        }
+    }
+    Y.res.assign(total, std::nan(""));
+    pe_hip_ac_sweep_stats S{};
+    std::vector<int> pst(static_cast<size_t>(n_out), PE_HIP_OK);
+    if(N == 0)
+    {
+        publish(&pst, S);
+        return PE_HIP_OK;
+    }
+
+    // ---- the adjoint system (its right-hand-side lists hold the first output's selector; every pass writes its own: k_sens_rhs)
+    if(!A.built)
+    {
+        pe::AcAdjoint const adj{ctl->out_pos[0], ctl->out_neg[0]};
+        if(int const rc = ensure_ac_built(h, A, &adj); rc != PE_HIP_OK) return rc;
+    }
+
+    // ---- per circuit: parameter table and stamp lists; per call: raw columns, weights, output rows
+    if(!Y.table_on_device)
+    {
+        Y.tab_pool.release();
+        Y.d_draw = Y.d_graw = Y.d_weight = nullptr;
+        HIPCHK(h, Y.tab_pool.upload(Y.V.par, Y.par));
+        HIPCHK(h, Y.tab_pool.upload(Y.V.sl_ptr, Y.sl_ptr));
+        HIPCHK(h, Y.tab_pool.upload(Y.V.sl_ent, Y.sl_ent));
+        HIPCHK(h, Y.tab_pool.alloc(Y.d_draw, hc.d_raw.size(), false));
+        HIPCHK(h, Y.tab_pool.alloc(Y.d_graw, hc.gen_par.size(), false));
+        HIPCHK(h, Y.tab_pool.alloc(Y.d_weight, static_cast<size_t>(n_par), false));
+        Y.table_on_device = true;
+    }
+    if(!hc.d_raw.empty()) HIPCHK(h, hipMemcpy(Y.d_draw, hc.d_raw.data(), hc.d_raw.size() * sizeof(double), hipMemcpyHostToDevice));
+    if(!hc.gen_par.empty()) HIPCHK(h, hipMemcpy(Y.d_graw, hc.gen_par.data(), hc.gen_par.size() * sizeof(double), hipMemcpyHostToDevice));
+    if(weighted && n_par > 0) HIPCHK(h, hipMemcpy(Y.d_weight, ctl->weight, static_cast<size_t>(n_par) * sizeof(double), hipMemcpyHostToDevice));
+    if(Y.out_len < static_cast<size_t>(n_out))
+    {
+        Y.out_pool.release();
+        Y.out_len = 0;
+        HIPCHK(h, Y.out_pool.alloc(Y.d_out_pos, static_cast<size_t>(n_out), false));
+        HIPCHK(h, Y.out_pool.alloc(Y.d_out_neg, static_cast<size_t>(n_out), false));
+        Y.out_len = static_cast<size_t>(n_out);
+    }
+    HIPCHK(h, hipMemcpy(Y.d_out_pos, ctl->out_pos, static_cast<size_t>(n_out) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(Y.d_out_neg, ctl->out_neg, static_cast<size_t>(n_out) * sizeof(int), hipMemcpyHostToDevice));
+    Y.V.n_par = n_par;
+    Y.V.n_chunks = std::max(1, (n_par + pe::SENS_CHUNK - 1) / pe::SENS_CHUNK);
+    Y.V.n_inst = B;
+    Y.V.n_half = N;
+    Y.V.gen_par_len = hc.gen_par_len;
+    Y.V.normalized = ctl->normalized != 0 ? 1 : 0;
+    Y.V.rhs0 = A.rhs0;
+    Y.V.d_raw = Y.d_draw;
+    Y.V.g_raw = Y.d_graw;
+    Y.V.weight = weighted ? Y.d_weight : nullptr;
+    Y.V.out_pos = Y.d_out_pos;
+    Y.V.out_neg = Y.d_out_neg;
+
+    std::vector<double> const omegas(static_cast<size_t>(n_out), 0.0);  // every output is a point at omega = 0: one band, one analysis
+    SweepHooks hooks;
+    hooks.name = "analyze_sens";
+    hooks.pass_knob = "SENS_OUTPUTS";
+    hooks.prepare = [&](int P) -> int
+    {
+        if(Y.res_len != total || !Y.d_res)
+        {
+            Y.res_pool.release();
+            Y.d_res = nullptr;
+            Y.res_len = 0;
+            HIPCHK(h, Y.res_pool.alloc(Y.d_res, total, false));
+            Y.res_len = total;
+        }
+        HIPCHK(h, hipMemset(Y.d_res, 0xff, total * sizeof(double)));  // (all ones: a NaN -- an output no pass wrote reads NaN)
+        size_t const need = static_cast<size_t>(B) * P * Y.V.n_chunks;
+        if(Y.partial_len != need || !Y.V.partial)
+        {
+            Y.pass_pool.release();
+            Y.V.partial = nullptr;
+            Y.partial_len = 0;
+            HIPCHK(h, Y.pass_pool.alloc(Y.V.partial, need));
+            Y.partial_len = need;
+        }
+        Y.V.P = P;
+        Y.V.xacc = W.V.xacc;
+        Y.V.point = W.V.point;
+        Y.V.rss = weighted ? Y.d_res : nullptr;
+        Y.V.s = keep ? Y.d_res + n_rss : nullptr;
+        return PE_HIP_OK;
+    };
+    hooks.after_fill = [&](pe_hip_engine* E) -> int
+    {
+        HIPCHK(h, pe::launch_sens_rhs(E->stream, E->V, Y.V));
+        return PE_HIP_OK;
+    };
+    hooks.epilogue = [&](pe_hip_engine* E) -> int
+    {
+        HIPCHK(h, pe::launch_sens_accumulate(E->stream, E->V, h->V, Y.V));
+        return PE_HIP_OK;
+    };
+    // what belongs to output i in the result buffer: its rss row, its block of sensitivities
+    auto finite_output = [&](int i)
+    {
+        size_t const o = static_cast<size_t>(i) * B;
+        for(size_t k = 0; weighted && k < static_cast<size_t>(B); ++k)
+            if(!std::isfinite(Y.res[o + k])) return false;
+        for(size_t k = 0; keep && k < static_cast<size_t>(B) * n_par; ++k)
+            if(!std::isfinite(Y.res[n_rss + o * n_par + k])) return false;
+        return true;
+    };
+    hooks.collect = [&](std::vector<char>& failed) -> int
+    {
+        if(total > 0) HIPCHK(h, hipMemcpy(Y.res.data(), Y.d_res, total * sizeof(double), hipMemcpyDeviceToHost));
+        for(int i = 0; i < n_out; ++i)
+            if(!failed[i] && !finite_output(i)) failed[i] = 1;
+        return PE_HIP_OK;
+    };
+    hooks.reread = [&](int i, bool& finite) -> int
+    {
+        size_t const o = static_cast<size_t>(i) * B;
+        if(weighted) HIPCHK(h, hipMemcpy(&Y.res[o], Y.d_res + o, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
+        if(keep && n_par > 0)
+            HIPCHK(h, hipMemcpy(&Y.res[n_rss + o * n_par], Y.d_res + n_rss + o * n_par, static_cast<size_t>(B) * n_par * sizeof(double), hipMemcpyDeviceToHost));
+        finite = finite_output(i);
+        return PE_HIP_OK;
+    };
+    if(int const rc = sweep_body(h, A, n_out, omegas.data(), pst, S, hooks); rc != PE_HIP_OK) return rc;
+
+    // a failed output reads NaN
+    for(int i = 0; i < n_out; ++i)
+    {
+        if(pst[i] == PE_HIP_OK) continue;
+        size_t const o = static_cast<size_t>(i) * B;
+        if(weighted) std::fill(Y.res.begin() + o, Y.res.begin() + o + B, std::nan(""));
+        if(keep) std::fill(Y.res.begin() + n_rss + o * n_par, Y.res.begin() + n_rss + (o + B) * n_par, std::nan(""));
+    }
+    publish(&pst, S);
+    for(int i = 0; i < n_out; ++i)
+        if(pst[i] != PE_HIP_OK) return fail(h, pst[i], "analyze_sens: output " + std::to_string(i) + " failed");
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_sens(pe_hip_engine* h, int first_output, int n_outputs, int first_instance, int count, double* s, double* rss)
+{
+    if(!h || !h->loaded || (!s && !rss)) return PE_HIP_ERR_ARG;
+    auto const& Y = h->sens;
+    if(!Y.valid || Y.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_sens: no sensitivity analysis yet");
+    if(first_output < 0 || n_outputs < 0 || first_output > Y.n_outputs - n_outputs || first_instance < 0 || count < 0 || first_instance > Y.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_sens: outputs or instances out of range");
+    if(s && !Y.kept) return fail(h, PE_HIP_ERR_ARG, "get_sens: the sensitivities were not kept (pe_hip_sens_control.keep_sensitivities)");
+    if(rss && !Y.weighted) return fail(h, PE_HIP_ERR_ARG, "get_sens: no weighted sum was formed (pe_hip_sens_control.weight)");
+    size_t const n_par = Y.par.size(), n_rss = Y.weighted ? static_cast<size_t>(Y.n_outputs) * Y.batch : 0;
+    for(int i = 0; i < n_outputs && count > 0; ++i)
+    {
+        size_t const src = static_cast<size_t>(first_output + i) * Y.batch + first_instance, dst = static_cast<size_t>(i) * count;
+        if(rss) std::memcpy(rss + dst, &Y.res[src], static_cast<size_t>(count) * sizeof(double));
+        if(s && n_par > 0) std::memcpy(s + dst * n_par, &Y.res[n_rss + src * n_par], static_cast<size_t>(count) * n_par * sizeof(double));
+    }
+    return PE_HIP_OK;
+}
+
+}  // extern "C"
+
 #if !defined(__HIPCC__)
 // Builds without HIP (the emulation library of tests/emu): the sweep's launchers as serial loops over the instances, with a one-thread
 // team running the text of pe_ac_sweep.hpp
@@ -1157,6 +1500,29 @@ namespace pe
                     *dst = sum;
             }
             if(Z.n_chunks > 1) noise_finish(Z, q);
+        }
+        return hipSuccess;
+    }
+    // ... and the sensitivity launchers with the text of pe_sens.hpp
+    hipError_t launch_sens_rhs(hipStream_t, DevView const& V, SensView const& Z)
+    {
+        for(int q = 0; q < V.batch; ++q) sens_rhs(SweepHostTeam{}, V, Z, q);
+        return hipSuccess;
+    }
+    hipError_t launch_sens_accumulate(hipStream_t, DevView const& V, DevView const& M, SensView const& Z)
+    {
+        if(!Z.s && !Z.weight) return hipSuccess;
+        for(int q = 0; q < V.batch; ++q)
+        {
+            for(int c = 0; c < Z.n_chunks; ++c)
+            {
+                double const sum = sens_accumulate_chunk(SweepHostTeam{}, M, Z, V.rows, q, c);
+                if(!Z.weight) continue;
+                if(Z.n_chunks > 1) Z.partial[static_cast<long long>(q) * Z.n_chunks + c] = sum;
+                else if(double* dst = sens_slot_rss(Z, q))
+                    *dst = sum;
+            }
+            if(Z.weight && Z.n_chunks > 1) sens_finish(Z, q);
         }
         return hipSuccess;
     }

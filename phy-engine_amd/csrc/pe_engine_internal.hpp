@@ -31,6 +31,7 @@
 #include "pe_kernels.hpp"
 #include "pe_lte.hpp"
 #include "pe_noise.hpp"
+#include "pe_sens.hpp"
 #include "pe_symbolic.hpp"
 
 #include <map>
@@ -239,6 +240,33 @@ struct pe_hip_engine
         std::vector<double> res;          // [n_points][batch] densities, then [n_points][batch][n_src] contributions when kept
         std::vector<double> integrated;   // [batch]
     } noise;
+    // DC sensitivity analysis (pe_hip_analyze_sens, pe_sens.hpp): the adjoint system at omega = 0 with sweep state of its own, like the noise
+    // analysis -- the outputs of a call are the points of its passes --, the parameter table and the by-slot stamp lists of the circuit,
+    // the raw columns of the last call and its result
+    struct Sens
+    {
+        Ac sys;
+        bool table_built{}, table_on_device{};
+        std::vector<pe::SensParam> par;   // definition order of include/pe_hip.h
+        std::vector<int> kind, index, column;
+        std::vector<int> sl_ptr;          // stamps of every value slot of the main engine (pe_sens.hpp)
+        std::vector<pe::SensEnt> sl_ent;
+        Pool tab_pool;                    // sized by the circuit: parameter table, stamp lists, raw columns, weights
+        Pool out_pool;                    // sized by n_outputs: the output rows
+        size_t out_len{};
+        int *d_out_pos{}, *d_out_neg{};
+        double *d_draw{}, *d_graw{}, *d_weight{};
+        Pool pass_pool;                   // sized by batch x P x chunks: chunk sums
+        size_t partial_len{};
+        Pool res_pool;                    // sized by the call: [rss | sensitivities]
+        size_t res_len{};
+        double* d_res{};
+        pe::SensView V{};
+        bool valid{};                     // `res` belongs to the current circuit at its current operating point
+        bool kept{}, weighted{};
+        int n_outputs{}, batch{};
+        std::vector<double> res;          // [n_outputs][batch] rss (weighted), then [n_outputs][batch][n_par] sensitivities (kept)
+    } sens;
     // DC sweep (pe_hip_analyze_dc_sweep, pe_dc_sweep.hpp): an engine of its own holding this circuit with batch (circuit batch) x P -- the
     // points of one pass are extra instances --, the buffers of its kernels and the stored result.  The main engine is only read.
     struct DcSweep
@@ -355,11 +383,12 @@ namespace pe_eng PE_ENG_HIDDEN
     // pe_engine_newton.cpp: variable-step transient
     void tr_adaptive_drop(pe_hip_engine* h);  // shadow state, history ring and step log gone (pe_hip_load_circuit)
     // pe_engine_ac.cpp: the stored AC sweep
-    void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy); the noise state too
-    inline void ac_sweep_invalidate(pe_hip_engine* h)  // whatever moves the operating point or the circuit: the stored sweep and the stored noise result
+    void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy); the noise and sensitivity state too
+    inline void ac_sweep_invalidate(pe_hip_engine* h)  // whatever moves the operating point or the circuit: the stored sweep, the stored noise and sensitivity results
     {
         h->ac.sweep.valid = false;
         h->noise.valid = false;
+        h->sens.valid = false;
     }
     // budget of a sweep engine's automatic pass size, and the most instances one engine takes (the y extent of a launch grid)
     long long sweep_memory_budget();

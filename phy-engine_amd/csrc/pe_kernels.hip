@@ -26,6 +26,7 @@
 #include "pe_ac_sweep.hpp"
 #include "pe_dc_sweep.hpp"
 #include "pe_noise.hpp"
+#include "pe_sens.hpp"
 #include "pe_lte.hpp"
 #include "pe_kernels.hpp"
 #include "pe_quad.hpp"
@@ -1783,6 +1784,60 @@ namespace pe
         // (a circuit without sources still writes its zero densities: one chunk)
         hipLaunchKernelGGL(k_noise_accumulate, dim3(Z.n_chunks, V.batch), dim3(NOISE_THREADS), 0, st, Z, V.rows);
         if(Z.n_chunks > 1) hipLaunchKernelGGL(k_noise_finish, dim3((V.batch + 255) / 256), dim3(256), 0, st, Z, V.batch);
+        return hipGetLastError();
+    }
+
+    // ---- DC sensitivity analysis (pe_sens.hpp, pe_engine_ac.cpp pe_hip_analyze_sens)
+    // right-hand side of adjoint-engine instance blockIdx.y: the selector of its slot's own output (after k_ac_sweep_fill, before the solve)
+    __global__ void __launch_bounds__(256) k_sens_rhs(DevView V, SensView Z)
+    {
+        sens_rhs(GridTeam{}, V, Z, static_cast<int>(blockIdx.y));
+    }
+    struct SensBlockTeam  // one workgroup owns one chunk of parameters of one instance
+    {
+        __device__ __forceinline__ int tid() const { return static_cast<int>(threadIdx.x); }
+        __device__ __forceinline__ int size() const { return SENS_THREADS; }
+    };
+    // adjoint-engine instance blockIdx.y, parameter chunk blockIdx.x: the sensitivities + the sum of their weighted squares, reduced by the
+    // scheme of k_noise_accumulate (a fixed strided subsequence per thread in ascending order, a fixed __shfl_down tree over the 64 lanes,
+    // the four wavefronts through LDS in wavefront order, one lane stores).  No floating-point atomics; nothing depends on P, the batch or
+    // the pass.  M: the main engine's view (operating point), read only.
+    __global__ void __launch_bounds__(SENS_THREADS) k_sens_accumulate(DevView M, SensView Z, int rows2)
+    {
+        __shared__ double wave_sum[SENS_THREADS / 64];
+        int const q = static_cast<int>(blockIdx.y), c = static_cast<int>(blockIdx.x);
+        double acc = sens_accumulate_chunk(SensBlockTeam{}, M, Z, rows2, q, c);
+        if(!Z.weight) return;  // (uniform: no sum is formed)
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+        if((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if(threadIdx.x != 0) return;
+        double total = wave_sum[0];
+#pragma unroll
+        for(int w = 1; w < SENS_THREADS / 64; ++w) total += wave_sum[w];
+        if(Z.n_chunks > 1)
+            Z.partial[static_cast<long long>(q) * Z.n_chunks + c] = total;
+        else if(double* dst = sens_slot_rss(Z, q))
+            *dst = total;
+    }
+    // second stage of a circuit with more than one chunk: one thread per instance adds its chunk sums in ascending order
+    __global__ void __launch_bounds__(256) k_sens_finish(SensView Z, int n)
+    {
+        int const q = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+        if(q < n) sens_finish(Z, q);
+    }
+    hipError_t launch_sens_rhs(hipStream_t st, DevView const& V, SensView const& Z)
+    {
+        if(V.batch <= 0 || V.rows <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_sens_rhs, dim3(sweep_grid(V.rows), V.batch), dim3(256), 0, st, V, Z);
+        return hipGetLastError();
+    }
+    hipError_t launch_sens_accumulate(hipStream_t st, DevView const& V, DevView const& M, SensView const& Z)
+    {
+        if(V.batch <= 0 || (!Z.s && !Z.weight)) return hipSuccess;
+        hipLaunchKernelGGL(k_sens_accumulate, dim3(Z.n_chunks, V.batch), dim3(SENS_THREADS), 0, st, M, Z, V.rows);
+        if(Z.weight && Z.n_chunks > 1) hipLaunchKernelGGL(k_sens_finish, dim3((V.batch + 255) / 256), dim3(256), 0, st, Z, V.batch);
         return hipGetLastError();
     }
 

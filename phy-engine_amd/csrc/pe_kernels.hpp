@@ -77,6 +77,14 @@ namespace pe
     struct NoiseView;
     hipError_t launch_noise_sources(hipStream_t st, DevView const& V, NoiseView const& Z);
     hipError_t launch_noise_accumulate(hipStream_t st, DevView const& V, NoiseView const& Z);
+    // DC sensitivity analysis (pe_sens.hpp).  rhs: V is the view of the adjoint sweep engine after launch_ac_sweep_fill -- the right-hand-side
+    // slots of instance b * Z.P + p become the selector of output Z.point[p] (zero for an unused slot).  accumulate: V is that view after
+    // refinement, M the MAIN engine's view (operating point, read only) -- for every instance with Z.point[p] >= 0 the sensitivities of its
+    // output to every parameter (into Z.s when kept) and, with weights, the sum of their weighted squares into Z.rss, in a summation order
+    // that depends on Z.n_par only.  Builds without HIP: serial host definitions in pe_engine_ac.cpp.
+    struct SensView;
+    hipError_t launch_sens_rhs(hipStream_t st, DevView const& V, SensView const& Z);
+    hipError_t launch_sens_accumulate(hipStream_t st, DevView const& V, DevView const& M, SensView const& Z);
     // variable-step transient (pe_lte.hpp): lte: q of the candidate V.x against the history ring + failed / non-finite instances into
     // L.result (cleared first); history_push: V.x of every instance into ring slot `slot`; state_copy: every (dst, src, bytes) of the table
     // (snapshot and roll-back of a step).  Builds without HIP: serial host definitions in pe_engine_newton.cpp.

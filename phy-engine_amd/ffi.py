@@ -33,6 +33,7 @@ EXPORTS = [
     "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
     "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
+    "pe_hip_get_sens_params", "pe_hip_analyze_sens", "pe_hip_get_sens",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
     "pe_hip_get_static_fronts", "pe_hip_get_static_skip_stats", "pe_hip_get_static_skip_refinement_stats",
     "pe_hip_get_matrix_ac", "pe_hip_get_ac_pass_size", "pe_hip_get_ac_analysis_omega",
@@ -195,6 +196,19 @@ class NoiseStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SensControl(C.Structure):
+    _fields_ = [("n_outputs", C.c_int), ("out_pos", C.POINTER(C.c_int)), ("out_neg", C.POINTER(C.c_int)), ("normalized", C.c_int),
+                ("keep_sensitivities", C.c_int), ("weight", C.POINTER(C.c_double))]
+
+
+class SensStats(C.Structure):
+    _fields_ = [("n_outputs", C.c_int), ("n_params", C.c_int), ("n_passes", C.c_int), ("outputs_per_pass", C.c_int), ("n_analyses", C.c_int),
+                ("n_refine_rounds", C.c_int), ("n_retried_outputs", C.c_int), ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -251,6 +265,9 @@ def lib():
         l.pe_hip_get_noise_sources.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 6
         l.pe_hip_get_noise_source_density.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         l.pe_hip_get_noise_integrated.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        l.pe_hip_get_sens_params.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 4
+        l.pe_hip_analyze_sens.argtypes = [C.c_void_p, C.POINTER(SensControl), C.POINTER(C.c_int), C.POINTER(SensStats)]
+        l.pe_hip_get_sens.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.pe_hip_set_dc_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(DcSweepControl), C.POINTER(C.c_int), C.POINTER(DcSweepStats)]
         l.pe_hip_get_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -620,7 +637,7 @@ class Engine(_Probes):
     def matrix_ac(self, which=0, instance=0, rhs=True):
         """(row_ptr, col_ind, vals, rhs) of a small-signal system as the device last assembled it (pe_hip_get_matrix_ac): the 2N
         real-equivalent system of the single-point engine (which 0), of instance q = b * P + p of the sweep's last pass (1), of the noise
-        analysis' adjoint engines (2 / 3).  rhs: as stamped, or None with rhs=False."""
+        analysis' adjoint engines (2 / 3), of the batched adjoint engine of the last analyze_sens pass (4).  rhs: as stamped, or None with rhs=False."""
         n, nz = C.c_int(), C.c_int()
         self._chk(lib().pe_hip_get_matrix_ac(self._h, int(which), int(instance), 0, None, None, None, None, C.byref(n), C.byref(nz)))
         rp = np.empty(n.value + 1, dtype=np.int32)
@@ -723,6 +740,45 @@ class Engine(_Probes):
         v = np.zeros(self.batch)
         self._chk(lib().pe_hip_get_noise_integrated(self._h, 0, self.batch, _dp(v)))
         return v
+
+    def sens_params(self):
+        """the parameter table of the resident circuit (pe_hip_get_sens_params): dict of int arrays kind (pe_hip_kind), index (in its
+        table), column (raw column as update_param names it), in the order of the sensitivities"""
+        n = C.c_int()
+        self._chk(lib().pe_hip_get_sens_params(self._h, 0, None, None, None, C.byref(n)))
+        out = {k: np.zeros(n.value, dtype=np.int32) for k in ("kind", "index", "column")}
+        self._chk(lib().pe_hip_get_sens_params(self._h, n.value, *[_ip(out[k]) for k in ("kind", "index", "column")], C.byref(n)))
+        return out
+
+    def analyze_sens(self, out_pos, out_neg=None, normalized=False, weight=None, keep=True, check=True):
+        """First-order sensitivity of every output x[out_pos[o]] - x[out_neg[o]] (rows of x, -1 / None: ground) of the resident operating
+        point to every parameter of sens_params() by the adjoint method on the device (pe_hip_analyze_sens).  Returns
+        (s [n_outputs][batch][n_params] or None when not kept, rss [n_outputs][batch] = sum_k (weight_k s_k)^2 or None without weights,
+        status [n_outputs], stats dict with the return code under 'rc'); a failed output reads NaN."""
+        pos = np.ascontiguousarray(out_pos, dtype=np.int32).reshape(-1)
+        neg = np.full(len(pos), -1, dtype=np.int32) if out_neg is None else np.ascontiguousarray(out_neg, dtype=np.int32).reshape(-1)
+        if len(neg) != len(pos):
+            raise ValueError("out_pos and out_neg differ in length")
+        n = len(pos)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        n_par = C.c_int()
+        self._chk(lib().pe_hip_get_sens_params(self._h, 0, None, None, None, C.byref(n_par)))
+        if w is not None and len(w) != n_par.value:
+            raise ValueError("weight needs one entry per parameter")
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        st = SensStats()
+        ctl = SensControl(n, _ip(pos) if n else None, _ip(neg) if n else None, 1 if normalized else 0, 1 if keep else 0,
+                          _dp(w) if w is not None else None)
+        rc = lib().pe_hip_analyze_sens(self._h, C.byref(ctl), _ip(status), C.byref(st))
+        if check:
+            self._chk(rc)
+        s = np.full((n, self.batch, n_par.value), np.nan) if keep else None
+        rss = np.full((n, self.batch), np.nan) if w is not None else None
+        if rc not in (ERR_ARG, ERR_NO_DEVICE, ERR_INTERNAL) and n and (keep or w is not None):
+            self._chk(lib().pe_hip_get_sens(self._h, 0, n, 0, self.batch, _dp(s) if keep and n_par.value else None, _dp(rss) if rss is not None else None))
+        d = st.asdict()
+        d["rc"] = rc
+        return s, rss, status[:n], d
 
     def phase_clocks_coop(self, instance=0):
         """Per-layout breakdown of the cooperative fronts (see pe_hip_get_phase_clocks_ex), microseconds / counts."""

@@ -1394,6 +1394,44 @@ namespace phy_engine
             return rc == PE_HIP_OK || gpu_fail();
         }
 
+        // DC sensitivity analysis (pe_hip_analyze_sens, include/pe_hip.h): d (v(out_pos) - v(out_neg)) / d p for every device parameter p of
+        // the circuit (out_neg null: ground) at its operating point, which is prepared and solved first (OP).  sens_results receives one
+        // entry per parameter in the order of pe_hip_get_sens_params: the parameter's stable position -- kind (pe_hip_kind), index of the
+        // device among the models of that kind in netlist order, raw column as the model's gpu_table_define hook lists it -- and the value
+        // (normalized: p d out / d p); last_sens_stats the rest.
+        struct sens_entry
+        {
+            int kind{}, index{}, column{};
+            double value{};
+        };
+        ::std::vector<sens_entry> sens_results{};
+        pe_hip_sens_stats last_sens_stats{};
+        auto& get_sens_results() noexcept { return sens_results; }
+        [[nodiscard]] bool analyze_sens(::phy_engine::model::node_t const& out_pos, ::phy_engine::model::node_t const* out_neg, bool normalized = false) noexcept
+        {
+            sens_results.clear();
+            last_sens_stats = pe_hip_sens_stats{};
+            auto const saved = at;
+            at = analyze_type::OP;
+            bool ok = prepare();
+            if(ok) ok = solve();
+            at = saved;
+            if(!ok || !gpu_ || !loaded_) return false;
+            auto row = [&](::phy_engine::model::node_t const* n) { return (!n || n == &nl.ground_node) ? -1 : static_cast<int>(n->node_index); };
+            int const pos = row(&out_pos), neg = row(out_neg);
+            int n_params = 0;
+            if(pe_hip_get_sens_params(gpu_, 0, nullptr, nullptr, nullptr, &n_params) != PE_HIP_OK) return gpu_fail();
+            ::std::vector<int> kind(static_cast<::std::size_t>(n_params)), index(kind.size()), column(kind.size());
+            if(pe_hip_get_sens_params(gpu_, n_params, kind.data(), index.data(), column.data(), &n_params) != PE_HIP_OK) return gpu_fail();
+            pe_hip_sens_control const ctl{1, &pos, &neg, normalized ? 1 : 0, 1, nullptr};
+            int const rc = pe_hip_analyze_sens(gpu_, &ctl, nullptr, &last_sens_stats);
+            if(rc == PE_HIP_ERR_ARG || rc == PE_HIP_ERR_NO_DEVICE || rc == PE_HIP_ERR_INTERNAL) return gpu_fail();
+            ::std::vector<double> s(kind.size());
+            if(n_params > 0 && pe_hip_get_sens(gpu_, 0, 1, 0, 1, s.data(), nullptr) != PE_HIP_OK) return gpu_fail();
+            for(::std::size_t k = 0; k < kind.size(); ++k) sens_results.push_back({kind[k], index[k], column[k], s[k]});
+            return rc == PE_HIP_OK || gpu_fail();
+        }
+
         // one AC solve (solve_once with iterate_ac): phasors scattered into the nodes / branches as complex values
         bool solve_ac_point(double omega) noexcept
         {
