@@ -477,6 +477,75 @@ int pe_hip_get_dc_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
 int pe_hip_get_dc_sweep_status(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, int* status, int* newton_iters,
                                int* seed_point);
 
+/* ---- Operating point with gmin and source stepping: the continuation every simulator of this kind falls back on when the bare Newton
+ * iteration of pe_hip_analyze_dc does not converge.  The solves are those of pe_hip_analyze_dc, untouched; the controller around them
+ * lives on the device, one (phase, lambda, Delta) per instance, and the host reads one small record per level: no solution, no status array.
+ *   1. Direct attempt.  The first solve is exactly pe_hip_analyze_dc of that mode from the resident state.  An instance that converges there is
+ *   finished: its state is bit for bit what pe_hip_analyze_dc leaves.  Only failing instances step; failing = status not PE_HIP_OK, or a
+ *   solution that is not finite.  A batch in which nothing fails costs one extra small launch and one read-back.
+ *   2. Phases.  method = PE_HIP_STEP_GMIN: gmin stepping only; PE_HIP_STEP_SOURCE: source stepping only; PE_HIP_STEP_AUTO: gmin stepping, then
+ *   source stepping for what gmin stepping could not solve.  Instances of one batch may be in different phases at the same time.  A phase
+ *   starts from x = 0 with the junction state and the relay contacts as pe_hip_reset leaves them; time, companion histories and counters
+ *   are not touched (the Newton iterations of the levels count like any other).
+ *   3. The homotopy, lambda in [0, 1].  Source stepping: every independent static source value of the instance holds lambda * its real value
+ *   (one rounded multiply; at lambda = 1 the real value itself): PE_HIP_VDC, PE_HIP_IDC and the digital drives.  The other values written
+ *   at load time are no sources and are never scaled: the resistance of a PE_HIP_SWITCH, the gains of the controlled sources and of the
+ *   op-amp, the transformer ratios.  Sources whose value is formed at every iteration -- PE_HIP_VAC, PE_HIP_IAC, PE_HIP_VGEN -- are not
+ *   scaled either: in OP / DC they contribute what they always do there, in TROP they keep their value at t = 0.  Gmin stepping: the conductance from every
+ *   node to ground is g_start * (g_end / g_start)^lambda below lambda = 1 and the engine's g_min itself at lambda = 1, with
+ *   g_end = max(g_min, 1e-13); sources stay at their real values.
+ *   4. The controller, in plain double arithmetic (+, *, min, comparisons).  Level lambda = 0 is solved first; if it fails, the phase fails.
+ *   Then the candidate is t = min(1, lambda + Delta).  Accepted (status PE_HIP_OK and a finite solution): the state goes into the instance's
+ *   shadow, lambda = t, Delta *= grow (not after the level lambda = 0).  Rejected: the state comes back from the shadow, Delta *= shrink;
+ *   Delta < dl_min fails the phase.  The instance fails when its last phase fails or when it has spent max_levels levels over all its phases.
+ *   Fields <= 0 take their defaults: dl_init 0.125, grow 2, shrink 0.25, dl_min 2^-20, g_start 1e-2, max_levels 200.  step_max_newton <= 0:
+ *   the engine's max_newton; a positive value caps the Newton iterations of the stepping levels only (the direct attempt and the
+ *   options of the engine are untouched).
+ *   5. What the call leaves.  A solved instance has status PE_HIP_OK and holds its solution at the real source values and the engine's g_min.
+ *   A failed instance has the status of its last failed attempt (PE_HIP_ERR_NO_CONVERGENCE or PE_HIP_ERR_SINGULAR) and holds the state of the
+ *   last accepted level of its last phase, zeros if that phase accepted none.  Whatever the outcome -- an error return included -- every
+ *   source value and the node-to-ground conductance of every instance are the real ones again before the call returns: no later analysis
+ *   runs on scaled sources.  (pe_hip_get_matrix shows the system of the last solve, as always.)  Returns the first failing instance's
+ *   status, like pe_hip_analyze_dc.
+ *   6. Refusals (PE_HIP_ERR_ARG): no circuit, the control NULL, an unknown method, a mode other than OP / DC / TROP, a negative control
+ *   field, a non-finite one; PE_HIP_STEP_SOURCE on a circuit with a host-stamp overlay (pe_hip_set_overlay: its sources are not the
+ *   engine's to scale) -- PE_HIP_STEP_AUTO then runs the direct attempt and gmin stepping only.
+ * One symbolic analysis serves every level (matched on instance 0's values as elsewhere); the residual safety net covers the large-gmin
+ * levels.  The shadow and the controller's arrays are allocated at the first call and freed with the circuit. */
+#define PE_HIP_STEP_GMIN   1
+#define PE_HIP_STEP_SOURCE 2
+#define PE_HIP_STEP_AUTO   3
+typedef struct pe_hip_op_step_control {
+    int method;          /* PE_HIP_STEP_GMIN | PE_HIP_STEP_SOURCE | PE_HIP_STEP_AUTO */
+    int max_levels;      /* levels per instance over all its phases; <= 0: 200 */
+    int step_max_newton; /* Newton cap of the stepping levels; <= 0: the engine's */
+    int log_capacity;    /* log entries kept per instance; 0: none */
+    double dl_init, grow, shrink, dl_min; /* <= 0: 0.125, 2, 0.25, 2^-20 */
+    double g_start;      /* <= 0: 1e-2 */
+} pe_hip_op_step_control;
+typedef struct pe_hip_op_step_stats {
+    long long n_levels;      /* levels solved, summed over the instances (the direct attempt is not a level) */
+    long long n_accepted, n_rejected;
+    int n_direct, n_gmin, n_source; /* instances solved by the direct attempt / in the gmin phase / in the source phase */
+    int n_failed;            /* instances that gave up */
+    long long newton_iters;  /* all attempts, summed; an attempt that did not converge counts its cap */
+    int n_solves;            /* batched solves of the call, the direct attempt included */
+    int n_launches;          /* controller launches */
+    double gpu_ms;           /* HIP-event time of the whole call on the engine's stream */
+    double control_ms;       /* host time spent in the controller launches and their read-backs */
+} pe_hip_op_step_stats;
+int pe_hip_analyze_op_stepping(pe_hip_engine* h, int mode, const pe_hip_op_step_control* c, pe_hip_op_step_stats* stats);
+/* outcome per instance of the last stepping call (each array may be NULL): phase_solved_in 0 direct, 1 gmin, 2 source, -1 failed;
+ * lambda_reached = the last accepted lambda of its last phase (1 when solved); levels solved; levels rejected; Newton iterations of all
+ * its attempts.  PE_HIP_ERR_ARG before the first call on the resident circuit. */
+int pe_hip_get_op_step_state(pe_hip_engine* h, int first, int count, int* phase_solved_in, double* lambda_reached, int* levels, int* rejected,
+                             long long* newton_iters);
+/* the log of one instance as kept on the device, at most `capacity` entries in the order solved (each array may be NULL): phase (1 gmin,
+ * 2 source), lambda of the level, value = what was written for it (the node-to-ground conductance, or lambda itself for source stepping),
+ * outcome (1 accepted, 0 rejected), Newton iterations when accepted.  n_total: levels the instance solved, which may exceed log_capacity. */
+int pe_hip_get_op_step_log(pe_hip_engine* h, int instance, int capacity, int* phase, double* lambda, double* value, int* outcome, int* iters,
+                           int* n_total);
+
 /* ---- Small-signal noise analysis (.NOISE): the output noise spectral density of the circuit at its operating point, the share of every
  * device in it, and the integrated noise over the swept band -- by the ADJOINT method: one solve of the transposed small-signal system per
  * frequency point, whatever the number of sources.  With A the complex small-signal matrix of pe_hip_analyze_ac at omega and e the output
@@ -705,6 +774,8 @@ int pe_hip_sweep_set_options(pe_hip_sweep* s, const pe_hip_options* opt);
 int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int batch, int n_tables, const pe_hip_device_table* tables);
 int pe_hip_sweep_reset(pe_hip_sweep* s);
 int pe_hip_sweep_operating_point(pe_hip_sweep* s, int mode, pe_hip_run_stats* stats); /* OP / DC / TROP solve of every instance */
+/* the same with gmin / source stepping, per device engine; stats: sums over the devices, times and launch counts of the slowest */
+int pe_hip_sweep_operating_point_stepping(pe_hip_sweep* s, int mode, const pe_hip_op_step_control* c, pe_hip_op_step_stats* stats);
 int pe_hip_sweep_run(pe_hip_sweep* s, double dt, int nsteps, pe_hip_run_stats* stats); /* transient steps of every instance; stats: sums, slowest device's times */
 int pe_hip_sweep_reduce(pe_hip_sweep* s, double* out); /* [4][rows]: sum, sum of squares, min, max of the current solution over all instances */
 int pe_hip_sweep_get_solution(pe_hip_sweep* s, int first_instance, int count, double* x);

@@ -474,6 +474,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     pe::m2_graphs_clear(h->graphs);  // (captured launch sequences point into the circuit being replaced)
     probe_drop(h);                   // (a probe configuration belongs to the circuit: rows, batch)
     tr_adaptive_drop(h);             // (... and so do the shadow state and the history of the variable-step transient)
+    op_step_drop(h);                 // (... and the controller arrays of the stepped operating point)
     h->circ_pool.release();
     h->stats_scratch = nullptr;
     h->stats_doubles = 0;

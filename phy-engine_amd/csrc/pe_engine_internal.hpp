@@ -31,6 +31,7 @@
 #include "pe_kernels.hpp"
 #include "pe_lte.hpp"
 #include "pe_noise.hpp"
+#include "pe_op_step.hpp"
 #include "pe_sens.hpp"
 #include "pe_symbolic.hpp"
 
@@ -287,6 +288,16 @@ struct pe_hip_engine
         std::vector<double> res;          // [n_points][batch][n_keep]
         std::vector<int> status, iters, seed;  // [n_points][batch]
     } dcs;
+    // operating point with gmin / source stepping (pe_hip_analyze_op_stepping, pe_op_step.hpp): the controller's per-instance arrays and
+    // the shadow of the state a DC solve reads (allocated at the first call, dropped by a circuit load), the log (sized by the call's
+    // log_capacity) and whether the arrays hold the outcome of a call on the resident circuit
+    struct OpStep
+    {
+        Pool pool, log_pool;
+        bool allocated{}, valid{};
+        int log_capacity{-1};
+        pe::OpStepView V{};
+    } ops;
     long long param_epoch{};  // bumped by whatever changes hc's parameters, the options or the knobs (the DC sweep engine is rebuilt after it)
     std::vector<double> sym_values_override;  // representative |A| values for the row matching (AC engine)
 
@@ -382,6 +393,7 @@ namespace pe_eng PE_ENG_HIDDEN
     std::vector<CkPart> ck_parts(pe_hip_engine* h);
     // pe_engine_newton.cpp: variable-step transient
     void tr_adaptive_drop(pe_hip_engine* h);  // shadow state, history ring and step log gone (pe_hip_load_circuit)
+    void op_step_drop(pe_hip_engine* h);      // controller arrays, shadow and log of the stepped operating point gone (pe_hip_load_circuit)
     // pe_engine_ac.cpp: the stored AC sweep
     void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy); the noise and sensitivity state too
     inline void ac_sweep_invalidate(pe_hip_engine* h)  // whatever moves the operating point or the circuit: the stored sweep, the stored noise and sensitivity results

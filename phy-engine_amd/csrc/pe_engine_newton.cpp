@@ -731,6 +731,12 @@ namespace pe
         for(int q = 0; q < V.batch; ++q) dc_sweep_gather(ProbeHostTeam{}, V, S, q);
         return hipSuccess;
     }
+    // ... and the controller of the stepped operating point (pe_op_step.hpp)
+    hipError_t launch_op_step_control(hipStream_t, DevView const& V, OpStepView const& S, int role)
+    {
+        op_step_control_serial(V, S, role);
+        return hipSuccess;
+    }
 }  // namespace pe
 #endif
 
@@ -1207,6 +1213,291 @@ int pe_hip_analyze_dc(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
     if(mode != PE_HIP_MODE_OP && mode != PE_HIP_MODE_DC && mode != PE_HIP_MODE_TROP) return fail(h, PE_HIP_ERR_ARG, "analyze_dc: mode must be OP, DC or TROP");
     HIPCHK(h, hipSetDevice(h->device));
     return dc_solve(h, mode, st, true);
+}
+
+}  // extern "C"
+
+// ---------------- operating point with gmin / source stepping: dc_solve per level, the controller on the device (include/pe_hip.h, pe_op_step.hpp)
+namespace pe_eng
+{
+    void op_step_drop(pe_hip_engine* h)
+    {
+        auto& O = h->ops;
+        if(O.allocated) (void)hipStreamSynchronize(h->stream);
+        O.pool.release();
+        O.log_pool.release();
+        O = pe_hip_engine::OpStep{};
+    }
+}  // namespace pe_eng
+
+namespace
+{
+    // the controller's arrays and the shadow, sized by the circuit; the log, sized by the call
+    int op_step_alloc(pe_hip_engine* h, int log_capacity)
+    {
+        auto& O = h->ops;
+        auto& S = O.V;
+        auto const& hc = h->hc;
+        size_t const B = static_cast<size_t>(hc.batch);
+        if(!O.allocated)
+        {
+            auto& P = O.pool;
+            HIPCHK(h, P.alloc(S.state, B));
+            HIPCHK(h, P.alloc(S.phase, B));
+            HIPCHK(h, P.alloc(S.first, B));
+            HIPCHK(h, P.alloc(S.have_shadow, B));
+            HIPCHK(h, P.alloc(S.lambda, B));
+            HIPCHK(h, P.alloc(S.delta, B));
+            HIPCHK(h, P.alloc(S.cand, B));
+            HIPCHK(h, P.alloc(S.final_status, B));
+            HIPCHK(h, P.alloc(S.levels, B));
+            HIPCHK(h, P.alloc(S.rejected, B));
+            HIPCHK(h, P.alloc(S.iters, B));
+            HIPCHK(h, P.alloc(S.it_prev, B));
+            HIPCHK(h, P.alloc(S.log_n, B));
+            HIPCHK(h, P.alloc(S.sx, B * hc.rows));
+            HIPCHK(h, P.alloc(S.su, B * hc.nD()));
+            HIPCHK(h, P.alloc(S.sg, B * hc.nD()));
+            HIPCHK(h, P.alloc(S.sr, B * hc.nRl()));
+            HIPCHK(h, P.alloc(S.rec, 1));
+            O.allocated = true;
+        }
+        if(O.log_capacity != log_capacity)
+        {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            O.log_pool.release();
+            O.log_capacity = -1;
+            size_t const n = B * static_cast<size_t>(log_capacity);
+            HIPCHK(h, O.log_pool.alloc(S.log_phase, n));
+            HIPCHK(h, O.log_pool.alloc(S.log_outcome, n));
+            HIPCHK(h, O.log_pool.alloc(S.log_iters, n));
+            HIPCHK(h, O.log_pool.alloc(S.log_lambda, n));
+            HIPCHK(h, O.log_pool.alloc(S.log_value, n));
+            O.log_capacity = log_capacity;
+        }
+        return PE_HIP_OK;
+    }
+}  // namespace
+
+extern "C" {
+
+int pe_hip_analyze_op_stepping(pe_hip_engine* h, int mode, const pe_hip_op_step_control* c, pe_hip_op_step_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(!c) return fail(h, PE_HIP_ERR_ARG, "analyze_op_stepping: no control");
+    if(mode != PE_HIP_MODE_OP && mode != PE_HIP_MODE_DC && mode != PE_HIP_MODE_TROP) return fail(h, PE_HIP_ERR_ARG, "analyze_op_stepping: mode must be OP, DC or TROP");
+    if(c->method != PE_HIP_STEP_GMIN && c->method != PE_HIP_STEP_SOURCE && c->method != PE_HIP_STEP_AUTO)
+        return fail(h, PE_HIP_ERR_ARG, "analyze_op_stepping: unknown method");
+    double const fields[5] = {c->dl_init, c->grow, c->shrink, c->dl_min, c->g_start};
+    for(double const f: fields)
+        if(!(f >= 0.0) || !std::isfinite(f)) return fail(h, PE_HIP_ERR_ARG, "analyze_op_stepping: a negative or non-finite control field");
+    if(c->max_levels < 0 || c->step_max_newton < 0 || c->log_capacity < 0) return fail(h, PE_HIP_ERR_ARG, "analyze_op_stepping: a negative control field");
+    if(c->method == PE_HIP_STEP_SOURCE && has_overlay(h))
+        return fail(h, PE_HIP_ERR_ARG, "analyze_op_stepping: the sources of a host-stamp overlay cannot be stepped -- use PE_HIP_STEP_GMIN or PE_HIP_STEP_AUTO");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto const& hc = h->hc;
+    int const B = hc.batch;
+    auto& O = h->ops;
+    O.valid = false;
+    // (a structurally singular circuit fails here as it does in pe_hip_analyze_dc: before anything is solved, so nothing can step)
+    if(hc.rows > 0)
+        if(int const rc = ensure_symbolic(h, false, 0.0); rc != PE_HIP_OK) return rc;
+    if(int const rc = op_step_alloc(h, c->log_capacity); rc != PE_HIP_OK) return rc;
+    auto& S = O.V;
+    int const engine_newton = h->V.max_newton;
+    S.method = has_overlay(h) ? (c->method & PE_HIP_STEP_GMIN) : c->method;
+    S.max_levels = c->max_levels > 0 ? c->max_levels : 200;
+    S.log_capacity = c->log_capacity;
+    S.direct_cap = hc.nonlinear ? engine_newton : 1;
+    S.attempt_cap = hc.nonlinear ? (c->step_max_newton > 0 ? c->step_max_newton : engine_newton) : 1;
+    S.dl_init = c->dl_init > 0.0 ? c->dl_init : 0.125;
+    S.grow = c->grow > 0.0 ? c->grow : 2.0;
+    S.shrink = c->shrink > 0.0 ? c->shrink : 0.25;
+    S.dl_min = c->dl_min > 0.0 ? c->dl_min : 0x1p-20;
+    S.g_min = h->opt.g_min;
+    S.g_start = c->g_start > 0.0 ? c->g_start : 1e-2;
+    S.g_ratio = std::max(h->opt.g_min, 1e-13) / S.g_start;
+    // the source slots and their real values: what fill_static_dv writes for VDC, IDC and the digital drives (the host circuit mirrors the
+    // resident values).  The other load-time values -- a switch's resistance among them -- are not in the list: nothing scales them.
+    std::vector<int> slot;
+    for(int i = 0; i < hc.nVdc(); ++i) slot.push_back(hc.dv_vdc + i);
+    for(int i = 0; i < hc.nIdc(); ++i) slot.push_back(hc.dv_idc + i);
+    for(int k = 0; k < hc.n_drives; ++k) slot.push_back(hc.dv_drv + k);
+    S.n_src = static_cast<int>(slot.size());
+    std::vector<double> base(static_cast<size_t>(B) * slot.size());
+    {
+        std::vector<double> dv(static_cast<size_t>(B) * hc.dv_len, 0.0);
+        fill_static_dv(h, dv);
+        for(int b = 0; b < B; ++b)
+            for(size_t j = 0; j < slot.size(); ++j) base[static_cast<size_t>(b) * slot.size() + j] = dv[static_cast<size_t>(b) * hc.dv_len + slot[j]];
+    }
+    Pool tabs;  // (uploaded once per call)
+    int const* d_slot{};
+    double const* d_base{};
+    HIPCHK(h, tabs.upload(d_slot, slot));
+    HIPCHK(h, tabs.upload(d_base, base));
+    S.src_slot = d_slot;
+    S.src_base = d_base;
+
+    pe_hip_op_step_stats T{};
+    hipStream_t const st = h->stream;
+    hipEvent_t ev_a{}, ev_b{};  // (dc_solve records the engine's own pair)
+    HIPCHK(h, hipEventCreate(&ev_a));
+    if(hipError_t const e = hipEventCreate(&ev_b); e != hipSuccess)
+    {
+        (void)hipEventDestroy(ev_a);
+        HIPCHK(h, e);
+    }
+    pe::OpStepRecord rec{};
+    auto control = [&](int role) -> int
+    {
+        auto const t0 = clk::now();
+        HIPCHK(h, hipMemsetAsync(S.rec, 0, sizeof(rec), st));
+        HIPCHK(h, pe::launch_op_step_control(st, h->V, S, role));
+        HIPCHK(h, hipMemcpyAsync(&rec, S.rec, sizeof(rec), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        ++T.n_launches;
+        T.control_ms += ms_since(t0);
+        return PE_HIP_OK;
+    };
+    // a numerical failure (or the parked status of the others) is an instance's own: everything else ends the call
+    auto numerical = [](int rc)
+    { return rc == PE_HIP_OK || rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE || rc == pe::DC_SWEEP_PARKED; };
+    bool stepping = false;  // (slots may hold scaled values: the finish role must run)
+    auto body = [&]() -> int
+    {
+        HIPCHK(h, hipEventRecord(ev_a, st));
+        HIPCHK(h, hipMemcpyAsync(S.it_prev, h->V.n_iters, static_cast<size_t>(B) * sizeof(long long), hipMemcpyDeviceToDevice, st));
+        int rc = dc_solve(h, mode, nullptr, true);  // 1. the direct attempt: pe_hip_analyze_dc itself
+        ++T.n_solves;
+        if(!numerical(rc)) return rc;
+        if(hc.rows == 0) return PE_HIP_OK;
+        stepping = true;
+        if(rc = control(pe::OP_STEP_ROLE_BEGIN); rc != PE_HIP_OK) return rc;
+        T.n_direct = rec.n_direct;
+        T.newton_iters += rec.iters;
+        T.n_failed += rec.n_failed;
+        if(rec.n_active == 0 && rec.n_failed == 0)
+        {
+            // nothing failed: no slot was touched, and the parked statuses are all PE_HIP_OK again without another launch
+            HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(B) * sizeof(int), st));
+            HIPCHK(h, hipStreamSynchronize(st));
+            stepping = false;
+            return PE_HIP_OK;
+        }
+        h->V.max_newton = hc.nonlinear ? S.attempt_cap : engine_newton;
+        while(rec.n_active > 0)
+        {
+            T.n_levels += rec.n_active;
+            rc = dc_solve(h, mode, nullptr, false);  // (a level is a new solve point: nothing of the last one is reused)
+            ++T.n_solves;
+            if(!numerical(rc)) return rc;
+            if(rc = control(pe::OP_STEP_ROLE_CONTROL); rc != PE_HIP_OK) return rc;
+            T.n_accepted += rec.n_accepted;
+            T.n_rejected += rec.n_rejected;
+            T.n_failed += rec.n_failed;
+            T.newton_iters += rec.iters;
+        }
+        return PE_HIP_OK;
+    };
+    int rc = body();
+    h->V.max_newton = engine_newton;
+    if(stepping)
+    {
+        // whatever happened: real values in every slot, final statuses, failed instances back to their last accepted level
+        std::string const err = h->err;
+        int const frc = control(pe::OP_STEP_ROLE_FINISH);
+        if(rc == PE_HIP_OK) rc = frc;
+        else
+            h->err = err;
+        h->fact_valid = false;
+        h->a_static.clear();
+    }
+    float ms = 0.f;
+    if(hipEventRecord(ev_b, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) (void)hipEventElapsedTime(&ms, ev_a, ev_b);
+    (void)hipEventDestroy(ev_a);
+    (void)hipEventDestroy(ev_b);
+    T.gpu_ms = ms;
+    if(rc != PE_HIP_OK)
+    {
+        if(stats) *stats = T;
+        return rc;
+    }
+    if(hc.rows == 0)
+    {
+        if(stats) *stats = T;
+        return PE_HIP_OK;
+    }
+    // the outcome: one read of the final statuses and phases (no solution)
+    std::vector<int> status(static_cast<size_t>(B)), phase(static_cast<size_t>(B)), state(static_cast<size_t>(B));
+    HIPCHK(h, hipMemcpy(status.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(phase.data(), S.phase, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(state.data(), S.state, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+    int first = PE_HIP_OK;
+    for(int b = 0; b < B; ++b)
+    {
+        if(state[b] == pe::OP_STEP_SOLVED)
+        {
+            if(phase[b] == pe::OP_STEP_GMIN) ++T.n_gmin;
+            else if(phase[b] == pe::OP_STEP_SOURCE)
+                ++T.n_source;
+        }
+        else if(first == PE_HIP_OK)
+            first = status[b] != PE_HIP_OK ? status[b] : PE_HIP_ERR_NO_CONVERGENCE;
+    }
+    O.valid = true;
+    if(stats) *stats = T;
+    if(first != PE_HIP_OK)
+        return fail(h, first, first == PE_HIP_ERR_SINGULAR ? "analyze_op_stepping: singular matrix (zero / non-finite pivot) at the last attempt of an instance"
+                                                            : "analyze_op_stepping: not every instance reached its operating point");
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_op_step_state(pe_hip_engine* h, int first, int count, int* phase_solved_in, double* lambda_reached, int* levels, int* rejected,
+                             long long* newton_iters)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    auto const& O = h->ops;
+    if(!O.valid) return fail(h, PE_HIP_ERR_ARG, "get_op_step_state: no stepping call yet");
+    if(first < 0 || count < 0 || first + count > h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_op_step_state: instances out of range");
+    HIPCHK(h, hipSetDevice(h->device));
+    size_t const n = static_cast<size_t>(count);
+    if(phase_solved_in)
+    {
+        std::vector<int> state(n);
+        HIPCHK(h, hipMemcpy(state.data(), O.V.state + first, n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(phase_solved_in, O.V.phase + first, n * sizeof(int), hipMemcpyDeviceToHost));
+        for(size_t i = 0; i < n; ++i)
+            if(state[i] != pe::OP_STEP_SOLVED) phase_solved_in[i] = -1;
+    }
+    if(lambda_reached) HIPCHK(h, hipMemcpy(lambda_reached, O.V.lambda + first, n * sizeof(double), hipMemcpyDeviceToHost));
+    if(levels) HIPCHK(h, hipMemcpy(levels, O.V.levels + first, n * sizeof(int), hipMemcpyDeviceToHost));
+    if(rejected) HIPCHK(h, hipMemcpy(rejected, O.V.rejected + first, n * sizeof(int), hipMemcpyDeviceToHost));
+    if(newton_iters) HIPCHK(h, hipMemcpy(newton_iters, O.V.iters + first, n * sizeof(long long), hipMemcpyDeviceToHost));
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_op_step_log(pe_hip_engine* h, int instance, int capacity, int* phase, double* lambda, double* value, int* outcome, int* iters,
+                           int* n_total)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    auto const& O = h->ops;
+    if(!O.valid) return fail(h, PE_HIP_ERR_ARG, "get_op_step_log: no stepping call yet");
+    if(instance < 0 || instance >= h->hc.batch || capacity < 0) return fail(h, PE_HIP_ERR_ARG, "get_op_step_log: instance or capacity out of range");
+    HIPCHK(h, hipSetDevice(h->device));
+    int total = 0;
+    HIPCHK(h, hipMemcpy(&total, O.V.log_n + instance, sizeof(int), hipMemcpyDeviceToHost));
+    if(n_total) *n_total = total;
+    size_t const n = static_cast<size_t>(std::min({capacity, total, O.log_capacity}));
+    size_t const o = static_cast<size_t>(instance) * static_cast<size_t>(O.log_capacity);
+    if(n == 0) return PE_HIP_OK;
+    if(phase) HIPCHK(h, hipMemcpy(phase, O.V.log_phase + o, n * sizeof(int), hipMemcpyDeviceToHost));
+    if(lambda) HIPCHK(h, hipMemcpy(lambda, O.V.log_lambda + o, n * sizeof(double), hipMemcpyDeviceToHost));
+    if(value) HIPCHK(h, hipMemcpy(value, O.V.log_value + o, n * sizeof(double), hipMemcpyDeviceToHost));
+    if(outcome) HIPCHK(h, hipMemcpy(outcome, O.V.log_outcome + o, n * sizeof(int), hipMemcpyDeviceToHost));
+    if(iters) HIPCHK(h, hipMemcpy(iters, O.V.log_iters + o, n * sizeof(int), hipMemcpyDeviceToHost));
+    return PE_HIP_OK;
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include "pe_front.hpp"
 #include "pe_ac_sweep.hpp"
 #include "pe_dc_sweep.hpp"
+#include "pe_op_step.hpp"
 #include "pe_noise.hpp"
 #include "pe_sens.hpp"
 #include "pe_lte.hpp"
@@ -1993,6 +1994,44 @@ namespace pe
     {
         if(V.batch <= 0) return hipSuccess;
         hipLaunchKernelGGL(k_dc_sweep_gather, dim3(sweep_grid(S.n_keep), V.batch), dim3(256), 0, st, V, S);
+        return hipGetLastError();
+    }
+
+    // ---- gmin / source stepping for operating points (pe_op_step.hpp, pe_engine_newton.cpp pe_hip_analyze_op_stepping): the controller between
+    // two DC solves.  One workgroup of four wavefronts per instance: (1) finiteness of x as a flag -- a ballot per wavefront, the four
+    // ballots ORed through LDS, never a floating-point maximum; (2) thread 0 takes the instance's decision (op_step_advance) and hands it
+    // to the workgroup through LDS; (3) the workgroup copies x and the junction / relay state to or from the shadow, coalesced, and writes
+    // the source slots and DV_GMIN of the next level.  Integer atomics only, on the record.
+    __global__ void __launch_bounds__(256) k_op_step_control(DevView V, OpStepView S, int role)
+    {
+        __shared__ int wave_bad[4];
+        __shared__ OpStepAct act;
+        int const b = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x);
+        HipTeam tm;
+        int const bad = role == OP_STEP_ROLE_FINISH ? 0 : op_step_nonfinite(tm, V, b);
+        bool const any = __ballot(bad) != 0;
+        if((tid & 63) == 0) wave_bad[tid >> 6] = any ? 1 : 0;
+        __syncthreads();
+        if(tid == 0)
+        {
+            OpStepRecord R{};
+            act = op_step_advance(V, S, b, wave_bad[0] | wave_bad[1] | wave_bad[2] | wave_bad[3], role, R);
+            if(R.n_active) atomicAdd(&S.rec->n_active, R.n_active);
+            if(R.n_done) atomicAdd(&S.rec->n_done, R.n_done);
+            if(R.n_failed) atomicAdd(&S.rec->n_failed, R.n_failed);
+            if(R.n_accepted) atomicAdd(&S.rec->n_accepted, R.n_accepted);
+            if(R.n_rejected) atomicAdd(&S.rec->n_rejected, R.n_rejected);
+            if(R.n_direct) atomicAdd(&S.rec->n_direct, R.n_direct);
+            if(R.iters) atomicAdd(reinterpret_cast<unsigned long long*>(&S.rec->iters), static_cast<unsigned long long>(R.iters));
+        }
+        __syncthreads();  // (the decision in LDS, and thread 0's reads of the state before the copies below overwrite it)
+        OpStepAct const a = act;
+        op_step_apply(tm, V, S, b, a);
+    }
+    hipError_t launch_op_step_control(hipStream_t st, DevView const& V, OpStepView const& S, int role)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_op_step_control, dim3(V.batch), dim3(256), 0, st, V, S, role);
         return hipGetLastError();
     }
 

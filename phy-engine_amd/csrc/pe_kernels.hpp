@@ -105,4 +105,10 @@ namespace pe
     hipError_t launch_dc_sweep_seed(hipStream_t st, DevView const& V, DcSweepView const& S, bool from_main);
     hipError_t launch_dc_sweep_classify(hipStream_t st, DevView const& V, DcSweepView const& S, bool reseed);
     hipError_t launch_dc_sweep_gather(hipStream_t st, DevView const& V, DcSweepView const& S);
+    // gmin / source stepping for operating points (pe_op_step.hpp): the controller of every instance after a solve -- role BEGIN classifies the
+    // direct attempt and opens the first phase of the failing instances, CONTROL accepts or rejects the level just solved and writes the
+    // slots of the next one, FINISH puts the real values and the final statuses back.  The host zeroes S.rec before the launch and reads it
+    // after.  Builds without HIP: serial host definition in pe_engine_newton.cpp.
+    struct OpStepView;
+    hipError_t launch_op_step_control(hipStream_t st, DevView const& V, OpStepView const& S, int role);
 }  // namespace pe

@@ -211,6 +211,36 @@ int pe_hip_sweep_operating_point(pe_hip_sweep* s, int mode, pe_hip_run_stats* st
     return rc;
 }
 
+// the same solve with gmin / source stepping (pe_hip_analyze_op_stepping) on every device's engine; stats (may be NULL): sums over the
+// devices, times and launch counts = the slowest device
+int pe_hip_sweep_operating_point_stepping(pe_hip_sweep* s, int mode, const pe_hip_op_step_control* c, pe_hip_op_step_stats* stats)
+{
+    if(!s || !s->loaded) return PE_HIP_ERR_ARG;
+    std::vector<pe_hip_op_step_stats> st(s->eng.size());
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_op_stepping(s->eng[g], mode, c, &st[g]); });
+    if(stats)
+    {
+        *stats = pe_hip_op_step_stats{};
+        for(size_t g = 0; g < s->eng.size(); ++g)
+        {
+            if(s->hi[g] <= s->lo[g]) continue;
+            stats->n_levels += st[g].n_levels;
+            stats->n_accepted += st[g].n_accepted;
+            stats->n_rejected += st[g].n_rejected;
+            stats->n_direct += st[g].n_direct;
+            stats->n_gmin += st[g].n_gmin;
+            stats->n_source += st[g].n_source;
+            stats->n_failed += st[g].n_failed;
+            stats->newton_iters += st[g].newton_iters;
+            stats->n_solves = std::max(stats->n_solves, st[g].n_solves);
+            stats->n_launches = std::max(stats->n_launches, st[g].n_launches);
+            stats->gpu_ms = std::max(stats->gpu_ms, st[g].gpu_ms);
+            stats->control_ms = std::max(stats->control_ms, st[g].control_ms);
+        }
+    }
+    return rc;
+}
+
 // out[4][rows]: sum, sum of squares, min, max over ALL instances -- each device reduces its block on the device
 // (pe_hip_sweep_statistics), the blocks are combined here in device order
 int pe_hip_sweep_reduce(pe_hip_sweep* s, double* out)

@@ -35,10 +35,12 @@ EXPORTS = [
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_get_sens_params", "pe_hip_analyze_sens", "pe_hip_get_sens",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
+    "pe_hip_analyze_op_stepping", "pe_hip_get_op_step_state", "pe_hip_get_op_step_log", "pe_hip_sweep_operating_point_stepping",
     "pe_hip_get_static_fronts", "pe_hip_get_static_skip_stats", "pe_hip_get_static_skip_refinement_stats",
     "pe_hip_get_matrix_ac", "pe_hip_get_ac_pass_size", "pe_hip_get_ac_analysis_omega",
 ]
 DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
+STEP_GMIN, STEP_SOURCE, STEP_AUTO = 1, 2, 3
 # pe_hip_measure_kind
 MEAS_MIN, MEAS_MAX, MEAS_AVG, MEAS_RMS, MEAS_INTEG, MEAS_CROSS = 1, 2, 3, 4, 5, 6
 _MEAS_NAMES = {"min": MEAS_MIN, "max": MEAS_MAX, "avg": MEAS_AVG, "rms": MEAS_RMS, "integ": MEAS_INTEG, "cross": MEAS_CROSS}
@@ -184,6 +186,26 @@ class DcSweepStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OpStepControl(C.Structure):
+    _fields_ = [("method", C.c_int), ("max_levels", C.c_int), ("step_max_newton", C.c_int), ("log_capacity", C.c_int), ("dl_init", C.c_double),
+                ("grow", C.c_double), ("shrink", C.c_double), ("dl_min", C.c_double), ("g_start", C.c_double)]
+
+
+class OpStepStats(C.Structure):
+    _fields_ = [("n_levels", C.c_longlong), ("n_accepted", C.c_longlong), ("n_rejected", C.c_longlong), ("n_direct", C.c_int), ("n_gmin", C.c_int),
+                ("n_source", C.c_int), ("n_failed", C.c_int), ("newton_iters", C.c_longlong), ("n_solves", C.c_int), ("n_launches", C.c_int),
+                ("gpu_ms", C.c_double), ("control_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def op_step_control(method=STEP_AUTO, max_levels=0, step_max_newton=0, log_capacity=256, dl_init=0.0, grow=0.0, shrink=0.0, dl_min=0.0, g_start=0.0):
+    """pe_hip_op_step_control; a field left at 0 takes the default of include/pe_hip.h"""
+    return OpStepControl(int(method), int(max_levels), int(step_max_newton), int(log_capacity), float(dl_init), float(grow), float(shrink),
+                         float(dl_min), float(g_start))
+
+
 class NoiseControl(C.Structure):
     _fields_ = [("out_pos", C.c_int), ("out_neg", C.c_int), ("temp_k", C.c_double), ("keep_contributions", C.c_int)]
 
@@ -272,6 +294,12 @@ def lib():
         l.pe_hip_analyze_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(DcSweepControl), C.POINTER(C.c_int), C.POINTER(DcSweepStats)]
         l.pe_hip_get_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
         l.pe_hip_get_dc_sweep_status.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
+        l.pe_hip_analyze_op_stepping.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpStepControl), C.POINTER(OpStepStats)]
+        l.pe_hip_get_op_step_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_longlong)]
+        l.pe_hip_get_op_step_log.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        l.pe_hip_sweep_operating_point_stepping.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpStepControl), C.POINTER(OpStepStats)]
         l.pe_hip_analyze_tr_adaptive.argtypes = [C.c_void_p, C.c_double, C.POINTER(TrControl), C.POINTER(TrAdaptiveStats)]
         l.pe_hip_get_tr_step_log.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         _lib = l
@@ -662,6 +690,36 @@ class Engine(_Probes):
         self._chk(lib().pe_hip_get_ac_pass_size(self._h, int(which), C.byref(p)))
         return p.value
 
+    def analyze_op_stepping(self, mode=MODE_OP, method=STEP_AUTO, check=True, **control):
+        """operating point with gmin / source stepping where the direct attempt fails (pe_hip_analyze_op_stepping); control: the fields of
+        pe_hip_op_step_control (op_step_control).  Returns the statistics + "rc"."""
+        st = OpStepStats()
+        ctl = op_step_control(method, **control)
+        rc = lib().pe_hip_analyze_op_stepping(self._h, int(mode), C.byref(ctl), C.byref(st))
+        if check:
+            self._chk(rc)
+        return dict(st.asdict(), rc=rc)
+
+    def op_step_state(self):
+        """per instance of the last analyze_op_stepping: phase_solved_in (0 direct, 1 gmin, 2 source, -1 failed), lambda_reached, levels,
+        rejected, newton_iters"""
+        B = self.batch
+        ph, lv, rj = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        lam = np.zeros(B)
+        it = np.zeros(B, dtype=np.int64)
+        self._chk(lib().pe_hip_get_op_step_state(self._h, 0, B, _ip(ph), _dp(lam), _ip(lv), _ip(rj), it.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return {"phase_solved_in": ph, "lambda_reached": lam, "levels": lv, "rejected": rj, "newton_iters": it}
+
+    def op_step_log(self, instance):
+        """the device-side log of one instance: phase, lambda, value, outcome, iters per level solved (as many as log_capacity kept) + n_total"""
+        n = C.c_int()
+        self._chk(lib().pe_hip_get_op_step_log(self._h, int(instance), 0, None, None, None, None, None, C.byref(n)))
+        k = n.value
+        ph, oc, it = (np.zeros(k, dtype=np.int32) for _ in range(3))
+        lam, val = np.zeros(k), np.zeros(k)
+        self._chk(lib().pe_hip_get_op_step_log(self._h, int(instance), k, _ip(ph), _dp(lam), _dp(val), _ip(oc), _ip(it), C.byref(n)))
+        return {"phase": ph, "lambda": lam, "value": val, "outcome": oc, "iters": it, "n_total": n.value}
+
     def set_dc_sweep_rows(self, rows=None):
         """rows of x kept for every point of the following analyze_dc_sweep calls; None / empty: all rows"""
         r = np.ascontiguousarray([] if rows is None else rows, dtype=np.int32).reshape(-1)
@@ -893,6 +951,15 @@ class Sweep(_Probes):
         st = RunStats()
         self._chk(lib().pe_hip_sweep_run(self._h, float(dt), int(nsteps), C.byref(st)))
         return st.asdict()
+
+    def operating_point_stepping(self, mode=MODE_OP, method=STEP_AUTO, check=True, **control):
+        """pe_hip_sweep_operating_point_stepping: Engine.analyze_op_stepping on every device's engine, statistics summed"""
+        st = OpStepStats()
+        ctl = op_step_control(method, **control)
+        rc = lib().pe_hip_sweep_operating_point_stepping(self._h, int(mode), C.byref(ctl), C.byref(st))
+        if check:
+            self._chk(rc)
+        return dict(st.asdict(), rc=rc)
 
     def reduce(self):
         out = np.empty((4, self.rows))

@@ -1432,6 +1432,36 @@ namespace phy_engine
             return rc == PE_HIP_OK || gpu_fail();
         }
 
+        // Operating point with gmin / source stepping (pe_hip_analyze_op_stepping, include/pe_hip.h): what analyze() does for OP, DC or the
+        // operating point of TROP, with the continuation of the header where the direct Newton iteration fails.  method: PE_HIP_STEP_GMIN,
+        // PE_HIP_STEP_SOURCE or PE_HIP_STEP_AUTO.  The solution is scattered into the nodes and branches as after analyze();
+        // last_op_step_stats says how it was reached.  analyze() itself is unchanged: it never steps.
+        pe_hip_op_step_stats last_op_step_stats{};
+        [[nodiscard]] bool analyze_op_stepping(analyze_type type, int method = PE_HIP_STEP_AUTO) noexcept
+        {
+            last_op_step_stats = pe_hip_op_step_stats{};
+            if(type != analyze_type::OP && type != analyze_type::DC && type != analyze_type::TROP)
+            {
+                last_error = "analyze_op_stepping: the analysis must be OP, DC or TROP";
+                return false;
+            }
+            auto const saved = at;
+            at = type;
+            bool const prepared = prepare();
+            at = saved;
+            if(!prepared || !gpu_ || !loaded_) return false;
+            int const mode = type == analyze_type::OP ? PE_HIP_MODE_OP : (type == analyze_type::TROP ? PE_HIP_MODE_TROP : PE_HIP_MODE_DC);
+            pe_hip_op_step_control ctl{};
+            ctl.method = method;
+            int const rc = node_counter + branch_counter == 0 ? PE_HIP_OK : pe_hip_analyze_op_stepping(gpu_, mode, &ctl, &last_op_step_stats);
+            scatter();
+            mirror_mna();
+            if(rc != PE_HIP_OK) return gpu_fail();
+            for(auto* c: overlay_models_)
+                if(!c->ptr->save_op()) return overlay_hook_failed(c, "save_op_define");
+            return true;
+        }
+
         // one AC solve (solve_once with iterate_ac): phasors scattered into the nodes / branches as complex values
         bool solve_ac_point(double omega) noexcept
         {
