@@ -755,6 +755,46 @@ int pe_hip_arm_probes(pe_hip_engine* h);
 int pe_hip_get_probe_samples(pe_hip_engine* h, int first_instance, int count, double* t, double* v, int* n_recorded, long long* n_dropped);
 int pe_hip_get_measures(pe_hip_engine* h, int first_instance, int count, double* out);
 
+/* ---- Fourier analysis of transient probes (.four): harmonics 0 .. H of f0 and the total harmonic distortion of configured probes,
+ * accumulated ON THE DEVICE at every accepted step of an armed probe window; the host reads back (H + 1) coefficients per probe and instance.
+ *   The window is [t_start, t_end], t_end = t_start + n_periods / f0, formed once on the host in double.  Tw = t_end - t_start,
+ *   w0 = 2 pi f0, tau = t - t_start.  v(t) of a configured probe is the piecewise-linear interpolant through the accepted points of the
+ *   armed window, the pairs (t0,v0) -> (t1,v1) the measures see.  For k = 0 .. H:
+ *                      a_0 = (1 / Tw) int v dtau, b_0 = 0
+ *                      a_k = (2 / Tw) int v cos(k w0 tau) dtau,  b_k = (2 / Tw) int v sin(k w0 tau) dtau      (k >= 1)
+ *   over the part of the window the accepted steps covered: the exact integral of that interpolant (Filon-trapezoidal weights per
+ *   segment, not a sample rule).  A segment that straddles t_start or t_end is clipped there, its end value taken by linear
+ *   interpolation; segments wholly outside contribute nothing.  Each integral is a compensated sum in the order of the accepted steps;
+ *   `stride` and `capacity` of the sample buffer have no influence, rejected or rolled-back steps record nothing.
+ *                      amp_k = sqrt(a_k^2 + b_k^2), amp_0 = |a_0|
+ *                      phase_k = atan2(-b_k, a_k) (phase_0 = 0 or pi), so that v ~ a_0 + sum amp_k cos(k w0 tau + phase_k)
+ *                      thd = sqrt(sum_{k = 2 .. H} amp_k^2) / amp_1, summed in ascending k; the division is what IEEE gives
+ *                      covered[b] = length of the window integrated so far (the sum of the clipped segments' tau_b - tau_a)
+ *   Coefficients are always normalised by the nominal Tw: compare covered with Tw.  An instance whose covered is 0 (never armed since
+ *   the configuration, or a window not yet reached) reads NaN.  Running past t_end is harmless, the last segment is clipped: with fixed
+ *   steps do run a step or two past it, because t is accumulated step by step and may fall a rounding short of t_end; with
+ *   pe_hip_analyze_tr_adaptive make t_end the t_stop or a breakpoint.
+ *   pe_hip_set_fourier  needs a probe configuration with at least one probe; `probes` are indices into its probe list (duplicates
+ *                      allowed).  NULL or n_probes = 0 removes the analysis.  pe_hip_set_probes and pe_hip_load_circuit drop it.  Like
+ *                      pe_hip_set_probes, a successful call ends an armed window: arm again.  pe_hip_arm_probes zeroes the accumulators;
+ *                      whatever disarms the probe window disarms this too, and what was accumulated stays readable until the next arm.
+ *                      Not part of a checkpoint.  PE_HIP_ERR_ARG, engine and current configuration unchanged, for: no circuit or no
+ *                      probes; f0 not finite or <= 0; t_start not finite; n_periods < 1; n_harmonics outside 1 .. 63; a probe index out
+ *                      of range; n_probes < 0; a t_end that is not finite or not > t_start in double.
+ *   pe_hip_get_fourier  coef [count][n_probes][H + 1][4] = a, b, amp, phase; thd [count][n_probes]; covered [count]; any pointer may be
+ *                      NULL.  Normalisation, amp, phase and thd are computed on the device (k_fourier_finish) at every call. */
+typedef struct pe_hip_fourier_control
+{
+    double f0;        /* Hz, finite, > 0 */
+    double t_start;   /* absolute time, finite */
+    int n_periods;    /* >= 1 */
+    int n_harmonics;  /* H, 1 .. 63  (DC + H harmonics = at most one wavefront of lanes) */
+    int n_probes;
+    const int* probes; /* indices into the probe list of pe_hip_set_probes; duplicates allowed */
+} pe_hip_fourier_control;
+int pe_hip_set_fourier(pe_hip_engine* h, const pe_hip_fourier_control* c);
+int pe_hip_get_fourier(pe_hip_engine* h, int first_instance, int count, double* coef, double* thd, double* covered);
+
 /* ---- Monte-Carlo / parameter sweep over several GPUs of one node (csrc/pe_sweep.cpp).
  * Independent instances of ONE topology are the natural shard of this path: the symbolic analysis is replicated per device, the
  * instances are dealt out in contiguous blocks of ceil(batch / G) per device -- the chunk rule of the reference's only
@@ -786,6 +826,9 @@ int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int 
 int pe_hip_sweep_arm_probes(pe_hip_sweep* s);
 int pe_hip_sweep_get_probe_samples(pe_hip_sweep* s, int first_instance, int count, double* t, double* v, int* n_recorded, long long* n_dropped);
 int pe_hip_sweep_get_measures(pe_hip_sweep* s, int first_instance, int count, double* out);
+/* the Fourier analysis of every instance of the sweep: pe_hip_set_fourier on each device's engine, pe_hip_get_fourier in global instance order */
+int pe_hip_sweep_set_fourier(pe_hip_sweep* s, const pe_hip_fourier_control* c);
+int pe_hip_sweep_get_fourier(pe_hip_sweep* s, int first_instance, int count, double* coef, double* thd, double* covered);
 /* iteration count of every step of instance 0 since the last reset (parity with the reference's Newton counts) */
 int pe_hip_get_newton_trace(pe_hip_engine* h, int capacity, int* iters, int* n_out);
 /* last stamped MNA system of one instance (CSR, sorted columns; vals/rhs may be NULL) */

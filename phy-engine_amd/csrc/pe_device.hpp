@@ -66,6 +66,18 @@ namespace pe
         int const* accept;          // [batch] split schedule (k_probe_record): 1 = the step just solved was accepted for this instance
     };
 
+    // Fourier analysis of configured probes (pe_fourier.hpp, pe_hip_set_fourier): harmonics 0 .. H of f0 over [t_start, t_end], accumulated at
+    // every accepted step of an armed window.  Lives in device memory: the recording launches get a pointer (null: none configured, tested
+    // once per step, wavefront-uniform), so that the resident kernel holds none of its fields across a solve.
+    struct FourierView
+    {
+        int n_fp, H;                // configured probes, harmonics above DC
+        int const* probes;          // [n_fp] indices into ProbeView::rows (duplicates allowed)
+        double w0, t_start, t_end;  // 2 pi f0; the window, formed on the host
+        double* acc;                // [batch][n_fp][H + 1][4] sum and compensation of int v cos, sum and compensation of int v sin
+        double* cov;                // [batch] length of the window integrated so far
+    };
+
     struct DevView
     {
         // ---- sizes
@@ -247,9 +259,11 @@ namespace pe
 #endif
 
     // The view of the launches that record into an armed probe window (k_tr_steps<MINW, true>, k_probe_arm, k_probe_record): the engine's
-    // view + the window.  The engine's own view, which captured launch sequences are keyed by, never carries it.
+    // view + the window (+ the Fourier analysis that rides on it).  The engine's own view, which captured launch sequences are keyed
+    // by, never carries it.
     struct ProbedView : DevView
     {
         ProbeView pr{};
+        FourierView const* fo{};  // device memory; null: no Fourier analysis configured
     };
 }  // namespace pe

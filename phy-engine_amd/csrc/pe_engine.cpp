@@ -241,6 +241,7 @@ pe::ProbedView probe_view(pe_hip_engine const* h)
     static_cast<pe::DevView&>(V) = h->V;
     V.probe_armed = 1;
     V.pr = h->probe.pv;
+    V.fo = h->fourier.configured ? h->fourier.dev : nullptr;
     return V;
 }
 void probe_disarm(pe_hip_engine* h)
@@ -248,9 +249,21 @@ void probe_disarm(pe_hip_engine* h)
     h->probe.armed = false;
     h->tra.n_pts = 0;  // (whatever ends a probe window also restarts the history of the variable-step transient: x or t moved)
 }
+void fourier_drop(pe_hip_engine* h)
+{
+    auto& F = h->fourier;
+    if(F.configured) (void)hipStreamSynchronize(h->stream);  // (a recording launch may still write the accumulators)
+    F.pool.release();
+    F.configured = false;
+    F.n_fp = F.H = 0;
+    F.fv = pe::FourierView{};
+    F.dev = nullptr;
+    F.out_coef = F.out_thd = nullptr;
+}
 void probe_drop(pe_hip_engine* h)
 {
     auto& P = h->probe;
+    fourier_drop(h);  // (its probe indices and its window belong to this configuration)
     if(P.configured) (void)hipStreamSynchronize(h->stream);  // (a recording launch may still read the buffers)
     P.pool.release();
     P.configured = P.armed = false;
@@ -337,6 +350,7 @@ void pe_hip_destroy(pe_hip_engine* h)
     if(h->ac.eng) pe_hip_destroy(h->ac.eng);
     (void)hipStreamSynchronize(h->stream);
     if(h->graphs) pe::m2_graphs_destroy(h->graphs);  // (captured launch sequences: before the memory they point into and their stream go)
+    h->fourier.pool.release();
     h->probe.pool.release();
     h->circ_pool.release();
     h->sym_pool.release();
@@ -1161,6 +1175,78 @@ int pe_hip_get_measures(pe_hip_engine* h, int first, int count, double* out)
             }
         }
     }
+    return PE_HIP_OK;
+}
+
+// ---------------- Fourier analysis of probes (pe_fourier.hpp; include/pe_hip.h)
+int pe_hip_set_fourier(pe_hip_engine* h, const pe_hip_fourier_control* c)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(!h->loaded || !h->probe.configured) return fail(h, PE_HIP_ERR_ARG, "set_fourier: no probe configuration (pe_hip_set_probes)");
+    if(c && c->n_probes < 0) return fail(h, PE_HIP_ERR_ARG, "set_fourier: negative count");
+    HIPCHK(h, hipSetDevice(h->device));
+    if(!c || c->n_probes == 0)
+    {
+        fourier_drop(h);
+        return PE_HIP_OK;
+    }
+    // everything is checked before anything changes: a refused configuration leaves the current one as it was
+    if(!c->probes) return fail(h, PE_HIP_ERR_ARG, "set_fourier: null array");
+    if(!std::isfinite(c->f0) || !(c->f0 > 0.0)) return fail(h, PE_HIP_ERR_ARG, "set_fourier: f0 must be finite and > 0");
+    if(!std::isfinite(c->t_start)) return fail(h, PE_HIP_ERR_ARG, "set_fourier: t_start must be finite");
+    if(c->n_periods < 1) return fail(h, PE_HIP_ERR_ARG, "set_fourier: n_periods must be >= 1");
+    if(c->n_harmonics < 1 || c->n_harmonics > 63) return fail(h, PE_HIP_ERR_ARG, "set_fourier: n_harmonics must be 1 .. 63");
+    if(h->probe.n_probes < 1) return fail(h, PE_HIP_ERR_ARG, "set_fourier: the probe configuration has no probes");
+    for(int p = 0; p < c->n_probes; ++p)
+        if(c->probes[p] < 0 || c->probes[p] >= h->probe.n_probes)
+            return fail(h, PE_HIP_ERR_ARG, "set_fourier: probe " + std::to_string(c->probes[p]) + " out of range");
+    double const t_end = c->t_start + static_cast<double>(c->n_periods) / c->f0;
+    if(!std::isfinite(t_end) || !(t_end > c->t_start)) return fail(h, PE_HIP_ERR_ARG, "set_fourier: t_start + n_periods / f0 is not a time after t_start");
+    long long const B = h->probe.batch, K = c->n_harmonics + 1;
+    long long n_items{}, n_doubles{}, n_bytes{};
+    if(__builtin_mul_overflow(B, static_cast<long long>(c->n_probes), &n_items) || __builtin_mul_overflow(n_items, K * 4, &n_doubles) ||
+       __builtin_mul_overflow(n_doubles, static_cast<long long>(sizeof(double)), &n_bytes) || static_cast<long long>(c->n_probes) * K > 0x7fffffffLL / 4)
+        return fail(h, PE_HIP_ERR_ARG, "set_fourier: batch x n_probes x (H + 1) x 4 overflows");
+    fourier_drop(h);
+    h->probe.armed = false;  // (like pe_hip_set_probes: a new configuration ends an armed window; arm again)
+    auto& F = h->fourier;
+    pe::FourierView& fv = F.fv;
+    fv.H = c->n_harmonics;
+    fv.w0 = 6.283185307179586476925286766559 * c->f0;
+    fv.t_start = c->t_start;
+    fv.t_end = t_end;
+    hipError_t e = F.pool.upload(fv.probes, std::vector<int>(c->probes, c->probes + c->n_probes));
+    if(e == hipSuccess) e = F.pool.alloc(fv.acc, static_cast<size_t>(n_doubles));
+    if(e == hipSuccess) e = F.pool.alloc(fv.cov, static_cast<size_t>(B));
+    if(e == hipSuccess) e = F.pool.alloc(F.out_coef, static_cast<size_t>(n_doubles), false);
+    if(e == hipSuccess) e = F.pool.alloc(F.out_thd, static_cast<size_t>(n_items), false);
+    fv.n_fp = c->n_probes;
+    if(e == hipSuccess) e = F.pool.upload(F.dev, std::vector<pe::FourierView>{fv});
+    if(e != hipSuccess)
+    {
+        fourier_drop(h);
+        HIPCHK(h, e);
+    }
+    F.n_fp = c->n_probes;
+    F.H = c->n_harmonics;
+    F.configured = true;
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_fourier(pe_hip_engine* h, int first, int count, double* coef, double* thd, double* covered)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    auto const& F = h->fourier;
+    if(!h->loaded || !F.configured) return fail(h, PE_HIP_ERR_ARG, "get_fourier: no Fourier configuration (pe_hip_set_fourier)");
+    if(first < 0 || count < 0 || first + count > h->probe.batch) return fail(h, PE_HIP_ERR_ARG, "get_fourier: instance range");
+    if(count == 0) return PE_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    size_t const f = static_cast<size_t>(first), n = static_cast<size_t>(count), np = static_cast<size_t>(F.n_fp), K4 = (static_cast<size_t>(F.H) + 1) * 4;
+    if(coef || thd) HIPCHK(h, pe::launch_fourier_finish(h->stream, F.fv, first, count, F.out_coef + f * np * K4, F.out_thd + f * np));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if(coef) HIPCHK(h, hipMemcpy(coef, F.out_coef + f * np * K4, n * np * K4 * sizeof(double), hipMemcpyDeviceToHost));
+    if(thd) HIPCHK(h, hipMemcpy(thd, F.out_thd + f * np, n * np * sizeof(double), hipMemcpyDeviceToHost));
+    if(covered) HIPCHK(h, hipMemcpy(covered, F.fv.cov + f, n * sizeof(double), hipMemcpyDeviceToHost));
     return PE_HIP_OK;
 }
 

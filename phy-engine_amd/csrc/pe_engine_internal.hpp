@@ -141,6 +141,17 @@ struct pe_hip_engine
         int* pin_accept{};         // pinned staging of the split schedule's accepted set
         size_t pin_cap{};
     } probe;
+    // Fourier analysis of probes (pe_hip_set_fourier, pe_fourier.hpp): rides on the probe configuration and its armed window; dropped with it
+    struct Fourier
+    {
+        Pool pool;
+        bool configured{};
+        int n_fp{}, H{};
+        pe::FourierView fv{};      // device buffers (the host's copy: k_fourier_finish takes it by value)
+        pe::FourierView const* dev{};  // the same in device memory: what probe_view hands to the recording launches
+        double* out_coef{};        // [batch][n_fp][H + 1][4] result of k_fourier_finish
+        double* out_thd{};         // [batch][n_fp]
+    } fourier;
     // variable-step transient (pe_hip_analyze_tr_adaptive, pe_lte.hpp): the shadow copy of the state of a step, the history ring and the
     // result slots (allocated at the first adaptive call, dropped by a circuit load), the history's host side, and the step log of the last call
     struct TrAdaptive
@@ -381,7 +392,8 @@ namespace pe_eng PE_ENG_HIDDEN
     // pe_engine.cpp: transient probes
     pe::ProbedView probe_view(pe_hip_engine const* h);  // the engine's view + its armed window (probe_armed set)
     void probe_disarm(pe_hip_engine* h);             // whatever moves x or t other than pe_hip_analyze_tr ends the window (samples stay)
-    void probe_drop(pe_hip_engine* h);               // configuration and buffers gone (pe_hip_load_circuit)
+    void probe_drop(pe_hip_engine* h);               // configuration and buffers gone (pe_hip_load_circuit); the Fourier configuration with it
+    void fourier_drop(pe_hip_engine* h);             // the Fourier configuration and its buffers gone
     int probe_record_step(pe_hip_engine* h, std::vector<int> const& accepted, double t);  // split schedule: one solved step
     // pe_engine_checkpoint.cpp: every array that makes up the state of an instance, in the order of the checkpoint blob -- shared with the
     // variable-step transient's device-side snapshot so that the two cannot drift

@@ -671,13 +671,23 @@ namespace pe
     }
     hipError_t launch_probe_arm(hipStream_t, ProbedView const& V)
     {
-        for(int b = 0; b < V.batch; ++b) probe_arm(ProbeHostTeam{}, V, b);
+        for(int b = 0; b < V.batch; ++b)
+        {
+            probe_arm(ProbeHostTeam{}, V, b);
+            if(V.fo) fourier_arm(ProbeHostTeam{}, V, b);
+        }
         return hipSuccess;
     }
     hipError_t launch_probe_record(hipStream_t, ProbedView const& V, double t)
     {
         for(int b = 0; b < V.batch; ++b)
             if(V.pr.accept[b]) probe_record(ProbeHostTeam{}, V, b, t);
+        return hipSuccess;
+    }
+    hipError_t launch_fourier_finish(hipStream_t, FourierView const& F, int first, int count, double* coef, double* thd)
+    {
+        for(long long i = 0; i < static_cast<long long>(count) * F.n_fp; ++i)
+            fourier_finish(F, first + static_cast<int>(i / F.n_fp), static_cast<int>(i % F.n_fp), coef + i * (F.H + 1) * 4, thd + i);
         return hipSuccess;
     }
     // ... and those of the variable-step transient (pe_lte.hpp)

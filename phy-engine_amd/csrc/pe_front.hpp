@@ -1689,8 +1689,9 @@ namespace pe
 
     // TR loop of circult::analyze (circuit.h:242-254) for `nsteps` steps of one instance.  PROBES (View = ProbedView): every accepted step
     // is recorded into the armed probe window V.pr (pe_probe.hpp) -- a separate instantiation, so that the probe-less resident kernel stays
-    // as it was.
-    template <class Team, bool PROBES, class View>
+    // as it was.  FOURIER: the recording also feeds the Fourier accumulators of V.fo (pe_fourier.hpp) -- again an instantiation of its own:
+    // inlined beside the solve, its two sincos calls cost the resident kernel scratch, which the users of probes alone do not pay.
+    template <class Team, bool PROBES, bool FOURIER = false, class View>
     PE_DEV void tr_steps_run(Team const& tm, View const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
     {
         if(V.status[b] != ST_OK) return;
@@ -1718,7 +1719,7 @@ namespace pe
             }
             ++steps;
             iters += it;
-            if constexpr(PROBES) probe_record(tm, V, b, t);
+            if constexpr(PROBES) probe_record<FOURIER>(tm, V, b, t);
         }
         tm.sync();
         if(tm.tid() == 0)
@@ -1735,7 +1736,13 @@ namespace pe
     template <class Team>
     PE_DEV void tr_steps(Team const& tm, DevView const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
     {
-        if(V.probe_armed) tr_steps_run<Team, true>(tm, static_cast<ProbedView const&>(V), b, dt, nsteps, reuse_factor, lds);
+        if(V.probe_armed)
+        {
+            ProbedView const& P = static_cast<ProbedView const&>(V);
+            if(P.fo) tr_steps_run<Team, true, true>(tm, P, b, dt, nsteps, reuse_factor, lds);
+            else
+                tr_steps_run<Team, true>(tm, P, b, dt, nsteps, reuse_factor, lds);
+        }
         else
             tr_steps_run<Team, false>(tm, V, b, dt, nsteps, reuse_factor, lds);
     }

@@ -582,6 +582,16 @@ namespace pe
         tr_steps_run<HipTeam, PROBES>(tm, V, b, dt, nsteps, reuse_factor != 0, pe_lds);
     }
 
+    // ... and the one that also accumulates the Fourier analysis of the probes (V.fo set: pe_fourier.hpp)
+    template <int MINW>
+    __global__ void __launch_bounds__(PE_THREADS, MINW) k_tr_steps_fourier(ProbedView V, double dt, int nsteps, int reuse_factor)
+    {
+        int const b = static_cast<int>(blockIdx.x);
+        if(b >= V.batch) return;
+        HipTeam tm;
+        tr_steps_run<HipTeam, true, true>(tm, V, b, dt, nsteps, reuse_factor != 0, pe_lds);
+    }
+
     template <int MINW>
     __global__ void __launch_bounds__(PE_THREADS, MINW) k_dc_point(DevView V, int mode)
     {
@@ -1098,7 +1108,8 @@ namespace pe
         size_t const lds = static_cast<size_t>(V.lds_doubles) * sizeof(double);
         if(V.probe_armed)  // (the view is the DevView part of a ProbedView: pe_engine.cpp probe_view)
         {
-            auto const fn = V.high_occupancy ? &k_tr_steps<4, true> : &k_tr_steps<2, true>;
+            bool const fourier = static_cast<ProbedView const&>(V).fo != nullptr;
+            auto const fn = fourier ? (V.high_occupancy ? &k_tr_steps_fourier<4> : &k_tr_steps_fourier<2>) : (V.high_occupancy ? &k_tr_steps<4, true> : &k_tr_steps<2, true>);
             hipError_t e = set_lds(reinterpret_cast<void const*>(fn), lds);
             if(e != hipSuccess) return e;
             hipLaunchKernelGGL(fn, dim3(V.batch), dim3(V.n_waves * 64), lds, st, static_cast<ProbedView const&>(V), dt, nsteps, reuse ? 1 : 0);
@@ -1533,6 +1544,7 @@ namespace pe
     __global__ void __launch_bounds__(64) k_probe_arm(ProbedView V)
     {
         probe_arm(HipTeam{}, V, static_cast<int>(blockIdx.x));
+        if(V.fo) fourier_arm(HipTeam{}, V, static_cast<int>(blockIdx.x));
     }
     // the split schedule's step at time t has been solved: the instances the host accepted (V.pr.accept) record it
     __global__ void __launch_bounds__(64) k_probe_record(ProbedView V, double t)
@@ -1551,6 +1563,20 @@ namespace pe
     {
         if(V.batch <= 0) return hipSuccess;
         hipLaunchKernelGGL(k_probe_record, dim3(V.batch), dim3(64), 0, st, V, t);
+        return hipGetLastError();
+    }
+    // ---- Fourier analysis of probes (pe_fourier.hpp): one lane per (instance, configured probe) of [first, first + count), k ascending
+    __global__ void __launch_bounds__(64) k_fourier_finish(FourierView F, int first, int count, double* __restrict__ coef, double* __restrict__ thd)
+    {
+        long long const i = static_cast<long long>(blockIdx.x) * 64 + threadIdx.x;
+        if(i >= static_cast<long long>(count) * F.n_fp) return;
+        fourier_finish(F, first + static_cast<int>(i / F.n_fp), static_cast<int>(i % F.n_fp), coef + i * (F.H + 1) * 4, thd + i);
+    }
+    hipError_t launch_fourier_finish(hipStream_t st, FourierView const& F, int first, int count, double* coef, double* thd)
+    {
+        long long const n = static_cast<long long>(count) * F.n_fp;
+        if(n <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_fourier_finish, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, st, F, first, count, coef, thd);
         return hipGetLastError();
     }
 

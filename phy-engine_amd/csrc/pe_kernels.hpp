@@ -60,6 +60,8 @@ namespace pe
     // The engine's translation unit pe_engine_newton.cpp holds a serial host definition of both for builds without HIP (the emulation library).
     hipError_t launch_probe_arm(hipStream_t st, ProbedView const& V);
     hipError_t launch_probe_record(hipStream_t st, ProbedView const& V, double t);
+    // Fourier analysis of probes (pe_fourier.hpp): coefficients [count][n_fp][H + 1][4] and THD [count][n_fp] of the instances from `first`
+    hipError_t launch_fourier_finish(hipStream_t st, FourierView const& F, int first, int count, double* coef, double* thd);
     // frequency-batched AC sweep (pe_ac_sweep.hpp): V is the view of the sweep's AC engine, whose instance b * S.P + p is circuit instance b at
     // point p of the pass.  fill: the value vector of every instance from the base vectors and S.omega.  residual_each: r = b0 - A xacc into
     // the right-hand-side slots, S.worst[q] per instance and *S.n_above = instances above the refinement threshold (NaN counts).

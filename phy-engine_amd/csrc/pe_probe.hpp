@@ -21,6 +21,7 @@
         #define PE_DEV inline
     #endif
 #endif
+#include "pe_fourier.hpp"  // (after PE_DEV)
 
 namespace pe
 {
@@ -106,7 +107,8 @@ namespace pe
 
     // an accepted TR step of an armed instance, solution x at time t1: every measure sees it; every stride-th one since arming is
     // appended as a sample while there is room, else counted in n_drop.  x must be complete (behind a team barrier) on entry.
-    template <class Team>
+    // FOURIER = false compiles the Fourier analysis out: the resident kernel of the probes alone is the code it was before there was one.
+    template <bool FOURIER = true, class Team>
     PE_DEV void probe_record(Team const& tm, ProbedView const& V, int b, double t1)
     {
         ProbeView const& P = V.pr;
@@ -123,6 +125,8 @@ namespace pe
             int const p = P.m_desc[4 * m + 1];
             measure_update(P, m, P.ms + (static_cast<long long>(b) * P.n_meas + m) * 2, t0, last[2 + p], t1, x[P.rows[p]]);
         }
+        if constexpr(FOURIER)
+            if(V.fo) fourier_record(tm, V, b, t0, t1);  // (sees every accepted step, whatever stride and capacity keep of it)
         tm.sync();  // (every lane has read the last point and the cursor before they move on)
         double* sv = P.v + (static_cast<long long>(b) * P.capacity + slot) * np;
         for(int p = tm.tid(); p < np; p += tm.size())

@@ -25,6 +25,7 @@ struct pe_hip_sweep
     bool loaded{};
     int n_probes{}, n_meas{}, capacity{};  // transient probes: the configuration every engine holds (read-back sizes)
     bool probes{};
+    int four_np{}, four_h{};  // Fourier analysis: configured probes and harmonics on every engine (four_np == 0: none)
     std::string err;
 };
 
@@ -148,6 +149,7 @@ int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int 
     s->rows = n_nodes + n_branches;
     s->loaded = false;
     s->probes = false;  // (a circuit load drops every engine's probe configuration)
+    s->four_np = s->four_h = 0;
     int const rc = for_each_engine(s,
                                    [&](int g)
                                    {
@@ -317,6 +319,7 @@ int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int 
         return PE_HIP_ERR_ARG;
     }
     int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_probes(s->eng[g], n_probes, rows, capacity, stride, n_measures, m); });
+    if(rc == PE_HIP_OK) s->four_np = s->four_h = 0;  // (a probe configuration drops the Fourier one)
     if(rc != PE_HIP_OK)
     {
         // an argument error is refused by every engine alike (nothing changed); anything else leaves the engines unequal: drop them all
@@ -325,6 +328,7 @@ int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int 
             for(size_t g = 0; g < s->eng.size(); ++g)
                 if(s->hi[g] > s->lo[g]) (void)pe_hip_set_probes(s->eng[g], 0, nullptr, 0, 0, 0, nullptr);
             s->probes = false;
+            s->four_np = s->four_h = 0;
         }
         return rc;
     }
@@ -374,6 +378,51 @@ int pe_hip_sweep_get_measures(pe_hip_sweep* s, int first_instance, int count, do
         int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
         if(b <= a) continue;
         if(int const rc = pe_hip_get_measures(s->eng[g], a - s->lo[g], b - a, out ? out + static_cast<size_t>(a - first_instance) * M * 2 : nullptr); rc != PE_HIP_OK)
+        {
+            s->err = pe_hip_last_error(s->eng[g]);
+            return rc;
+        }
+    }
+    return PE_HIP_OK;
+}
+
+// Fourier analysis of the probes: the same configuration on every engine, results concatenated in instance order
+int pe_hip_sweep_set_fourier(pe_hip_sweep* s, const pe_hip_fourier_control* c)
+{
+    if(!s || !s->loaded || !s->probes)
+    {
+        if(s) s->err = "set_fourier: no probe configuration";
+        return PE_HIP_ERR_ARG;
+    }
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_fourier(s->eng[g], c); });
+    if(rc != PE_HIP_OK)
+    {
+        // an argument error is refused by every engine alike (nothing changed); anything else leaves the engines unequal: drop it on all
+        if(rc != PE_HIP_ERR_ARG)
+        {
+            for(size_t g = 0; g < s->eng.size(); ++g)
+                if(s->hi[g] > s->lo[g]) (void)pe_hip_set_fourier(s->eng[g], nullptr);
+            s->four_np = s->four_h = 0;
+        }
+        return rc;
+    }
+    bool const on = c && c->n_probes > 0;
+    s->four_np = on ? c->n_probes : 0;
+    s->four_h = on ? c->n_harmonics : 0;
+    return PE_HIP_OK;
+}
+
+int pe_hip_sweep_get_fourier(pe_hip_sweep* s, int first_instance, int count, double* coef, double* thd, double* covered)
+{
+    if(!s || !s->loaded || !s->probes || s->four_np == 0 || first_instance < 0 || count < 0 || first_instance + count > s->batch) return PE_HIP_ERR_ARG;
+    size_t const np = static_cast<size_t>(s->four_np), K4 = (static_cast<size_t>(s->four_h) + 1) * 4;
+    for(size_t g = 0; g < s->eng.size(); ++g)
+    {
+        int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
+        if(b <= a) continue;
+        size_t const o = static_cast<size_t>(a - first_instance);
+        if(int const rc = pe_hip_get_fourier(s->eng[g], a - s->lo[g], b - a, coef ? coef + o * np * K4 : nullptr, thd ? thd + o * np : nullptr, covered ? covered + o : nullptr);
+           rc != PE_HIP_OK)
         {
             s->err = pe_hip_last_error(s->eng[g]);
             return rc;

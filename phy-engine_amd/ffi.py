@@ -31,6 +31,7 @@ EXPORTS = [
     "pe_hip_sweep_load_circuit", "pe_hip_sweep_reset", "pe_hip_sweep_operating_point", "pe_hip_sweep_run", "pe_hip_sweep_reduce", "pe_hip_sweep_get_solution",
     "pe_hip_sweep_get_instance_state", "pe_hip_set_probes", "pe_hip_arm_probes", "pe_hip_get_probe_samples", "pe_hip_get_measures",
     "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
+    "pe_hip_set_fourier", "pe_hip_get_fourier", "pe_hip_sweep_set_fourier", "pe_hip_sweep_get_fourier",
     "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_get_sens_params", "pe_hip_analyze_sens", "pe_hip_get_sens",
@@ -78,6 +79,11 @@ class Measure(C.Structure):
     _fields_ = [("kind", C.c_int), ("probe", C.c_int), ("edge", C.c_int), ("occurrence", C.c_int), ("level", C.c_double)]
 
 
+class FourierControl(C.Structure):
+    _fields_ = [("f0", C.c_double), ("t_start", C.c_double), ("n_periods", C.c_int), ("n_harmonics", C.c_int), ("n_probes", C.c_int),
+                ("probes", C.POINTER(C.c_int))]
+
+
 def _measures(measures):
     """measures: (kind, probe[, level, edge, occurrence]) tuples or dicts with those keys; kind a MEAS_* value or its name ('min', 'cross', ...)."""
     ms = list(measures)
@@ -102,12 +108,15 @@ def _probe_argtypes(l, prefix):
     getattr(l, prefix + "get_probe_samples").argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
                                                 C.POINTER(C.c_longlong)]
     getattr(l, prefix + "get_measures").argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    getattr(l, prefix + "set_fourier").argtypes = [C.c_void_p, C.POINTER(FourierControl)]
+    getattr(l, prefix + "get_fourier").argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
 
 
 class _Probes:
     """set_probes / arm_probes / probe_samples / measures, shared by Engine and Sweep (prefix pe_hip_ / pe_hip_sweep_)."""
     _prefix = "pe_hip_"
     _probe_cfg = (0, 0, 0)  # n_probes, capacity, n_measures
+    _four_cfg = (0, 0)      # configured probes, harmonics
 
     def set_probes(self, rows, capacity, stride=1, measures=()):
         """record x[rows] of every instance at every stride-th accepted transient step of an armed window (room for `capacity` samples)
@@ -116,6 +125,7 @@ class _Probes:
         n_m, arr = _measures(measures)
         self._chk(getattr(lib(), self._prefix + "set_probes")(self._h, len(r), _ip(r), int(capacity), int(stride), n_m, arr))
         self._probe_cfg = (len(r), int(capacity), n_m) if (len(r) or n_m) else (0, 0, 0)
+        self._four_cfg = (0, 0)  # (a probe configuration drops the Fourier one)
 
     def arm_probes(self):
         self._chk(getattr(lib(), self._prefix + "arm_probes")(self._h))
@@ -138,6 +148,30 @@ class _Probes:
         out = np.empty((count, self._probe_cfg[2], 2))
         self._chk(getattr(lib(), self._prefix + "get_measures")(self._h, int(first), int(count), _dp(out)))
         return out
+
+    def set_fourier(self, f0=None, t_start=0.0, n_periods=1, n_harmonics=9, probes=()):
+        """harmonics 0 .. n_harmonics of f0 over [t_start, t_start + n_periods / f0] of the probes `probes` (indices into the probe list),
+        accumulated on the device at every accepted step of an armed window (include/pe_hip.h); probes=() removes the analysis.  Ends an
+        armed window like set_probes: arm again."""
+        p = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        fn = getattr(lib(), self._prefix + "set_fourier")
+        if len(p) == 0:
+            self._chk(fn(self._h, None))
+            self._four_cfg = (0, 0)
+            return
+        c = FourierControl(float(f0), float(t_start), int(n_periods), int(n_harmonics), len(p), _ip(p))
+        self._chk(fn(self._h, C.byref(c)))
+        self._four_cfg = (len(p), int(n_harmonics))
+
+    def fourier(self, first=0, count=None):
+        """(coef [count][n_probes][H + 1][4] = a, b, amp, phase; thd [count][n_probes]; covered [count]) -- NaN where nothing was integrated"""
+        count = self.batch - first if count is None else count
+        n_p, H = self._four_cfg
+        coef = np.empty((count, n_p, H + 1, 4))
+        thd = np.empty((count, n_p))
+        cov = np.empty(count)
+        self._chk(getattr(lib(), self._prefix + "get_fourier")(self._h, int(first), int(count), _dp(coef), _dp(thd), _dp(cov)))
+        return coef, thd, cov
 
 
 class RunStats(C.Structure):
@@ -460,6 +494,7 @@ class Engine(_Probes):
         self.rows = n_nodes + n_branches
         self.batch = batch
         self._probe_cfg = (0, 0, 0)  # (a load drops the probe configuration)
+        self._four_cfg = (0, 0)
         self._ac_rows = None         # (... and the row selection of AC sweeps)
         self._dc_rows = None         # (... and of DC sweeps)
 
@@ -935,6 +970,7 @@ class Sweep(_Probes):
         self._chk(lib().pe_hip_sweep_load_circuit(self._h, int(n_nodes), int(n_br), int(batch), len(tables), arr))
         self.rows, self.batch = n_nodes + n_br, batch
         self._probe_cfg = (0, 0, 0)
+        self._four_cfg = (0, 0)
 
     def shards(self):
         out = []

@@ -1462,6 +1462,46 @@ namespace phy_engine
             return true;
         }
 
+        // Fourier analysis of a node voltage over a transient (pe_hip_set_fourier / pe_hip_get_fourier, include/pe_hip.h): harmonics
+        // 0 .. n_harmonics of f0 over [t_start, t_start + n_periods / f0] (absolute simulation time) and the total harmonic distortion,
+        // accumulated on the device at every accepted step.  set_fourier prepares the circuit for a transient, makes `probe` the one probe of
+        // the engine (replacing any probe configuration made on gpu_engine()) and opens the window at the current point; the analyze()
+        // calls that follow (TR / TROP, same topology) are integrated.  get_fourier reads fourier_results[k] = {a, b, amp, phase},
+        // fourier_thd and fourier_covered (compare it with n_periods / f0); NaN while nothing has been integrated.
+        struct fourier_harmonic
+        {
+            double a{}, b{}, amp{}, phase{};
+        };
+        ::std::vector<fourier_harmonic> fourier_results{};
+        double fourier_thd{}, fourier_covered{};
+        [[nodiscard]] bool set_fourier(::phy_engine::model::node_t const& probe, double f0, double t_start, int n_periods, int n_harmonics) noexcept
+        {
+            fourier_results.clear();
+            auto const saved = at;
+            at = analyze_type::TR;
+            bool const prepared = prepare();
+            at = saved;
+            if(!prepared || !gpu_ || !loaded_) return false;
+            if(&probe == &nl.ground_node)
+            {
+                last_error = "set_fourier: the probe is the ground node";
+                return false;
+            }
+            int const row = static_cast<int>(probe.node_index), index = 0;
+            pe_hip_fourier_control const ctl{f0, t_start, n_periods, n_harmonics, 1, &index};
+            if(pe_hip_set_probes(gpu_, 1, &row, 1, 1, 0, nullptr) != PE_HIP_OK || pe_hip_set_fourier(gpu_, &ctl) != PE_HIP_OK || pe_hip_arm_probes(gpu_) != PE_HIP_OK)
+                return gpu_fail();
+            fourier_results.resize(static_cast<::std::size_t>(n_harmonics) + 1);
+            return true;
+        }
+        [[nodiscard]] bool get_fourier() noexcept
+        {
+            if(!gpu_ || !loaded_ || fourier_results.empty()) return false;
+            static_assert(sizeof(fourier_harmonic) == 4 * sizeof(double));
+            if(pe_hip_get_fourier(gpu_, 0, 1, &fourier_results[0].a, &fourier_thd, &fourier_covered) != PE_HIP_OK) return gpu_fail();
+            return true;
+        }
+
         // one AC solve (solve_once with iterate_ac): phasors scattered into the nodes / branches as complex values
         bool solve_ac_point(double omega) noexcept
         {
