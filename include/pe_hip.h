@@ -285,7 +285,9 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
  *     - LTE test, once three accepted points are in the history: err_r = h^3 / 2 |DD3_r| (third divided difference over those points and
  *       the candidate x*), tol_r = trtol (lte_reltol max(|x*_r|, |x_n,r|) + abstol), q = max err_r / tol_r over all rows of all instances.
  *       q > 1 (or not a number) and h > dt_min: roll back, dt = h max(0.1, 0.9 q^(-1/3)) (outcome 1); at dt_min the step is accepted and
- *       counted in n_at_dt_min.
+ *       counted in n_at_dt_min.  That estimate and the exponent 1/3 are the trapezoidal rule's (error h^3 / 12 times the third derivative).
+ *       Under pe_hip_set_tr_method (below) they become: PE_HIP_TR_BE err_r = h^2 |DD2_r| over the last two points and the candidate, exponent
+ *       1/2; PE_HIP_TR_GEAR2 err_r = h^3 (1 + rho)^2 / (rho (1 + 2 rho)) |DD3_r| with rho = h / (t2 - t1), exponent 1/3.
  *     - accepted (outcome 0): dt = h min(2, 0.9 q^(-1/3)) if the step was tested, else dt = h.  A step that reached a breakpoint other
  *       than t_stop restarts the history at that point and continues with dt = dt_init.
  *   The history (three previous solutions per instance, device memory of the engine) is empty at the first adaptive call and after
@@ -795,6 +797,46 @@ typedef struct pe_hip_fourier_control
 int pe_hip_set_fourier(pe_hip_engine* h, const pe_hip_fourier_control* c);
 int pe_hip_get_fourier(pe_hip_engine* h, int first_instance, int count, double* coef, double* thd, double* covered);
 
+/* ---- Integration rule of the transient (SPICE method=trap / gear, a backward-Euler step).  The trapezoidal rule is A-stable but not
+ * L-stable: on a stiff element hit by an edge its amplification factor tends to -1 and the element's voltage or current alternates in
+ * sign step after step.  Backward Euler (first order) and the variable-step second-order Gear rule (BDF2) damp such an element at once.
+ *   For a step from t_n to t_n + h, with h_p the accepted step that led to t_n and rho = h / h_p, the derivative at the new point is
+ *   a0 y_{n+1} + a1 y_n + a2 y_{n-1}:
+ *                      BE     a0 = 1 / h                         a1 = -1 / h           a2 = 0
+ *                      GEAR2  a0 = (1 + 2 rho) / (h (1 + rho))   a1 = -(1 + rho) / h   a2 = rho^2 / (h (1 + rho))
+ *   A GEAR2 step takes the BE coefficients, decided per instance on the device, when the instance has no second point (h_p = 0) or when
+ *   rho > 1 + sqrt 2, the zero-stability limit of variable-step BDF2.  Capacitors, inductors and coupled inductors get the companion of
+ *   the rule.  The diffusion capacitance of a junction is cd = tt geq of the last linearisation, FROZEN at the start of the step as it is
+ *   for the trapezoidal rule, under the same guards: companion conductance a0 cd, history cd (a1 vd_n + a2 vd_{n-1}).
+ *   pe_hip_set_tr_method  an engine setting like the options: allowed without a circuit, survives pe_hip_load_circuit.  The default is
+ *                      PE_HIP_TR_TRAP; an engine that never calls it, or sets TRAP, computes the bits it always computed and allocates
+ *                      nothing.  An unknown value is PE_HIP_ERR_ARG, engine unchanged.  Setting the current method again changes nothing;
+ *                      a different one restarts the integration history of every instance.
+ *   pe_hip_get_tr_history  h_prev [count]: per instance the step h_p that its second history point belongs to; 0: the next step starts the
+ *                      history (a BE step under GEAR2).  Reads 0 under TRAP.
+ *   The history restarts (h_p := 0 for every instance) at pe_hip_load_circuit, _reset, _analyze_dc and _analyze_op_stepping,
+ *   _set_solution, _set_time, _checkpoint_load of a blob without history, a method change, and inside pe_hip_analyze_tr_adaptive at every
+ *   breakpoint other than t_stop that a step reaches (the derivative jumps at a source corner: a two-step formula must not look across
+ *   it).  pe_hip_analyze_tr does NOT restart it: consecutive calls continue one trajectory, with whatever dt each call has.  An instance
+ *   whose step failed restarts its own history before its next step.
+ *   Variable-step controller (pe_hip_analyze_tr_adaptive).  The history rule (three accepted points before the test runs) and the
+ *   decisions are those of the trapezoidal rule (err_r = h^3 / 2 |DD3_r|, exponent 1/3); estimate and exponent become
+ *                      BE     err_r = h^2 |DD2_r| over the last two points and the candidate (the error is h^2 / 2 times the second
+ *                             derivative, which is about 2 DD2); rejection factor max(0.1, 0.9 q^(-1/2)), growth min(2, 0.9 q^(-1/2))
+ *                      GEAR2  err_r = h^3 (1 + rho)^2 / (rho (1 + 2 rho)) |DD3_r|, rho = h / (t2 - t1) (the error is
+ *                             h^3 (1 + rho)^2 / (6 rho (1 + 2 rho)) times the third derivative, which is about 6 DD3: 2/9 h^3 at rho = 1);
+ *                             exponent 1/3
+ *   The growth cap of 2 keeps rho below 1 + sqrt 2.  q travels as the NaN-preserving integer image of the maximum, as before.
+ *   Checkpoints.  Under TRAP a blob is "PEHIPCK2", byte for byte what it was.  Under BE / GEAR2 it is "PEHIPCK3": the same parts, then the
+ *   method and the history; a continued run is bit-identical to an uninterrupted one.  A "PEHIPCK2" blob loads under any method and
+ *   restarts the history; a "PEHIPCK3" blob loads only into an engine set to the blob's method (else PE_HIP_ERR_ARG).
+ *   A circuit with a host-stamp overlay integrates in its own host hooks: pe_hip_analyze_tr under a method other than TRAP is
+ *   PE_HIP_ERR_ARG, engine unchanged.  AC, noise, sensitivity, DC sweep and operating points do not depend on the method. */
+enum pe_hip_tr_method { PE_HIP_TR_TRAP = 0, PE_HIP_TR_BE = 1, PE_HIP_TR_GEAR2 = 2 };
+int pe_hip_set_tr_method(pe_hip_engine* h, int method);
+int pe_hip_get_tr_method(pe_hip_engine* h, int* method);
+int pe_hip_get_tr_history(pe_hip_engine* h, int first_instance, int count, double* h_prev);
+
 /* ---- Monte-Carlo / parameter sweep over several GPUs of one node (csrc/pe_sweep.cpp).
  * Independent instances of ONE topology are the natural shard of this path: the symbolic analysis is replicated per device, the
  * instances are dealt out in contiguous blocks of ceil(batch / G) per device -- the chunk rule of the reference's only
@@ -829,6 +871,8 @@ int pe_hip_sweep_get_measures(pe_hip_sweep* s, int first_instance, int count, do
 /* the Fourier analysis of every instance of the sweep: pe_hip_set_fourier on each device's engine, pe_hip_get_fourier in global instance order */
 int pe_hip_sweep_set_fourier(pe_hip_sweep* s, const pe_hip_fourier_control* c);
 int pe_hip_sweep_get_fourier(pe_hip_sweep* s, int first_instance, int count, double* coef, double* thd, double* covered);
+/* pe_hip_set_tr_method on every device's engine (allowed before pe_hip_sweep_load_circuit) */
+int pe_hip_sweep_set_tr_method(pe_hip_sweep* s, int method);
 /* iteration count of every step of instance 0 since the last reset (parity with the reference's Newton counts) */
 int pe_hip_get_newton_trace(pe_hip_engine* h, int capacity, int* iters, int* n_out);
 /* last stamped MNA system of one instance (CSR, sorted columns; vals/rhs may be NULL) */

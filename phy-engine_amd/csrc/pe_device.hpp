@@ -135,6 +135,8 @@ namespace pe
         long long* prof;     // [.][8] phase clocks (100 MHz ticks): eval+stamp, factor waves, factor coop, fwd waves, fwd+bwd coop, bwd waves, newton, companion
         int* trace;          // Newton iterations per step of instance 0
         int trace_cap;
+        int tr_method{};     // integration rule of the transient (pe_integ.hpp TR_TRAP / TR_BE / TR_GEAR2; pe_hip_set_tr_method).  (It sits in the
+                             // padding before trace_len: the offsets of the other fields are unchanged.)
         int* trace_len;
         long long factor_doubles, arena_doubles;
         // ---- symbolic (shared)
@@ -224,9 +226,13 @@ namespace pe
         double* rres;     // [.][rows]  residual b - A x (right-hand side of the correction solve)
         double* eta_acc;  // [.][4]     max |r_i|, max_i sum_j |a_ij|, max |x_i|, max |b_i| of the last solve (split schedule: atomic max)
         double residual_tol;  // <= 0: check disabled
+        // ---- BE / GEAR2 (pe_integ.hpp): [.][nC + nL + 2 nCl + nD + 1] values at t_{n-1} and the slot h_p; null while the method is TR_TRAP.
+        // (Last field: the kernels that never read it see the layout they always saw.)
+        double* tr_hist{};
     };
     // (the kernel argument of the probe-less kernels must keep its size: a larger DevView changes the register allocation of k_tr_steps)
     static_assert(offsetof(DevView, v_abstol) == offsetof(DevView, probe_armed) + sizeof(int), "probe_armed must fill the padding before v_abstol");
+    static_assert(offsetof(DevView, trace_len) == offsetof(DevView, tr_method) + sizeof(int), "tr_method must fill the padding before trace_len");
 
     // Static fronts of the lane-group kernel across the Newton iterations of one solve point (pe_symbolic.hpp "static fronts").
     // These tables ride next to the view, never in it (a larger DevView changes the register allocation of the resident kernels).

@@ -219,6 +219,11 @@ int finish_load(pe_hip_engine* h)
     apply_options(h, V);
     h->V = V;
     h->loaded = true;
+    if(int const irc = integ_alloc(h); irc != PE_HIP_OK)  // (the engine's integration rule survives the load; its history starts empty)
+    {
+        h->loaded = false;
+        return irc;
+    }
     // One dry run of the sweep's exchange step (statistics kernels + the asynchronous copy of their result into the pinned buffer) on the
     // zeroed solution: the first use of that path costs the runtime 7-8 ms (first asynchronous device-to-host copy of the stream: copy-queue
     // set-up; measured with scripts/r4_reduce_probe.py: 7.4 ms, then 0.07 ms) -- paid here, with the load, instead of on every rank's
@@ -248,6 +253,7 @@ void probe_disarm(pe_hip_engine* h)
 {
     h->probe.armed = false;
     h->tra.n_pts = 0;  // (whatever ends a probe window also restarts the history of the variable-step transient: x or t moved)
+    integ_restart(h);  // (... and that of the BE / GEAR2 rules: the next step has no second point)
 }
 void fourier_drop(pe_hip_engine* h)
 {
@@ -352,6 +358,7 @@ void pe_hip_destroy(pe_hip_engine* h)
     if(h->graphs) pe::m2_graphs_destroy(h->graphs);  // (captured launch sequences: before the memory they point into and their stream go)
     h->fourier.pool.release();
     h->probe.pool.release();
+    h->integ_pool.release();
     h->circ_pool.release();
     h->sym_pool.release();
     h->csr.pool.release();
@@ -400,6 +407,53 @@ int pe_hip_set_options(pe_hip_engine* h, const pe_hip_options* o)
         h->fact_valid = false;
         h->a_static.clear();
     }
+    return PE_HIP_OK;
+}
+
+int pe_hip_set_tr_method(pe_hip_engine* h, int method)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(method != PE_HIP_TR_TRAP && method != PE_HIP_TR_BE && method != PE_HIP_TR_GEAR2) return fail(h, PE_HIP_ERR_ARG, "set_tr_method: unknown integration method");
+    if(method == h->tr_method) return PE_HIP_OK;
+    int const before = h->tr_method;
+    h->tr_method = method;
+    if(!h->loaded)
+    {
+        h->V.tr_method = method;
+        return PE_HIP_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if(int const rc = integ_alloc(h); rc != PE_HIP_OK)
+    {
+        h->tr_method = before;
+        h->V.tr_method = before;
+        return rc;
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_tr_method(pe_hip_engine* h, int* method)
+{
+    if(!h || !method) return PE_HIP_ERR_ARG;
+    *method = h->tr_method;
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_tr_history(pe_hip_engine* h, int first_instance, int count, double* h_prev)
+{
+    if(!h || !h->loaded || !h_prev || first_instance < 0 || count < 0 || first_instance + count > h->hc.batch) return PE_HIP_ERR_ARG;
+    if(!h->V.tr_hist || h->tr_method == PE_HIP_TR_TRAP)
+    {
+        std::fill(h_prev, h_prev + count, 0.0);
+        return PE_HIP_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    size_t const stride = static_cast<size_t>(pe::integ_stride(h->V));
+    if(count > 0)
+        HIPCHK(h, hipMemcpy2D(h_prev, sizeof(double), h->V.tr_hist + static_cast<size_t>(first_instance) * stride + (stride - 1), stride * sizeof(double), sizeof(double),
+                              static_cast<size_t>(count), hipMemcpyDeviceToHost));
     return PE_HIP_OK;
 }
 
@@ -489,6 +543,9 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     probe_drop(h);                   // (a probe configuration belongs to the circuit: rows, batch)
     tr_adaptive_drop(h);             // (... and so do the shadow state and the history of the variable-step transient)
     op_step_drop(h);                 // (... and the controller arrays of the stepped operating point)
+    h->integ_pool.release();         // (... and the history of the BE / GEAR2 rules; the rule itself stays)
+    h->V.tr_hist = nullptr;
+    h->integ_hp = 0.0;
     h->circ_pool.release();
     h->stats_scratch = nullptr;
     h->stats_doubles = 0;

@@ -29,6 +29,7 @@
 #include "pe_dc_sweep.hpp"
 #include "pe_device.hpp"
 #include "pe_kernels.hpp"
+#include "pe_integ.hpp"
 #include "pe_lte.hpp"
 #include "pe_noise.hpp"
 #include "pe_op_step.hpp"
@@ -169,6 +170,15 @@ struct pe_hip_engine
         std::vector<double> log_dt;
         std::vector<int> log_outcome;
     } tra;
+    // integration rule of the transient (pe_hip_set_tr_method, pe_integ.hpp): an engine setting like the options -- it survives a circuit
+    // load.  The history array V.tr_hist lives in a pool of its own, allocated once a rule other than the trapezoidal one is in effect for a
+    // resident circuit (a trapezoidal user's memory is what it was).  integ_hp: the h_p that EVERY instance holds as far as the host can
+    // show (0 after a restart, the step after steps that every instance took); NaN when it cannot -- an instance failed or was stepped
+    // alone -- and then nothing that is keyed on the companion conductance a0 is reused.
+    int tr_method{};
+    Pool integ_pool;
+    double integ_hp{};
+    bool integ_failed{};  // some instance's last step failed under BE / GEAR2: its history restarts before its next step
     long long n_symbolic{};  // symbolic analyses of the resident circuit so far (ensure_symbolic)
     Pool circ_pool;  // topology, params, state
     Pool sym_pool;   // symbolic arrays + factor storage
@@ -403,6 +413,15 @@ namespace pe_eng PE_ENG_HIDDEN
         size_t bytes;
     };
     std::vector<CkPart> ck_parts(pe_hip_engine* h);
+    // pe_engine_newton.cpp: backward Euler / Gear-2
+    int integ_alloc(pe_hip_engine* h);    // V.tr_method := the engine's rule; the history array where that rule needs one (restarted); captured sequences dropped
+    void integ_restart(pe_hip_engine* h); // h_p := 0 of every instance: the next step starts the history
+    // what the bookkeeping of the companion conductances is keyed on: dt under the trapezoidal rule (2C/dt), a0 of the coming step otherwise
+    // (NaN, which equals nothing, when the host cannot show that every instance has the same); and the dt whose trapezoidal conductance
+    // 2C/dt equals a0 C, for the representative values of the pivot matching
+    int integ_before_steps(pe_hip_engine* h);  // the history of the instances whose last step failed restarts (before their status is cleared)
+    double integ_key(pe_hip_engine const* h, double dt);
+    double integ_sym_dt(pe_hip_engine const* h, double dt);
     // pe_engine_newton.cpp: variable-step transient
     void tr_adaptive_drop(pe_hip_engine* h);  // shadow state, history ring and step log gone (pe_hip_load_circuit)
     void op_step_drop(pe_hip_engine* h);      // controller arrays, shadow and log of the stepped operating point gone (pe_hip_load_circuit)

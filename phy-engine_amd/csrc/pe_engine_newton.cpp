@@ -486,14 +486,17 @@ namespace pe_eng PE_ENG_HIDDEN
                 }
             double const t = t_prev + dt;
             // linear circuit, same dt as the last factorisation: stamp + triangular solves only
-            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == dt;
+            // (what the companion conductances of this step are a function of: dt under the trapezoidal rule, a0 under BE / GEAR2 -- a GEAR2 step after
+            //  a restart has a0 = 1 / h, the following ones 3 / (2 h) at the same dt; NaN, equal to nothing, where the instances may differ)
+            double const key = integ_key(h, dt);
+            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == key;
             // The matrix of a transient step differs from the last step's only in its x-dependent slots while dt and the parameters stay (the
             // companion conductances 2C/dt, 2L/dt are constants of the step size): instances whose matrix holds a full stamp of this dt skip the
             // other 97 % of the matrix gather on the first iteration too (k_m2_stamp 0.56 -> 0.2 ms per time point at 1 024 instances).  The
             // set is cleared wherever a static value can change (a_static_invalidate: parameters, options, load, checkpoint, re-analysis,
             // any OP / DC / TROP solve -- they stamp other companions); knob STATIC_A=0: always the full stamp.
             static bool const static_a = env_int0("PHY_ENGINE_HIP_STATIC_A", 1) != 0;
-            bool a_static_ok = static_a && h->a_static_dt == dt && h->a_static.size() == static_cast<size_t>(B);
+            bool a_static_ok = static_a && h->a_static_dt == key && h->a_static.size() == static_cast<size_t>(B);
             for(int b = 0; b < B && a_static_ok; ++b)
                 if(S.active[b] && !h->a_static[static_cast<size_t>(b)]) a_static_ok = false;
             rc = m2_point(h, S, PE_HIP_MODE_TR, t, dt, !reuse, res, launches, (with_companion && !own_launch) ? &dt : nullptr, a_static_ok);
@@ -501,8 +504,8 @@ namespace pe_eng PE_ENG_HIDDEN
             {
                 // the first iteration of this step stamped everything for the instances that were active at its start (S.active is spent by now:
                 // the mask of the step is status OK && (!only || only[b]) -- recomputed)
-                if(h->a_static_dt != dt || h->a_static.size() != static_cast<size_t>(B)) h->a_static.assign(static_cast<size_t>(B), 0);
-                h->a_static_dt = dt;
+                if(h->a_static_dt != key || h->a_static.size() != static_cast<size_t>(B)) h->a_static.assign(static_cast<size_t>(B), 0);
+                h->a_static_dt = key;
                 for(int b = 0; b < B; ++b)
                     if(res[b] != 0) h->a_static[static_cast<size_t>(b)] = 1;  // (res != 0: the instance took part in this point)
             }
@@ -510,7 +513,14 @@ namespace pe_eng PE_ENG_HIDDEN
             if(may_reuse)
             {
                 h->fact_valid = true;
-                h->fact_dt = dt;
+                h->fact_dt = key;
+            }
+            if(h->tr_method != PE_HIP_TR_TRAP)
+            {
+                // every instance took this step and holds h_p = dt now, or the host no longer knows one h_p for all of them
+                bool all = !only;
+                for(int b = 0; b < B && all; ++b) all = S.status[b] == PE_HIP_OK && res[b] > 0;
+                h->integ_hp = all ? dt : std::nan("");
             }
             if(h->probe.armed) accepted.assign(B, 0);
             for(int b = 0; b < B; ++b)
@@ -709,6 +719,31 @@ namespace pe
         }
         return hipSuccess;
     }
+    // ... and those of the BE / GEAR2 rules (pe_integ.hpp)
+    hipError_t launch_tr_lte_integ(hipStream_t, DevView const& V, LteView const& L, int method)
+    {
+        *L.result = LteResult{};
+        for(int b = 0; b < V.batch; ++b)
+        {
+            int nonfinite = 0;
+            unsigned long long const u = integ_lte_partial(ProbeHostTeam{}, V, L, method, b, nonfinite);
+            if(L.test)
+            {
+                L.q_each[b] = u;
+                if(u > L.result->q) L.result->q = u;
+            }
+            L.result->n_nonfinite += nonfinite;
+            if(V.status[b] != 0) ++L.result->n_failed;
+            L.result->iters_spent += L.iters_now[b] - L.iters_before[b];
+        }
+        return hipSuccess;
+    }
+    hipError_t launch_integ_restart(hipStream_t, DevView const& V, bool only_failed)
+    {
+        if(!V.tr_hist) return hipSuccess;
+        for(int b = 0; b < V.batch; ++b) integ_restart(ProbeHostTeam{}, V, b, only_failed);
+        return hipSuccess;
+    }
     hipError_t launch_tr_history_push(hipStream_t, DevView const& V, double* hist, int slot)
     {
         lte_history_push(ProbeHostTeam{}, V, hist, slot);
@@ -768,10 +803,14 @@ namespace pe_eng PE_ENG_HIDDEN
             done = nsteps;
         }
         if(done < nsteps) h->a_static.clear();  // (the resident kernel stamps the matrix itself: what the split schedule knew about it is void)
+        bool const integ = h->tr_method != PE_HIP_TR_TRAP;
         while(done < nsteps)
         {
-            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == dt;
-            int const n = reuse || !may_reuse ? std::min(chunk, nsteps - done) : 1;  // first step factors, the rest may reuse
+            double const key = integ_key(h, dt);
+            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == key;
+            int n = reuse || !may_reuse ? std::min(chunk, nsteps - done) : 1;  // first step factors, the rest may reuse
+            // (GEAR2: one launch reuses one factorisation -- a step whose a0 is not that of the steps behind it, the first after a restart, goes alone)
+            if(integ && reuse && !(h->integ_hp == dt)) n = 1;
             if(h->probe.armed)
             {
                 pe::ProbedView const pv = probe_view(h);
@@ -784,8 +823,9 @@ namespace pe_eng PE_ENG_HIDDEN
             if(may_reuse)
             {
                 h->fact_valid = true;
-                h->fact_dt = dt;
+                h->fact_dt = key;
             }
+            if(integ) h->integ_hp = dt;  // (put right below should an instance have failed)
         }
         for(int attempt = 0; attempt < 2; ++attempt)
         {
@@ -794,13 +834,87 @@ namespace pe_eng PE_ENG_HIDDEN
             rc = prepare_inaccurate_retry(h, true, dt, attempt, s0, nsteps, groups);
             if(rc != PE_HIP_OK) return rc;
             if(groups.empty()) break;
+            if(integ) h->integ_hp = std::nan("");  // (instances stepped alone)
             for(auto const& g: groups)
             {
                 rc = run_m2_tr(h, dt, g.first, launches, &g.second);
                 if(rc != PE_HIP_OK) return rc;
             }
         }
+        if(integ && nsteps > 0)
+        {
+            // every instance that is OK has taken its nsteps steps of dt: h_p = dt.  One that failed holds the point its failed step stored:
+            // its history restarts before its next step (integ_before_steps), and until then the host knows no common h_p
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            std::vector<int> status(static_cast<size_t>(h->hc.batch));
+            HIPCHK(h, hipMemcpy(status.data(), h->V.status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
+            bool const all_ok = std::all_of(status.begin(), status.end(), [](int v) { return v == PE_HIP_OK; });
+            h->integ_hp = all_ok ? dt : std::nan("");
+            if(!all_ok) h->integ_failed = true;
+        }
         return PE_HIP_OK;
+    }
+
+    // before the status of the instances is cleared for new steps: the history of the instances whose last step failed restarts
+    int integ_before_steps(pe_hip_engine* h)
+    {
+        if(h->tr_method == PE_HIP_TR_TRAP || !h->integ_failed) return PE_HIP_OK;
+        HIPCHK(h, pe::launch_integ_restart(h->stream, h->V, true));
+        h->integ_failed = false;
+        h->integ_hp = std::nan("");
+        h->fact_valid = false;
+        h->a_static.clear();
+        return PE_HIP_OK;
+    }
+
+    int integ_alloc(pe_hip_engine* h)
+    {
+        h->V.tr_method = h->tr_method;
+        if(!h->loaded) return PE_HIP_OK;
+        // whatever was keyed on the other rule's companion conductances is void; captured launch sequences hold the old view; the snapshot
+        // table of the variable-step transient is built again, with or without the history array
+        h->fact_valid = false;
+        h->a_static.clear();
+        h->sym_dt = 0.0;
+        pe::m2_graphs_clear(h->graphs);
+        tr_adaptive_drop(h);
+        h->integ_failed = false;
+        h->integ_hp = 0.0;
+        if(h->tr_method == PE_HIP_TR_TRAP)
+        {
+            h->integ_pool.release();
+            h->V.tr_hist = nullptr;
+            return PE_HIP_OK;
+        }
+        if(!h->V.tr_hist) HIPCHK(h, h->integ_pool.alloc(h->V.tr_hist, static_cast<size_t>(h->hc.batch) * static_cast<size_t>(pe::integ_stride(h->V))));
+        integ_restart(h);
+        return PE_HIP_OK;
+    }
+
+    void integ_restart(pe_hip_engine* h)
+    {
+        if(!h->loaded || !h->V.tr_hist) return;
+        (void)pe::launch_integ_restart(h->stream, h->V, false);
+        (void)hipStreamSynchronize(h->stream);  // (the calls that restart go on with blocking copies)
+        h->integ_failed = false;
+        h->integ_hp = 0.0;
+        if(h->tr_method != PE_HIP_TR_TRAP)
+        {
+            h->fact_valid = false;  // (the a0 of the coming step is another)
+            h->a_static.clear();
+        }
+    }
+
+    double integ_key(pe_hip_engine const* h, double dt)
+    {
+        if(h->tr_method == PE_HIP_TR_TRAP) return dt;
+        if(std::isnan(h->integ_hp)) return h->integ_hp;
+        return pe::integ_coef(h->tr_method, dt, h->integ_hp).a0;
+    }
+    double integ_sym_dt(pe_hip_engine const* h, double dt)
+    {
+        if(h->tr_method == PE_HIP_TR_TRAP) return dt;
+        return 2.0 / pe::integ_coef(h->tr_method, dt, std::isnan(h->integ_hp) ? 0.0 : h->integ_hp).a0;
     }
 }  // namespace pe_eng
 
@@ -822,6 +936,8 @@ namespace pe_eng PE_ENG_HIDDEN
         if(A.allocated) return PE_HIP_OK;
         auto parts = ck_parts(h);
         parts.push_back({h->V.trace_len, sizeof(int)});
+        if(h->tr_method != PE_HIP_TR_TRAP && h->V.tr_hist)  // (the one entry the table has left: the history of BE / GEAR2, values and h_p in ONE array)
+            parts.push_back({h->V.tr_hist, static_cast<size_t>(h->hc.batch) * static_cast<size_t>(pe::integ_stride(h->V)) * sizeof(double)});
         if(parts.size() > 16) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_tr_adaptive: the state of an instance has more arrays than the snapshot table holds");
         A.save = A.restore = pe::StateCopy{};
         for(auto const& p: parts)
@@ -892,6 +1008,8 @@ extern "C" {
 int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats* st)
 {
     if(!h || !h->loaded || nsteps < 0 || !(dt > 0.0)) return h ? fail(h, PE_HIP_ERR_ARG, "analyze_tr: bad arguments or no circuit") : PE_HIP_ERR_ARG;
+    if(h->tr_method != PE_HIP_TR_TRAP && has_overlay(h))
+        return fail(h, PE_HIP_ERR_ARG, "analyze_tr: a host-stamp overlay integrates in its own hooks, with the trapezoidal rule: set PE_HIP_TR_TRAP");
     HIPCHK(h, hipSetDevice(h->device));
     ac_sweep_invalidate(h);
     h->tra.n_pts = 0;  // (fixed steps restart the history of the variable-step transient)
@@ -899,7 +1017,9 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     h->dominant_ms = 0.0;
     h->dominant_launches = 0;
     if(h->hc.rows == 0 || nsteps == 0) return PE_HIP_OK;
-    int rc = ensure_symbolic(h, true, dt);
+    int rc = ensure_symbolic(h, true, integ_sym_dt(h, dt));
+    if(rc != PE_HIP_OK) return rc;
+    rc = integ_before_steps(h);
     if(rc != PE_HIP_OK) return rc;
     // A failed solve is not sticky (circuit.h:242-254: the reference rolls tr_duration back, returns false, and the next
     // analyze() simply tries again from that state -- e.g. after the caller raised g_min): every run starts with all instances live.
@@ -941,6 +1061,7 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
     if(c->n_breakpoints < 0 || (c->n_breakpoints > 0 && !c->breakpoints)) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: bad breakpoint list");
     for(int k = 0; k < c->n_breakpoints; ++k)
         if(!fin(c->breakpoints[k])) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: non-finite breakpoint");
+    int const method = h->tr_method;
     if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_tr_adaptive: a host-stamp overlay keeps host state that a rejected step cannot roll back");
     HIPCHK(h, hipSetDevice(h->device));
     int const B = h->hc.batch;
@@ -994,10 +1115,16 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
     bool failed_at_dt_min = false;
     double dt = c->dt_init;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    // (the controller's exponent: the trapezoidal rule and GEAR2 are of second order, err ~ h^3; BE of first, err ~ h^2)
+    double const q_exp = method == PE_HIP_TR_BE ? -1.0 / 2.0 : -1.0 / 3.0;
+    double hp_snapshot = h->integ_hp;
+    bool failed_snapshot = h->integ_failed;
     auto const roll_back = [&]() -> int
     {
         // the state of the snapshot; the host side as pe_hip_checkpoint_load leaves it (what the step spent came with the LTE result)
         HIPCHK(h, pe::launch_tr_state_copy(h->stream, A.restore));
+        h->integ_hp = hp_snapshot;  // (the history array of BE / GEAR2 is part of the snapshot: the host's knowledge of its h_p goes back with it)
+        h->integ_failed = failed_snapshot;
         h->fact_valid = false;
         h->a_static.clear();
         return PE_HIP_OK;
@@ -1012,8 +1139,12 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
             double const hs = std::min({dt, dt_max, t_bp - t});
             if(!(hs > 0.0)) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_tr_adaptive: the step underflowed");
             // snapshot, then one ordinary step that records nothing (the probes see it once it is accepted)
+            rc = integ_before_steps(h);
+            if(rc != PE_HIP_OK) return rc;
             HIPCHK(h, pe::launch_tr_state_copy(h->stream, A.save));
-            rc = ensure_symbolic(h, true, hs);
+            hp_snapshot = h->integ_hp;
+            failed_snapshot = h->integ_failed;
+            rc = ensure_symbolic(h, true, integ_sym_dt(h, hs));
             if(rc != PE_HIP_OK) return rc;
             HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(B) * sizeof(int), h->stream));
             bool const armed = h->probe.armed;
@@ -1044,7 +1175,9 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
             L.iters_now = h->V.n_iters;
             L.iters_before = A.shadow_iters;
             L.result = A.result;
-            HIPCHK(h, pe::launch_tr_lte(h->stream, h->V, L));
+            if(method == PE_HIP_TR_TRAP) HIPCHK(h, pe::launch_tr_lte(h->stream, h->V, L));
+            else
+                HIPCHK(h, pe::launch_tr_lte_integ(h->stream, h->V, L, method));
             pe::LteResult res{};
             HIPCHK(h, hipMemcpyAsync(&res, A.result, sizeof(res), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1082,7 +1215,7 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
                     ++S.n_rejected_lte;
                     S.newton_iters_rejected += res.iters_spent;
                     if(int const rrc = roll_back(); rrc != PE_HIP_OK) return rrc;
-                    double const f = q > 1.0 ? std::max(0.1, 0.9 * std::pow(q, -1.0 / 3.0)) : 0.1;  // (defensive: q is a NaN only with a NaN in the history, not reachable through the public calls -- the smallest factor)
+                    double const f = q > 1.0 ? std::max(0.1, 0.9 * std::pow(q, q_exp)) : 0.1;  // (defensive: q is a NaN only with a NaN in the history, not reachable through the public calls -- the smallest factor)
                     dt = std::max(hs * f, dt_min);
                     continue;
                 }
@@ -1097,13 +1230,14 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
                 if(int const prc = probe_record_step(h, all, t); prc != PE_HIP_OK) return prc;
             bool const at_bp = next_bp + 1 < bps.size() && reached(t, t_bp);
             if(at_bp) A.n_pts = 0;  // (the history restarts AT the breakpoint: the point pushed below is its first)
+            if(at_bp) integ_restart(h);  // (... and so does that of BE / GEAR2: x' jumps at a source corner, a two-step formula must not look across it)
             A.head = (A.head + 1) % 3;
             HIPCHK(h, pe::launch_tr_history_push(h->stream, h->V, A.hist, A.head));
             A.t_pts[A.head] = t;
             A.n_pts = std::min(A.n_pts + 1, 4);
             if(at_bp) dt = c->dt_init;
             else if(test)
-                dt = hs * (q > 0.0 ? std::min(2.0, 0.9 * std::pow(q, -1.0 / 3.0)) : (q == 0.0 ? 2.0 : 1.0));  // (a NaN q accepted at dt_min: no growth)
+                dt = hs * (q > 0.0 ? std::min(2.0, 0.9 * std::pow(q, q_exp)) : (q == 0.0 ? 2.0 : 1.0));  // (a NaN q accepted at dt_min: no growth)
             else
                 dt = hs;
             dt = std::max(dt, dt_min);

@@ -31,6 +31,7 @@
     #define PE_MARK(name) ((void)0)
 #endif
 #include "pe_probe.hpp"  // (after PE_DEV)
+#include "pe_integ.hpp"
 
 namespace pe
 {
@@ -102,7 +103,7 @@ namespace pe
     // start of a time step: trapezoidal companion models take the previous time point's solution
     // ------------------------------------------------------------------------------------------------
     template <class Team>
-    PE_DEV void companion_update(Team const& tm, DevView const& V, int b, double dt)
+    PE_DEV void companion_update_trap(Team const& tm, DevView const& V, int b, double dt)
     {
         double const* x = V.x + static_cast<long long>(b) * V.rows;
         double* dv = V.dv + static_cast<long long>(b) * V.dv_len;
@@ -188,6 +189,29 @@ namespace pe
                 }
             }
         }
+    }
+
+    // ... and under the rule of the view (pe_hip_set_tr_method).  BE / GEAR2 (pe_integ.hpp): the update, then h_p := dt behind a barrier -- every
+    // thread has read the slot by then.  A team that cannot synchronise (the grid-wide team of the split schedule's elementwise kernels) gets
+    // that commit as a launch of its own behind the update (pe_kernels.hip integ_companion_launch).
+    template <class Team>
+    PE_DEV void integ_step_update(Team const& tm, DevView const& V, int b, double dt)
+    {
+        integ_companion_update(tm, V, b, dt);
+        if constexpr(requires { tm.sync(); })
+        {
+            tm.sync();
+            integ_commit(tm, V, b, dt);
+        }
+    }
+    // (the kernels of the library call companion_update_trap / integ_step_update directly, each from an instantiation of its own, so that the
+    //  trapezoidal kernels hold nothing of the other rules; this dispatch serves the callers that have the view alone)
+    template <class Team>
+    PE_DEV void companion_update(Team const& tm, DevView const& V, int b, double dt)
+    {
+        if(V.tr_method != TR_TRAP) integ_step_update(tm, V, b, dt);
+        else
+            companion_update_trap(tm, V, b, dt);
     }
 
     // ------------------------------------------------------------------------------------------------
@@ -1691,7 +1715,8 @@ namespace pe
     // is recorded into the armed probe window V.pr (pe_probe.hpp) -- a separate instantiation, so that the probe-less resident kernel stays
     // as it was.  FOURIER: the recording also feeds the Fourier accumulators of V.fo (pe_fourier.hpp) -- again an instantiation of its own:
     // inlined beside the solve, its two sincos calls cost the resident kernel scratch, which the users of probes alone do not pay.
-    template <class Team, bool PROBES, bool FOURIER = false, class View>
+    // INTEG: the steps of a view whose rule is BE or GEAR2 (pe_integ.hpp) -- once more an instantiation of its own.
+    template <class Team, bool PROBES, bool FOURIER = false, bool INTEG = false, class View>
     PE_DEV void tr_steps_run(Team const& tm, View const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
     {
         if(V.status[b] != ST_OK) return;
@@ -1700,7 +1725,9 @@ namespace pe
         int st = ST_OK;
         for(int sidx = 0; sidx < nsteps; ++sidx)
         {
-            companion_update(tm, V, b, dt);
+            if constexpr(INTEG) integ_step_update(tm, V, b, dt);
+            else
+                companion_update_trap(tm, V, b, dt);
             tm.sync();
             double const prev = t;
             t = prev + dt;
@@ -1733,18 +1760,25 @@ namespace pe
     }
 
     // the same, dispatched on the armed state of the view (a view with probe_armed set is a ProbedView)
-    template <class Team>
-    PE_DEV void tr_steps(Team const& tm, DevView const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
+    template <class Team, bool INTEG>
+    PE_DEV void tr_steps_of(Team const& tm, DevView const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
     {
         if(V.probe_armed)
         {
             ProbedView const& P = static_cast<ProbedView const&>(V);
-            if(P.fo) tr_steps_run<Team, true, true>(tm, P, b, dt, nsteps, reuse_factor, lds);
+            if(P.fo) tr_steps_run<Team, true, true, INTEG>(tm, P, b, dt, nsteps, reuse_factor, lds);
             else
-                tr_steps_run<Team, true>(tm, P, b, dt, nsteps, reuse_factor, lds);
+                tr_steps_run<Team, true, false, INTEG>(tm, P, b, dt, nsteps, reuse_factor, lds);
         }
         else
-            tr_steps_run<Team, false>(tm, V, b, dt, nsteps, reuse_factor, lds);
+            tr_steps_run<Team, false, false, INTEG>(tm, V, b, dt, nsteps, reuse_factor, lds);
+    }
+    template <class Team>
+    PE_DEV void tr_steps(Team const& tm, DevView const& V, int b, double dt, int nsteps, bool reuse_factor, double* lds)
+    {
+        if(V.tr_method != TR_TRAP) tr_steps_of<Team, true>(tm, V, b, dt, nsteps, reuse_factor, lds);
+        else
+            tr_steps_of<Team, false>(tm, V, b, dt, nsteps, reuse_factor, lds);
     }
 
     // OP / DC / TROP point of circult::analyze (circuit.h:183-191, 257-266)

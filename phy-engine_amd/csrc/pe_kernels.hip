@@ -592,6 +592,17 @@ namespace pe
         tr_steps_run<HipTeam, true, true>(tm, V, b, dt, nsteps, reuse_factor != 0, pe_lds);
     }
 
+    // ... and the ones that integrate with backward Euler / Gear-2 (V.tr_method, pe_integ.hpp), whatever they record: launched only for a view
+    // whose rule is not the trapezoidal one, so that the kernels above hold nothing of it
+    template <int MINW, bool PROBES, bool FOURIER>
+    __global__ void __launch_bounds__(PE_THREADS, MINW) k_tr_steps_integ(std::conditional_t<PROBES, ProbedView, DevView> V, double dt, int nsteps, int reuse_factor)
+    {
+        int const b = static_cast<int>(blockIdx.x);
+        if(b >= V.batch) return;
+        HipTeam tm;
+        tr_steps_run<HipTeam, PROBES, FOURIER, true>(tm, V, b, dt, nsteps, reuse_factor != 0, pe_lds);
+    }
+
     template <int MINW>
     __global__ void __launch_bounds__(PE_THREADS, MINW) k_dc_point(DevView V, int mode)
     {
@@ -630,6 +641,11 @@ namespace pe
     // the tree into kernels whose boundaries are the only inter-workgroup synchronisation -- no spin-waits, no
     // cross-CU visibility protocol.  grid = (work items, instances).
     // =====================================================================================================
+    struct LaneTeam  // one thread is the whole team (per-instance bookkeeping, one instance per lane)
+    {
+        __device__ __forceinline__ int tid() const { return 0; }
+        __device__ __forceinline__ int size() const { return 1; }
+    };
     struct GridTeam  // elementwise phases: G workgroups share one instance's device / slot / row loops
     {
         __device__ __forceinline__ int tid() const { return static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x); }
@@ -640,7 +656,27 @@ namespace pe
     {
         int const b = static_cast<int>(blockIdx.y);
         if(!V.active[b]) return;
-        companion_update(GridTeam{}, V, b, dt);
+        companion_update_trap(GridTeam{}, V, b, dt);
+    }
+    // the same under BE / GEAR2 (pe_integ.hpp): the update, then -- every thread of every workgroup has read the slot -- h_p := dt
+    __global__ void __launch_bounds__(256) k_m2_integ_update(DevView V, double dt)
+    {
+        int const b = static_cast<int>(blockIdx.y);
+        if(!V.active[b]) return;
+        integ_companion_update(GridTeam{}, V, b, dt);
+    }
+    __global__ void __launch_bounds__(64) k_m2_integ_commit(DevView V, double dt)
+    {
+        int const b = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+        if(b >= V.batch || !V.active[b]) return;
+        integ_commit(LaneTeam{}, V, b, dt);
+    }
+    // the history of every instance (only_failed: of the instances whose status is not OK) restarts
+    __global__ void __launch_bounds__(64) k_integ_restart(DevView V, int only_failed)
+    {
+        int const b = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+        if(b >= V.batch) return;
+        integ_restart(LaneTeam{}, V, b, only_failed != 0);
     }
 
     // companion_dt_set != 0: first Newton iteration of a transient step -- the trapezoidal companion update of that step (what k_m2_companion
@@ -651,7 +687,7 @@ namespace pe
         int const b = static_cast<int>(blockIdx.y);
         if(!V.active[b]) return;
         GridTeam tm;
-        if(companion_dt_set) companion_update(tm, V, b, companion_dt);
+        if(companion_dt_set) companion_update_trap(tm, V, b, companion_dt);
         double const* x = V.x + static_cast<long long>(b) * V.rows;
         double* xp = V.xprev + static_cast<long long>(b) * V.rows;
         for(int r = tm.tid(); r < V.rows; r += tm.size()) xp[r] = x[r];
@@ -1106,6 +1142,25 @@ namespace pe
     hipError_t launch_tr_steps(hipStream_t st, DevView const& V, double dt, int nsteps, bool reuse)
     {
         size_t const lds = static_cast<size_t>(V.lds_doubles) * sizeof(double);
+        if(V.tr_method != TR_TRAP)  // BE / GEAR2: the instantiations of their own
+        {
+            if(!V.tr_hist) return hipErrorInvalidValue;
+            if(V.probe_armed)
+            {
+                bool const fourier = static_cast<ProbedView const&>(V).fo != nullptr;
+                auto const fn = fourier ? (V.high_occupancy ? &k_tr_steps_integ<4, true, true> : &k_tr_steps_integ<2, true, true>)
+                                        : (V.high_occupancy ? &k_tr_steps_integ<4, true, false> : &k_tr_steps_integ<2, true, false>);
+                hipError_t e = set_lds(reinterpret_cast<void const*>(fn), lds);
+                if(e != hipSuccess) return e;
+                hipLaunchKernelGGL(fn, dim3(V.batch), dim3(V.n_waves * 64), lds, st, static_cast<ProbedView const&>(V), dt, nsteps, reuse ? 1 : 0);
+                return hipGetLastError();
+            }
+            auto const fn = V.high_occupancy ? &k_tr_steps_integ<4, false, false> : &k_tr_steps_integ<2, false, false>;
+            hipError_t e = set_lds(reinterpret_cast<void const*>(fn), lds);
+            if(e != hipSuccess) return e;
+            hipLaunchKernelGGL(fn, dim3(V.batch), dim3(V.n_waves * 64), lds, st, V, dt, nsteps, reuse ? 1 : 0);
+            return hipGetLastError();
+        }
         if(V.probe_armed)  // (the view is the DevView part of a ProbedView: pe_engine.cpp probe_view)
         {
             bool const fourier = static_cast<ProbedView const&>(V).fo != nullptr;
@@ -1145,6 +1200,8 @@ namespace pe
         int g = by_rows > (want < fine ? want : fine) ? by_rows : (want < fine ? want : fine);
         return g < 1 ? 1 : (g > 64 ? 64 : g);
     }
+
+    static hipError_t integ_companion_launch(hipStream_t st, DevView const& V, double dt);  // (below, with launch_m2_companion)
 
     // ev0 / ev1 (may be null): HIP events recorded around the dominant launch (k_m2_factor_parts, or the backward
     // k_m2_solve_parts when the factors are reused) for the per-kernel roofline of bench.py.
@@ -1186,6 +1243,12 @@ namespace pe
         };
         if(!refine)
         {
+            // (BE / GEAR2: the companion update of the step in launches of its own in front of the evaluation -- k_m2_eval holds the trapezoidal one)
+            if(companion && V.tr_method != TR_TRAP)
+            {
+                if(hipError_t const e = integ_companion_launch(st, V, companion_dt); e != hipSuccess) return e;
+                companion = false;
+            }
             hipLaunchKernelGGL(k_m2_eval, dim3(G, B), dim3(256), 0, st, V, mode, t, last_step, eval_dyn, companion ? 1 : 0, companion_dt);
             hipLaunchKernelGGL(k_m2_stamp, dim3(G, B), dim3(256), 0, st, V, stamp_dyn, skip_static ? static_cast<double const*>(sk->wy) : nullptr,
                                skip_static ? sk->row_keep : nullptr);  // (+ w = P rhs)
@@ -1379,6 +1442,13 @@ namespace pe
                                          bool companion, double companion_dt, int* pub_flags, double* pub_eta, unsigned long long* pub_seq, unsigned long long seq,
                                          StaticSkip const* sk)
     {
+        // (BE / GEAR2: the companion update of the step stays outside the captured sequence, stream-ordered in front of it -- its dt is an
+        //  argument of launches that the replay does not patch)
+        if(companion && V.tr_method != TR_TRAP)
+        {
+            if(hipError_t const e = integ_companion_launch(st, V, companion_dt); e != hipSuccess) return e;
+            companion = false;
+        }
         int const dyn = (V.dyn_a && V.dyn_b) ? stamp_mode : 0;
         int const static_bits = sk ? ((sk->save ? 1 : 0) | (sk->skip ? 2 : 0)) : 0;
         M2GraphEntry* hit = nullptr;
@@ -1476,8 +1546,26 @@ namespace pe
         return hipGraphLaunch(hit->exec, st);
     }
 
+    // BE / GEAR2: the companion update of a step of the split schedule, two launches (update; h_p := dt)
+    static hipError_t integ_companion_launch(hipStream_t st, DevView const& V, double dt)
+    {
+        if(!V.tr_hist) return hipErrorInvalidValue;
+        if(V.batch <= 0) return hipSuccess;
+        int const G = grid_per_instance(V);
+        hipLaunchKernelGGL(k_m2_integ_update, dim3(G, V.batch), dim3(256), 0, st, V, dt);
+        hipLaunchKernelGGL(k_m2_integ_commit, dim3((V.batch + 63) / 64), dim3(64), 0, st, V, dt);
+        return hipGetLastError();
+    }
+    hipError_t launch_integ_restart(hipStream_t st, DevView const& V, bool only_failed)
+    {
+        if(!V.tr_hist || V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_integ_restart, dim3((V.batch + 63) / 64), dim3(64), 0, st, V, only_failed ? 1 : 0);
+        return hipGetLastError();
+    }
+
     hipError_t launch_m2_companion(hipStream_t st, DevView const& V, double dt)
     {
+        if(V.tr_method != TR_TRAP) return integ_companion_launch(st, V, dt);
         int const G = grid_per_instance(V);
         hipLaunchKernelGGL(k_m2_companion, dim3(G, V.batch), dim3(256), 0, st, V, dt);
         return hipGetLastError();
@@ -1610,6 +1698,34 @@ namespace pe
             }
         }
     }
+    // ... the same for the estimates of BE / GEAR2 (pe_integ.hpp integ_lte_partial)
+    __global__ void __launch_bounds__(256) k_tr_lte_integ(DevView V, LteView L, int method)
+    {
+        int const b = static_cast<int>(blockIdx.y);
+        int nonfinite = 0;
+        unsigned long long u = integ_lte_partial(GridTeam{}, V, L, method, b, nonfinite);
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1)
+        {
+            unsigned long long const t = __shfl_xor(u, o);
+            u = t > u ? t : u;
+        }
+        bool const any_nonfinite = __ballot(nonfinite) != 0;
+        if((threadIdx.x & 63) == 0)
+        {
+            if(L.test)
+            {
+                atomicMax(L.q_each + b, u);
+                atomicMax(&L.result->q, u);
+            }
+            if(any_nonfinite) atomicAdd(&L.result->n_nonfinite, 1);
+            if(blockIdx.x == 0 && threadIdx.x == 0)
+            {
+                if(V.status[b] != 0) atomicAdd(&L.result->n_failed, 1);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&L.result->iters_spent), static_cast<unsigned long long>(L.iters_now[b] - L.iters_before[b]));
+            }
+        }
+    }
     __global__ void __launch_bounds__(256) k_tr_history_push(DevView V, double* __restrict__ hist, int slot)
     {
         lte_history_push(GridTeam{}, V, hist, slot);
@@ -1635,6 +1751,15 @@ namespace pe
         if(e == hipSuccess && L.test) e = hipMemsetAsync(L.q_each, 0, static_cast<size_t>(V.batch) * sizeof(unsigned long long), st);
         if(e != hipSuccess) return e;
         hipLaunchKernelGGL(k_tr_lte, dim3(std::max(1, std::min(64, (V.rows + 255) / 256)), V.batch), dim3(256), 0, st, V, L);
+        return hipGetLastError();
+    }
+    hipError_t launch_tr_lte_integ(hipStream_t st, DevView const& V, LteView const& L, int method)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipError_t e = hipMemsetAsync(L.result, 0, sizeof(LteResult), st);
+        if(e == hipSuccess && L.test) e = hipMemsetAsync(L.q_each, 0, static_cast<size_t>(V.batch) * sizeof(unsigned long long), st);
+        if(e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_tr_lte_integ, dim3(std::max(1, std::min(64, (V.rows + 255) / 256)), V.batch), dim3(256), 0, st, V, L, method);
         return hipGetLastError();
     }
     hipError_t launch_tr_history_push(hipStream_t st, DevView const& V, double* hist, int slot)

@@ -95,6 +95,12 @@ namespace pe
     hipError_t launch_tr_lte(hipStream_t st, DevView const& V, LteView const& L);
     hipError_t launch_tr_history_push(hipStream_t st, DevView const& V, double* hist, int slot);
     hipError_t launch_tr_state_copy(hipStream_t st, StateCopy const& S);
+    // backward Euler / Gear-2 (pe_integ.hpp; V.tr_method, V.tr_hist).  lte_integ: launch_tr_lte with the estimate of `method`.  restart: h_p := 0
+    // of every instance (only_failed: of the instances whose status is not OK).  The companion update of a step itself rides in
+    // launch_tr_steps / launch_m2_companion / launch_m2_iteration*, dispatched on V.tr_method.  Builds without HIP: serial host definitions
+    // in pe_engine_newton.cpp.
+    hipError_t launch_tr_lte_integ(hipStream_t st, DevView const& V, LteView const& L, int method);
+    hipError_t launch_integ_restart(hipStream_t st, DevView const& V, bool only_failed);
     // DC sweep (pe_dc_sweep.hpp): V is the view of the sweep engine, whose instance b * S.P + p is circuit instance b at slot p of the pass.
     // fill: the swept slot of every instance from S.value.  seed: solution and junction / relay state of every destination with
     // S.seed_of[q] >= 0 from that source -- a circuit instance of the main engine (from_main: round 0) or an instance of the sweep engine.

@@ -135,6 +135,24 @@ int pe_hip_sweep_set_options(pe_hip_sweep* s, const pe_hip_options* opt)
     return PE_HIP_OK;
 }
 
+// the integration rule of the transient, the same on every engine (an engine setting: allowed before a circuit is loaded)
+int pe_hip_sweep_set_tr_method(pe_hip_sweep* s, int method)
+{
+    if(!s) return PE_HIP_ERR_ARG;
+    if(method != PE_HIP_TR_TRAP && method != PE_HIP_TR_BE && method != PE_HIP_TR_GEAR2)  // (refused before any engine changes)
+    {
+        s->err = "set_tr_method: unknown integration method";
+        return PE_HIP_ERR_ARG;
+    }
+    for(size_t g = 0; g < s->eng.size(); ++g)
+        if(int const rc = pe_hip_set_tr_method(s->eng[g], method); rc != PE_HIP_OK)
+        {
+            s->err = pe_hip_last_error(s->eng[g]);
+            return rc;
+        }
+    return PE_HIP_OK;
+}
+
 int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int batch, int n_tables, const pe_hip_device_table* tables)
 {
     if(!s || batch <= 0 || n_tables < 0 || (n_tables > 0 && !tables)) return PE_HIP_ERR_ARG;

@@ -33,6 +33,7 @@ EXPORTS = [
     "pe_hip_sweep_set_probes", "pe_hip_sweep_arm_probes", "pe_hip_sweep_get_probe_samples", "pe_hip_sweep_get_measures",
     "pe_hip_set_fourier", "pe_hip_get_fourier", "pe_hip_sweep_set_fourier", "pe_hip_sweep_get_fourier",
     "pe_hip_analyze_tr_adaptive", "pe_hip_get_tr_step_log",
+    "pe_hip_set_tr_method", "pe_hip_get_tr_method", "pe_hip_get_tr_history", "pe_hip_sweep_set_tr_method",
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_get_sens_params", "pe_hip_analyze_sens", "pe_hip_get_sens",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
@@ -41,6 +42,9 @@ EXPORTS = [
     "pe_hip_get_matrix_ac", "pe_hip_get_ac_pass_size", "pe_hip_get_ac_analysis_omega",
 ]
 DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
+# pe_hip_tr_method
+TR_TRAP, TR_BE, TR_GEAR2 = 0, 1, 2
+_TR_NAMES = {"trap": TR_TRAP, "be": TR_BE, "gear2": TR_GEAR2, "gear": TR_GEAR2}
 STEP_GMIN, STEP_SOURCE, STEP_AUTO = 1, 2, 3
 # pe_hip_measure_kind
 MEAS_MIN, MEAS_MAX, MEAS_AVG, MEAS_RMS, MEAS_INTEG, MEAS_CROSS = 1, 2, 3, 4, 5, 6
@@ -336,6 +340,9 @@ def lib():
         l.pe_hip_sweep_operating_point_stepping.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpStepControl), C.POINTER(OpStepStats)]
         l.pe_hip_analyze_tr_adaptive.argtypes = [C.c_void_p, C.c_double, C.POINTER(TrControl), C.POINTER(TrAdaptiveStats)]
         l.pe_hip_get_tr_step_log.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+        l.pe_hip_set_tr_method.argtypes = [C.c_void_p, C.c_int]
+        l.pe_hip_get_tr_method.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        l.pe_hip_get_tr_history.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         _lib = l
     return _lib
 
@@ -570,6 +577,25 @@ class Engine(_Probes):
         if n.value:
             self._chk(lib().pe_hip_get_tr_step_log(self._h, 0, int(n.value), _dp(dt), _ip(oc), C.byref(n)))
         return dt, oc
+
+    def set_tr_method(self, method):
+        """integration rule of the transient: TR_TRAP (default), TR_BE or TR_GEAR2, or 'trap' / 'be' / 'gear2' (pe_hip_set_tr_method); an
+        engine setting that survives load_deck.  A change restarts the integration history of every instance."""
+        m = _TR_NAMES[method.lower()] if isinstance(method, str) else int(method)
+        self._chk(lib().pe_hip_set_tr_method(self._h, m))
+
+    @property
+    def tr_method(self):
+        m = C.c_int(0)
+        self._chk(lib().pe_hip_get_tr_method(self._h, C.byref(m)))
+        return m.value
+
+    def tr_history(self, first=0, count=None):
+        """h_p [count]: the step the second history point of every instance belongs to; 0: its next step starts the history (always under TRAP)"""
+        count = self.batch - first if count is None else count
+        out = np.empty(count)
+        self._chk(lib().pe_hip_get_tr_history(self._h, int(first), int(count), _dp(out)))
+        return out
 
     def analyze_dc(self, mode=MODE_DC, check=True):
         st = RunStats()
@@ -937,6 +963,7 @@ class Sweep(_Probes):
         l.pe_hip_sweep_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
         l.pe_hip_sweep_load_circuit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DeviceTable)]
         l.pe_hip_sweep_run.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(RunStats)]
+        l.pe_hip_sweep_set_tr_method.argtypes = [C.c_void_p, C.c_int]
         l.pe_hip_sweep_operating_point.argtypes = [C.c_void_p, C.c_int, C.POINTER(RunStats)]
         l.pe_hip_sweep_reduce.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         l.pe_hip_sweep_get_solution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -960,6 +987,11 @@ class Sweep(_Probes):
     def set_options(self, g_min=0.0, refactor_every_solve=1, residual_tol=0.0):
         o = Options(0.0, 0.0, 0.0, 0.0, g_min, 0, refactor_every_solve, 0.0, residual_tol)
         self._chk(lib().pe_hip_sweep_set_options(self._h, C.byref(o)))
+
+    def set_tr_method(self, method):
+        """pe_hip_set_tr_method on every device's engine (Engine.set_tr_method)"""
+        m = _TR_NAMES[method.lower()] if isinstance(method, str) else int(method)
+        self._chk(lib().pe_hip_sweep_set_tr_method(self._h, m))
 
     def load_deck(self, deck, batch, overrides=None):
         n_nodes, n_br, tables = deck_tables(deck, batch, overrides, 0)

@@ -1502,6 +1502,23 @@ namespace phy_engine
             return true;
         }
 
+        // Integration rule of the transient (pe_hip_set_tr_method, include/pe_hip.h): PE_HIP_TR_TRAP (the default, the reference's only rule),
+        // PE_HIP_TR_BE or PE_HIP_TR_GEAR2.  A setting of the circuit: it holds for every analyze() that follows, whatever is loaded in
+        // between; a change restarts the integration history.  false (last_error set, nothing changed): an unknown value.  A netlist with
+        // models that stamp on the host integrates in their own hooks: its TR analyze() fails under a rule other than TRAP.
+        int tr_method_{PE_HIP_TR_TRAP};
+        [[nodiscard]] bool set_tr_method(int method) noexcept
+        {
+            if(method != PE_HIP_TR_TRAP && method != PE_HIP_TR_BE && method != PE_HIP_TR_GEAR2)
+            {
+                last_error = "set_tr_method: unknown integration method";
+                return false;
+            }
+            if(gpu_ && pe_hip_set_tr_method(gpu_, method) != PE_HIP_OK) return gpu_fail();
+            tr_method_ = method;
+            return true;
+        }
+
         // one AC solve (solve_once with iterate_ac): phasors scattered into the nodes / branches as complex values
         bool solve_ac_point(double omega) noexcept
         {
@@ -1728,6 +1745,7 @@ namespace phy_engine
             o.r_open = env.r_open;
             o.refactor_every_solve = 1;
             if(pe_hip_set_options(gpu_, &o) != PE_HIP_OK) return gpu_fail();
+            if(pe_hip_set_tr_method(gpu_, tr_method_) != PE_HIP_OK) return gpu_fail();  // (the current one again changes nothing)
 
             if(!loaded_ || !next.same_topology(resident_))
             {
