@@ -691,6 +691,77 @@ int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* c, int* out
  * weights); a failed output reads NaN */
 int pe_hip_get_sens(pe_hip_engine* h, int first_output, int n_outputs, int first_instance, int count, double* s, double* rss);
 
+/* ---- Multi-port network analysis (.NET / .SP / .LIN): the impedance, admittance and scattering matrices of the circuit at its operating
+ * point between n chosen terminal pairs (ports), over a frequency sweep.  The matrix of a frequency point is the same for every port and
+ * only the right-hand side differs: a pass of the sweep factors ONCE and solves the other ports with the factors kept.
+ *   Z.  With A the complex small-signal matrix of pe_hip_analyze_ac at omega and e_j = +1 at port_pos[j], -1 at port_neg[j] (a unit current
+ *   into port j's positive terminal and out of its negative one; rows 0-based as everywhere, -1: ground), A x = e_j gives column j:
+ *   Z[i][j] = x[port_pos[i]] - x[port_neg[i]], the response at port i to an excitation at port j, in ohm for node rows.  Every independent
+ *   AC source of the circuit is switched off: the right-hand side is the selector alone, the matrix is untouched -- a voltage source is a
+ *   short, a current source is open.
+ *   Y and S.  Y = Z^-1.  S = D^-1 (Z - Z0) (Z + Z0)^-1 D with Z0 = diag(z0), D = diag(sqrt z0): power waves with real reference
+ *   resistances.  S is formed from (Z + Z0)^-1, not from Y: a port on a node held by a voltage source makes Z singular and leaves S well
+ *   defined.  Both inverses come from complex Gaussian elimination with partial pivoting by modulus, on the device, one matrix per
+ *   (point, instance).  An inverse does not exist when an entry of the matrix M to invert is not finite or, after pivoting, a pivot is not
+ *   finite or has |pivot| <= n_ports 2^-52 max |M_ij|: that matrix (Y, or S) reads NaN and its status is PE_HIP_ERR_SINGULAR; Z is
+ *   unaffected, and so is the other of the two.
+ *   Operating point.  The rule of pe_hip_analyze_ac: the last linearisation -- run pe_hip_analyze_dc(PE_HIP_MODE_OP) first.  An instance
+ *   whose last analysis failed has no operating point: the call returns that status, every point carries it and reads NaN.
+ *   Points.  The rules of pe_hip_analyze_ac_sweep: any order, duplicates and 0 allowed, the same bands (n_analyses counts them), the same
+ *   memory rule for the automatic pass size; the knob NET_POINTS sets the pass size; gpu_ms is measured the same way (the conversion
+ *   included); results in the caller's order.  A point with a failing or non-finite instance in its pass is retried ALONE, one pass of one
+ *   point under an analysis on its own values (n_retried_points); if it fails again it carries that status and reads NaN (Z, Y and S, the
+ *   two matrix statuses carry it too), the other points stay readable.  Returns PE_HIP_OK, or the first failing point's status; a
+ *   singular Y or S is no failure of the call.
+ *   One factorisation per pass.  A pass fills the value vectors, writes port 0's selector, factors and solves, and for ports 1 .. n-1
+ *   writes the next selector and solves with the factors kept; every refinement correction of this call uses the kept factors too
+ *   (threshold, at most three rounds and the closing residual are those of the forward sweep).  n_factorisations counts the batched
+ *   numeric factorisations launched: one per pass, plus any the residual safety net forced (a re-match on an instance's own values, in
+ *   the factoring solve or in a kept-factor one, is followed by a factorisation of EVERY instance under the new pivot order, and those
+ *   factors are the ones kept from then on); n_solves the batched kept-factor solves.
+ *   pe_hip_options.refactor_every_solve speaks of the main engine's transient and does not apply to this call's own engine.
+ *   Determinism.  The conversion of a matrix depends on that matrix alone (no atomics, no scratch), the column of a port on its own
+ *   right-hand side: results do not depend on the pass size, the batch or the pass, and permuting the ports permutes rows and columns of
+ *   Z exactly.  They depend on the other points of the call through the band, as in the noise analysis.
+ *   State.  The call has state of its own (a forward small-signal system with selector lists, engines, buffers); the main engine is read
+ *   and never written: a stored AC sweep, noise result, sensitivity result and DC sweep read the same bits before and after.  The calls
+ *   that make a stored noise result unreadable make this one unreadable too (PE_HIP_ERR_ARG, "no network analysis yet").
+ *   PE_HIP_ERR_ARG, engine unchanged: no circuit, n_points < 1, omegas or c NULL, a negative or non-finite omega, n_ports out of range,
+ *   port_pos / port_neg NULL, a row out of range, port_pos == port_neg for a port (both -1 included), two identical ports, a non-finite
+ *   or non-positive z0, a circuit with a host-stamp overlay.  There is no twin on the multi-device pe_hip_sweep_* handle. */
+#define PE_HIP_NET_MAX_PORTS 8
+enum { PE_HIP_NET_Z = 0, PE_HIP_NET_Y = 1, PE_HIP_NET_S = 2 };
+typedef struct pe_hip_net_control {
+    int n_ports;              /* 1 .. PE_HIP_NET_MAX_PORTS */
+    const int* port_pos;      /* [n_ports] rows of x; -1: ground */
+    const int* port_neg;
+    const double* z0;         /* [n_ports] reference resistances, finite, > 0; NULL: 50 ohm each */
+} pe_hip_net_control;
+typedef struct pe_hip_net_stats {
+    int n_points;             /* as passed */
+    int n_ports;
+    int n_passes;             /* passes, retries included */
+    int points_per_pass;      /* largest number of points put into one pass */
+    int n_analyses;           /* symbolic analyses: one per frequency band + one per retried point */
+    int n_factorisations;     /* batched numeric factorisations launched (passes + retries + any the safety net forced) */
+    int n_solves;             /* batched kept-factor solves: ports after the first, and every refinement correction */
+    int n_refine_rounds;      /* correction solves, summed over passes and ports */
+    int n_retried_points;     /* points that failed in their pass and were solved again alone */
+    double gpu_ms;            /* HIP-event time of the passes and of the conversion */
+} pe_hip_net_stats;
+int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, const pe_hip_net_control* c, int* point_status, pe_hip_net_stats* stats);
+/* one matrix kind (PE_HIP_NET_Z / _Y / _S) of the last call in the CALLER's point order: re, im [n_points][count][n_ports][n_ports], entry
+ * [i][j] the response at port i to an excitation at port j; a failed point, and a matrix without inverse, read NaN */
+int pe_hip_get_net(pe_hip_engine* h, int which, int first_point, int n_points, int first_instance, int count, double* re, double* im);
+/* statuses of Y and of S of the last call, [n_points][count] each: PE_HIP_OK, PE_HIP_ERR_SINGULAR, or the status of a failed point;
+ * either pointer may be NULL */
+int pe_hip_get_net_status(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, int* y_status, int* s_status);
+/* The conversion alone, on caller-supplied impedance matrices z_re / z_im [n_mats][n_ports][n_ports]: the same device kernel, the same
+ * rules.  Needs a created engine, no circuit.  z0: [n_ports] or NULL (50 ohm each).  y_* / s_*: [n_mats][n_ports][n_ports], statuses
+ * [n_mats]; any output pointer may be NULL.  PE_HIP_ERR_ARG: n_ports out of range, n_mats < 1, z_re or z_im NULL, a bad z0. */
+int pe_hip_convert_net(pe_hip_engine* h, int n_ports, int n_mats, const double* z_re, const double* z_im, const double* z0, double* y_re, double* y_im,
+                       double* s_re, double* s_im, int* y_status, int* s_status);
+
 /* x = [node voltages ; branch currents], instance-major [count][rows] */
 int pe_hip_get_solution(pe_hip_engine* h, int first_instance, int count, double* x);
 int pe_hip_set_solution(pe_hip_engine* h, int first_instance, int count, const double* x);

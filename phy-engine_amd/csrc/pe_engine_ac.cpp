@@ -2,7 +2,8 @@
 // solved by a second engine, iterative refinement on the device) and pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep (a whole frequency
 // sweep as batches of that system on a third engine, pe_ac_sweep.hpp), and pe_hip_analyze_noise / pe_hip_get_noise* (the same sweep body
 // on the adjoint system, pe_noise.hpp), and pe_hip_analyze_sens / pe_hip_get_sens* (the same body on the adjoint system at omega = 0, one
-// point per output, pe_sens.hpp).
+// point per output, pe_sens.hpp), and pe_hip_analyze_net / pe_hip_get_net* / pe_hip_convert_net (the same body on a forward system of its
+// own with one right-hand side per port on one factorisation per pass, pe_net.hpp).
 #include "pe_engine_internal.hpp"
 
 #include <functional>
@@ -54,13 +55,16 @@ namespace
     }
 
     // the third engine: the AC system with batch (circuit batch) x P, constructed like A.eng, and the buffers sized by that batch
-    int sweep_engine_build(pe_hip_engine* h, pe_hip_engine::Ac& A, int P, std::string const& name)
+    // keep_factors: the engine stores L21 too, so that a later solve can run on the factors of an earlier one (the network analysis decides
+    // itself when they are valid: pe_hip_options.refactor_every_solve speaks of the main engine's transient)
+    int sweep_engine_build(pe_hip_engine* h, pe_hip_engine::Ac& A, int P, std::string const& name, bool keep_factors = false)
     {
         auto& W = A.sweep;
         sweep_engine_drop(W);
         if(pe_hip_create(h->device, &W.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, name + ": " + std::string(pe_hip_last_error(nullptr)));
         W.eng->knobs = h->knobs;
         W.eng->opt = h->opt;
+        if(keep_factors) W.eng->opt.refactor_every_solve = 0;
         W.eng->hc = A.circ.hc;
         W.eng->hc.batch = h->hc.batch * P;
         int const rc = finish_load(W.eng);
@@ -124,6 +128,14 @@ namespace pe_eng
         Y.pass_pool.release();
         Y.res_pool.release();
         Y = pe_hip_engine::Sens{};
+        // the network analysis likewise
+        auto& T = h->net;
+        sweep_engine_drop(T.sys.sweep);
+        if(T.sys.eng) pe_hip_destroy(T.sys.eng);
+        T.sys.sweep.circ_pool.release();
+        T.port_pool.release();
+        T.res_pool.release();
+        T = pe_hip_engine::Net{};
     }
 }  // namespace pe_eng
 
@@ -308,6 +320,13 @@ namespace
         std::function<int(int i, bool& finite)> reread;         // noise (no `single`): point i was retried alone in a pass of its own -- read it back
         std::function<int(pe_hip_engine* E)> after_fill;        // sensitivity only (else empty): the value vectors of a pass stand -- its own right-hand sides
         char const* pass_knob = "AC_SWEEP_POINTS";              // the knob that sets the points per pass
+        // network analysis only: n_rhs right-hand sides per pass on ONE factorisation -- the first as everywhere, then next_rhs(E, j) writes
+        // the j-th and it is solved with the factors kept; every correction solve keeps them too; the epilogue runs once per right-hand side
+        int n_rhs = 1;
+        bool keep_factors = false;
+        std::function<int(pe_hip_engine* E, int j)> next_rhs;
+        int* n_factorisations = nullptr;                        // (counted from the engine's n_factor_launches)
+        int* n_solves = nullptr;                                // kept-factor solves
     };
 
     // The body of a frequency sweep on the real-equivalent system A (forward: h->ac, adjoint: h->noise.sys): base vectors, bands,
@@ -446,7 +465,7 @@ namespace
         cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
         int const P = static_cast<int>(std::min<long long>(cap, largest_band));
         if(!W.eng || W.P != P)
-            if(int const rc = sweep_engine_build(h, A, P, K.name); rc != PE_HIP_OK) return rc;
+            if(int const rc = sweep_engine_build(h, A, P, K.name, K.keep_factors); rc != PE_HIP_OK) return rc;
         S.points_per_pass = 0;
 
         // ---- result buffers on the device
@@ -460,10 +479,21 @@ namespace
         std::vector<double> omega_h(static_cast<size_t>(P)), worst_h;
         std::vector<int> point_h(static_cast<size_t>(P));
         // one batched factor + solve of all Q instances from the device's value vectors; a numerical failure of some instances is theirs alone
-        auto solve = [&]() -> int
+        // (kept: with the factors of the pass's first solve -- the network analysis' further right-hand sides and its corrections)
+        auto solve = [&](bool kept = false) -> int
         {
             HIPCHK(h, hipMemset(E->V.status, 0, static_cast<size_t>(Q) * sizeof(int)));
-            int const rc = pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
+            long long const f0 = E->n_factor_launches, r0 = E->n_rematched;
+            int rc = kept ? dc_solve_kept(E, PE_HIP_MODE_DC, nullptr) : pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
+            if(K.keep_factors && !kept && E->n_rematched != r0 && (rc == PE_HIP_OK || numerical(rc)))
+            {
+                // the safety net re-matched the pivot order inside the factoring solve: only the instances it retried hold factors of the new
+                // order, and the solves that follow keep them -- every instance factors again under it (as dc_solve_kept does for its own)
+                HIPCHK(h, hipMemset(E->V.status, 0, static_cast<size_t>(Q) * sizeof(int)));
+                rc = pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
+            }
+            if(K.n_factorisations) *K.n_factorisations += static_cast<int>(E->n_factor_launches - f0);
+            if(kept && K.n_solves) ++*K.n_solves;
             if(rc != PE_HIP_OK && !numerical(rc)) return fail(h, rc, K.name + ": " + E->err);
             if(rc != PE_HIP_OK)
             {
@@ -493,37 +523,54 @@ namespace
             HIPCHK(h, pe::launch_ac_sweep_fill(es, E->V, W.V));
             if(K.after_fill)
                 if(int const rc = K.after_fill(E); rc != PE_HIP_OK) return rc;
-            if(int const rc = solve(); rc != PE_HIP_OK) return rc;
-            HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
-            W.b0_valid = true;
-            // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds, then one closing residual evaluation of the iterate the
-            // third correction produced), decided per instance: the host reads one int per round
-            int above = 0;
-            for(int round = 0;; ++round)
+            bool const keep = K.keep_factors;  // (the network analysis: one factorisation per pass)
+            int last_above = 0;
+            // the rounds ran out with instances still above the threshold: fine when their error is merely not at rounding level yet (the
+            // single-point path stops there too), a failure when it is not a number
+            auto check_above = [&]() -> int
             {
-                HIPCHK(h, pe::launch_ac_residual_each(es, E->V, W.V));
-                HIPCHK(h, hipMemcpyAsync(&above, W.V.n_above, sizeof(int), hipMemcpyDeviceToHost, es));
+                if(last_above == 0) return PE_HIP_OK;
                 HIPCHK(h, hipStreamSynchronize(es));
-                if(above == 0 || round == 3) break;
-                if(int const rc = solve(); rc != PE_HIP_OK) return rc;
-                HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, false));
-                ++S.n_refine_rounds;
+                worst_h.resize(static_cast<size_t>(Q));
+                HIPCHK(h, hipMemcpy(worst_h.data(), W.V.worst, static_cast<size_t>(Q) * sizeof(double), hipMemcpyDeviceToHost));
+                for(int q = 0; q < Q; ++q)
+                    if(!std::isfinite(worst_h[q]) && inst_status[q] == 0) inst_status[q] = PE_HIP_ERR_INACCURATE;
+                return PE_HIP_OK;
+            };
+            for(int j = 0; j < K.n_rhs; ++j)
+            {
+                if(j > 0)
+                {
+                    W.b0_valid = false;
+                    if(int const rc = K.next_rhs(E, j); rc != PE_HIP_OK) return rc;
+                }
+                if(int const rc = solve(j > 0); rc != PE_HIP_OK) return rc;
+                HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, true));
+                W.b0_valid = true;
+                // refinement as in pe_hip_analyze_ac (same threshold, at most three rounds, then one closing residual evaluation of the iterate
+                // the third correction produced), decided per instance: the host reads one int per round
+                int above = 0;
+                for(int round = 0;; ++round)
+                {
+                    HIPCHK(h, pe::launch_ac_residual_each(es, E->V, W.V));
+                    HIPCHK(h, hipMemcpyAsync(&above, W.V.n_above, sizeof(int), hipMemcpyDeviceToHost, es));
+                    HIPCHK(h, hipStreamSynchronize(es));
+                    if(above == 0 || round == 3) break;
+                    if(int const rc = solve(keep); rc != PE_HIP_OK) return rc;
+                    HIPCHK(h, pe::launch_ac_accumulate_each(es, E->V, W.V, false));
+                    ++S.n_refine_rounds;
+                }
+                if(int const rc = K.epilogue(E); rc != PE_HIP_OK) return rc;
+                last_above = above;
+                if(j + 1 < K.n_rhs)  // (the next right-hand side overwrites the errors of this one)
+                    if(int const rc = check_above(); rc != PE_HIP_OK) return rc;
             }
-            if(int const rc = K.epilogue(E); rc != PE_HIP_OK) return rc;
             HIPCHK(h, hipEventRecord(h->ev1, es));
             HIPCHK(h, hipStreamSynchronize(es));
             float ms = 0.f;
             HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
             S.gpu_ms += ms;
-            if(above != 0)
-            {
-                // the rounds ran out with instances still above the threshold: fine when their error is merely not at rounding level yet (the
-                // single-point path stops there too), a failure when it is not a number
-                worst_h.resize(static_cast<size_t>(Q));
-                HIPCHK(h, hipMemcpy(worst_h.data(), W.V.worst, static_cast<size_t>(Q) * sizeof(double), hipMemcpyDeviceToHost));
-                for(int q = 0; q < Q; ++q)
-                    if(!std::isfinite(worst_h[q]) && inst_status[q] == 0) inst_status[q] = PE_HIP_ERR_INACCURATE;
-            }
+            if(int const rc = check_above(); rc != PE_HIP_OK) return rc;
             for(int p = 0; p < n; ++p)
                 for(int b = 0; b < B; ++b)
                     if(inst_status[static_cast<size_t>(b) * P + p] != 0) failed[point_h[p]] = 1;
@@ -1444,6 +1491,300 @@ int pe_hip_get_sens(pe_hip_engine* h, int first_output, int n_outputs, int first
 
 }  // extern "C"
 
+
+namespace
+{
+    static_assert(pe::NET_MAX_PORTS == PE_HIP_NET_MAX_PORTS && pe::NET_ERR_SINGULAR == PE_HIP_ERR_SINGULAR, "pe_net.hpp names these without including the C header");
+
+    bool net_z0_ok(double const* z0, int n)
+    {
+        for(int i = 0; z0 && i < n; ++i)
+            if(!std::isfinite(z0[i]) || !(z0[i] > 0.0)) return false;
+        return true;
+    }
+}  // namespace
+
+extern "C" {
+
+/* Z, Y and S of the circuit between n ports over a frequency sweep: the sweep body of pe_hip_analyze_ac_sweep on a forward system with
+ * state of its own (h->net) whose right-hand side is a port's selector -- one factorisation per pass, the ports after the first solved
+ * with the factors kept (dc_solve_kept) --, columns gathered on the device (k_net_gather), the dense conversion there too (k_net_convert).
+ * Definitions: include/pe_hip.h. */
+int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, const pe_hip_net_control* ctl, int* point_status, pe_hip_net_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(n_points < 1 || !omegas || !ctl) return fail(h, PE_HIP_ERR_ARG, "analyze_net: n_points < 1, no omegas or no control");
+    for(int i = 0; i < n_points; ++i)
+        if(!std::isfinite(omegas[i]) || omegas[i] < 0.0) return fail(h, PE_HIP_ERR_ARG, "analyze_net: negative or non-finite omega");
+    auto& hc = h->hc;
+    int const B = hc.batch, N = hc.rows, n = ctl->n_ports;
+    if(n < 1 || n > PE_HIP_NET_MAX_PORTS || !ctl->port_pos || !ctl->port_neg) return fail(h, PE_HIP_ERR_ARG, "analyze_net: n_ports out of range or no port rows");
+    for(int i = 0; i < n; ++i)
+    {
+        int const pos = ctl->port_pos[i], neg = ctl->port_neg[i];
+        if(pos < -1 || pos >= N || neg < -1 || neg >= N) return fail(h, PE_HIP_ERR_ARG, "analyze_net: port row out of range");
+        if(pos == neg) return fail(h, PE_HIP_ERR_ARG, "analyze_net: a port needs two different rows (-1: ground)");
+        for(int k = 0; k < i; ++k)
+            if(ctl->port_pos[k] == pos && ctl->port_neg[k] == neg) return fail(h, PE_HIP_ERR_ARG, "analyze_net: two identical ports");
+    }
+    if(!net_z0_ok(ctl->z0, n)) return fail(h, PE_HIP_ERR_ARG, "analyze_net: a reference resistance is not finite or not positive");
+    if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_net: host-stamped overlay models are not supported");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto& Z = h->net;
+    auto& A = Z.sys;
+    auto& W = A.sweep;
+    Z.valid = false;
+    size_t const nn = static_cast<size_t>(n) * n, n_mats = static_cast<size_t>(n_points) * B, plane = n_mats * nn;
+    pe_hip_ac_sweep_stats S{};
+    S.n_points = n_points;
+    int n_fact = 0, n_solves = 0;
+    std::vector<int> pst(static_cast<size_t>(n_points), PE_HIP_OK);
+    auto publish = [&]()
+    {
+        Z.n_points = n_points;
+        Z.batch = B;
+        Z.n_ports = n;
+        Z.valid = true;
+        if(point_status) std::copy(pst.begin(), pst.end(), point_status);
+        if(stats)
+        {
+            stats->n_points = n_points;
+            stats->n_ports = n;
+            stats->n_passes = S.n_passes;
+            stats->points_per_pass = S.points_per_pass;
+            stats->n_analyses = S.n_analyses;
+            stats->n_factorisations = n_fact;
+            stats->n_solves = n_solves;
+            stats->n_refine_rounds = S.n_refine_rounds;
+            stats->n_retried_points = S.n_fallback_points;
+            stats->gpu_ms = S.gpu_ms;
+        }
+    };
+    // what belongs to point i: its block of every plane, its statuses
+    auto blank = [&](int i, int status)
+    {
+        for(int pl = 0; pl < 6; ++pl) std::fill_n(Z.res.begin() + pl * plane + static_cast<size_t>(i) * B * nn, static_cast<size_t>(B) * nn, std::nan(""));
+        for(int w = 0; w < 2; ++w) std::fill_n(Z.status.begin() + w * n_mats + static_cast<size_t>(i) * B, static_cast<size_t>(B), status);
+    };
+    Z.res.assign(6 * plane, std::nan(""));
+    Z.status.assign(2 * n_mats, PE_HIP_OK);
+
+    // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
+    {
+        std::vector<int> inst(static_cast<size_t>(B), 0);
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+        for(int b = 0; b < B; ++b)
+        {
+            if(inst[static_cast<size_t>(b)] == PE_HIP_OK) continue;
+            std::fill(pst.begin(), pst.end(), inst[static_cast<size_t>(b)]);
+            for(int i = 0; i < n_points; ++i) blank(i, inst[static_cast<size_t>(b)]);
+            publish();
+            return fail(h, inst[static_cast<size_t>(b)], "analyze_net: instance " + std::to_string(b) + " has no operating point (its last analysis failed)");
+        }
+    }
+
+    // ---- the forward system; its right-hand-side lists select port 0 (the circuit's own AC sources are switched off)
+    int const pos0 = ctl->port_pos[0], neg0 = ctl->port_neg[0];
+    if(!A.built)
+    {
+        if(int const rc = ensure_ac_built(h, A); rc != PE_HIP_OK) return rc;
+        Z.have_port0 = false;
+    }
+    if(!Z.have_port0 || Z.pos0 != pos0 || Z.neg0 != neg0)
+    {
+        noise_selector_lists(A.circ.hc.rows, pos0, neg0, A.b_ptr0, A.b_src0);
+        W.circ_pool.release();  // (base vectors, scale flags and the lists: uploaded again by the sweep body)
+        W.V.base = nullptr;
+        W.V.scale = nullptr;
+        W.V.b_ptr0 = W.V.b_src0 = nullptr;
+    }
+    Z.have_port0 = true;
+    Z.pos0 = pos0;
+    Z.neg0 = neg0;
+
+    // ---- the ports of this call
+    if(!Z.d_pos)
+    {
+        HIPCHK(h, Z.port_pool.alloc(Z.d_pos, PE_HIP_NET_MAX_PORTS));
+        HIPCHK(h, Z.port_pool.alloc(Z.d_neg, PE_HIP_NET_MAX_PORTS));
+        HIPCHK(h, Z.port_pool.alloc(Z.d_z0, PE_HIP_NET_MAX_PORTS));
+    }
+    {
+        double z0[PE_HIP_NET_MAX_PORTS];
+        for(int i = 0; i < n; ++i) z0[i] = ctl->z0 ? ctl->z0[i] : 50.0;
+        HIPCHK(h, hipMemcpy(Z.d_pos, ctl->port_pos, static_cast<size_t>(n) * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(Z.d_neg, ctl->port_neg, static_cast<size_t>(n) * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(Z.d_z0, z0, static_cast<size_t>(n) * sizeof(double), hipMemcpyHostToDevice));
+    }
+
+    int cur = 0;  // the port whose right-hand side the pass is solving
+    SweepHooks hooks;
+    hooks.name = "analyze_net";
+    hooks.pass_knob = "NET_POINTS";
+    hooks.n_rhs = n;
+    hooks.keep_factors = true;
+    hooks.n_factorisations = &n_fact;
+    hooks.n_solves = &n_solves;
+    hooks.prepare = [&](int P) -> int
+    {
+        // (the planes are sized by n_points x batch x n^2, the statuses by n_points x batch: two calls can agree in one and not in the other)
+        if(Z.res_len != plane || Z.status_len != 2 * n_mats || !Z.d_res || !Z.d_status)
+        {
+            Z.res_pool.release();
+            Z.d_res = nullptr;
+            Z.d_status = nullptr;
+            Z.res_len = 0;
+            Z.status_len = 0;
+            HIPCHK(h, Z.res_pool.alloc(Z.d_res, 6 * plane, false));
+            HIPCHK(h, Z.res_pool.alloc(Z.d_status, 2 * n_mats, false));
+            Z.res_len = plane;
+            Z.status_len = 2 * n_mats;
+        }
+        HIPCHK(h, hipMemset(Z.d_res, 0xff, 6 * plane * sizeof(double)));  // (all ones: a NaN -- a point no pass wrote reads NaN)
+        Z.V.n_ports = n;
+        Z.V.P = P;
+        Z.V.n_inst = B;
+        Z.V.n_half = N;
+        Z.V.rhs0 = A.rhs0;
+        Z.V.pos = Z.d_pos;
+        Z.V.neg = Z.d_neg;
+        Z.V.z0 = Z.d_z0;
+        Z.V.point = W.V.point;
+        Z.V.xacc = W.V.xacc;
+        Z.V.b0 = W.V.b0;
+        Z.V.z_re = Z.d_res;
+        Z.V.z_im = Z.d_res + plane;
+        cur = 0;
+        return PE_HIP_OK;
+    };
+    hooks.next_rhs = [&](pe_hip_engine* E, int j) -> int
+    {
+        cur = j;
+        HIPCHK(h, pe::launch_net_rhs(E->stream, E->V, Z.V, j));
+        return PE_HIP_OK;
+    };
+    hooks.epilogue = [&](pe_hip_engine* E) -> int
+    {
+        HIPCHK(h, pe::launch_net_gather(E->stream, E->V, Z.V, cur));
+        if(cur == n - 1) cur = 0;
+        return PE_HIP_OK;
+    };
+    auto finite_point = [&](int i)
+    {
+        size_t const o = static_cast<size_t>(i) * B * nn;
+        for(size_t k = 0; k < static_cast<size_t>(B) * nn; ++k)
+            if(!std::isfinite(Z.res[o + k]) || !std::isfinite(Z.res[plane + o + k])) return false;
+        return true;
+    };
+    hooks.collect = [&](std::vector<char>& failed) -> int
+    {
+        HIPCHK(h, hipMemcpy(Z.res.data(), Z.d_res, 2 * plane * sizeof(double), hipMemcpyDeviceToHost));
+        for(int i = 0; i < n_points; ++i)
+            if(!failed[i] && !finite_point(i)) failed[i] = 1;
+        return PE_HIP_OK;
+    };
+    hooks.reread = [&](int i, bool& finite) -> int
+    {
+        size_t const o = static_cast<size_t>(i) * B * nn;
+        HIPCHK(h, hipMemcpy(&Z.res[o], Z.d_res + o, static_cast<size_t>(B) * nn * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&Z.res[plane + o], Z.d_res + plane + o, static_cast<size_t>(B) * nn * sizeof(double), hipMemcpyDeviceToHost));
+        finite = finite_point(i);
+        return PE_HIP_OK;
+    };
+    if(int const rc = sweep_body(h, A, n_points, omegas, pst, S, hooks); rc != PE_HIP_OK) return rc;
+
+    // ---- Y and S of every (point, instance) on the device, from the impedance matrices as they stand there
+    {
+        double* const d = Z.d_res;
+        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+        HIPCHK(h, pe::launch_net_convert(h->stream, n, static_cast<int>(n_mats), d, d + plane, Z.d_z0, d + 2 * plane, d + 3 * plane, d + 4 * plane, d + 5 * plane,
+                                         Z.d_status, Z.d_status + n_mats));
+        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        S.gpu_ms += ms;
+        HIPCHK(h, hipMemcpy(Z.res.data() + 2 * plane, d + 2 * plane, 4 * plane * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(Z.status.data(), Z.d_status, 2 * n_mats * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    // a failed point reads NaN and carries its status
+    for(int i = 0; i < n_points; ++i)
+        if(pst[i] != PE_HIP_OK) blank(i, pst[i]);
+    publish();
+    for(int i = 0; i < n_points; ++i)
+        if(pst[i] != PE_HIP_OK) return fail(h, pst[i], "analyze_net: point " + std::to_string(i) + " failed");
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_net(pe_hip_engine* h, int which, int first_point, int n_points, int first_instance, int count, double* re, double* im)
+{
+    if(!h || !h->loaded || !re || !im || which < PE_HIP_NET_Z || which > PE_HIP_NET_S) return PE_HIP_ERR_ARG;
+    auto const& Z = h->net;
+    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_net: no network analysis yet");
+    if(first_point < 0 || n_points < 0 || first_point > Z.n_points - n_points || first_instance < 0 || count < 0 || first_instance > Z.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_net: points or instances out of range");
+    size_t const nn = static_cast<size_t>(Z.n_ports) * Z.n_ports, plane = static_cast<size_t>(Z.n_points) * Z.batch * nn;
+    for(int i = 0; i < n_points && count > 0; ++i)
+    {
+        size_t const src = (static_cast<size_t>(first_point + i) * Z.batch + first_instance) * nn, dst = static_cast<size_t>(i) * count * nn;
+        std::memcpy(re + dst, &Z.res[2 * which * plane + src], static_cast<size_t>(count) * nn * sizeof(double));
+        std::memcpy(im + dst, &Z.res[(2 * which + 1) * plane + src], static_cast<size_t>(count) * nn * sizeof(double));
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_net_status(pe_hip_engine* h, int first_point, int n_points, int first_instance, int count, int* y_status, int* s_status)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    auto const& Z = h->net;
+    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_net_status: no network analysis yet");
+    if(first_point < 0 || n_points < 0 || first_point > Z.n_points - n_points || first_instance < 0 || count < 0 || first_instance > Z.batch - count)
+        return fail(h, PE_HIP_ERR_ARG, "get_net_status: points or instances out of range");
+    size_t const n_mats = static_cast<size_t>(Z.n_points) * Z.batch;
+    for(int i = 0; i < n_points && count > 0; ++i)
+    {
+        size_t const src = static_cast<size_t>(first_point + i) * Z.batch + first_instance, dst = static_cast<size_t>(i) * count;
+        if(y_status) std::memcpy(y_status + dst, &Z.status[src], static_cast<size_t>(count) * sizeof(int));
+        if(s_status) std::memcpy(s_status + dst, &Z.status[n_mats + src], static_cast<size_t>(count) * sizeof(int));
+    }
+    return PE_HIP_OK;
+}
+
+/* the conversion kernel of pe_hip_analyze_net on the caller's matrices */
+int pe_hip_convert_net(pe_hip_engine* h, int n_ports, int n_mats, const double* z_re, const double* z_im, const double* z0, double* y_re, double* y_im,
+                       double* s_re, double* s_im, int* y_status, int* s_status)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(n_ports < 1 || n_ports > PE_HIP_NET_MAX_PORTS || n_mats < 1 || !z_re || !z_im) return fail(h, PE_HIP_ERR_ARG, "convert_net: n_ports out of range, n_mats < 1 or no matrices");
+    if(!net_z0_ok(z0, n_ports)) return fail(h, PE_HIP_ERR_ARG, "convert_net: a reference resistance is not finite or not positive");
+    HIPCHK(h, hipSetDevice(h->device));
+    size_t const plane = static_cast<size_t>(n_mats) * n_ports * n_ports;
+    Pool pool;
+    double *d{}, *d_z0{};
+    int* d_status{};
+    HIPCHK(h, pool.alloc(d, 6 * plane, false));
+    HIPCHK(h, pool.alloc(d_z0, PE_HIP_NET_MAX_PORTS));
+    HIPCHK(h, pool.alloc(d_status, 2 * static_cast<size_t>(n_mats), false));
+    double ref[PE_HIP_NET_MAX_PORTS];
+    for(int i = 0; i < n_ports; ++i) ref[i] = z0 ? z0[i] : 50.0;
+    HIPCHK(h, hipMemcpy(d, z_re, plane * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d + plane, z_im, plane * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_z0, ref, static_cast<size_t>(n_ports) * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, pe::launch_net_convert(h->stream, n_ports, n_mats, d, d + plane, d_z0, d + 2 * plane, d + 3 * plane, d + 4 * plane, d + 5 * plane, d_status,
+                                     d_status + n_mats));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double* const out[4] = {y_re, y_im, s_re, s_im};
+    for(int k = 0; k < 4; ++k)
+        if(out[k]) HIPCHK(h, hipMemcpy(out[k], d + (2 + k) * plane, plane * sizeof(double), hipMemcpyDeviceToHost));
+    if(y_status) HIPCHK(h, hipMemcpy(y_status, d_status, static_cast<size_t>(n_mats) * sizeof(int), hipMemcpyDeviceToHost));
+    if(s_status) HIPCHK(h, hipMemcpy(s_status, d_status + n_mats, static_cast<size_t>(n_mats) * sizeof(int), hipMemcpyDeviceToHost));
+    return PE_HIP_OK;
+}
+
+}  // extern "C"
+
 #if !defined(__HIPCC__)
 // Builds without HIP (the emulation library of tests/emu): the sweep's launchers as serial loops over the instances, with a one-thread
 // team running the text of pe_ac_sweep.hpp
@@ -1523,6 +1864,28 @@ namespace pe
                     *dst = sum;
             }
             if(Z.weight && Z.n_chunks > 1) sens_finish(Z, q);
+        }
+        return hipSuccess;
+    }
+    // ... and the network launchers with the text of pe_net.hpp (the conversion: a one-lane wave that holds the whole augmented matrix)
+    hipError_t launch_net_rhs(hipStream_t, DevView const& V, NetView const& Z, int j)
+    {
+        for(int q = 0; q < V.batch; ++q) net_rhs(SweepHostTeam{}, V, Z, q, j);
+        return hipSuccess;
+    }
+    hipError_t launch_net_gather(hipStream_t, DevView const& V, NetView const& Z, int j)
+    {
+        for(int q = 0; q < V.batch; ++q) net_gather(SweepHostTeam{}, V, Z, q, j);
+        return hipSuccess;
+    }
+    hipError_t launch_net_convert(hipStream_t, int n, int n_mats, double const* z_re, double const* z_im, double const* z0, double* y_re, double* y_im,
+                                  double* s_re, double* s_im, int* y_status, int* s_status)
+    {
+        for(long long m = 0; m < n_mats; ++m)  // (both callers have checked n)
+        {
+            long long const o = m * n * n;
+            net_convert(NetSerialWave{}, n, z_re + o, z_im + o, z0, y_re ? y_re + o : nullptr, y_im ? y_im + o : nullptr, s_re ? s_re + o : nullptr,
+                        s_im ? s_im + o : nullptr, y_status ? y_status + m : nullptr, s_status ? s_status + m : nullptr);
         }
         return hipSuccess;
     }

@@ -31,6 +31,7 @@
 #include "pe_kernels.hpp"
 #include "pe_integ.hpp"
 #include "pe_lte.hpp"
+#include "pe_net.hpp"
 #include "pe_noise.hpp"
 #include "pe_op_step.hpp"
 #include "pe_sens.hpp"
@@ -289,6 +290,29 @@ struct pe_hip_engine
         int n_outputs{}, batch{};
         std::vector<double> res;          // [n_outputs][batch] rss (weighted), then [n_outputs][batch][n_par] sensitivities (kept)
     } sens;
+    // multi-port network analysis (pe_hip_analyze_net, pe_net.hpp): the FORWARD real-equivalent system with sweep state of its own, like the
+    // noise analysis -- its right-hand-side lists hold port 0's selector instead of the circuit's AC sources, the other ports' selectors are
+    // written per pass (k_net_rhs) --, the ports of the last call on the device and its result
+    struct Net
+    {
+        Ac sys;
+        bool have_port0{};
+        int pos0{-1}, neg0{-1};           // the port the right-hand-side lists of `sys` select
+        Pool port_pool;                   // port rows and reference resistances (PE_HIP_NET_MAX_PORTS each)
+        int *d_pos{}, *d_neg{};
+        double* d_z0{};
+        Pool res_pool;                    // sized by the call: [Z re | Z im | Y re | Y im | S re | S im] and the two statuses
+        size_t res_len{};                 // doubles of one plane
+        size_t status_len{};              // ints of d_status
+        double* d_res{};
+        int* d_status{};                  // [2][n_points][batch]: Y, then S
+        pe::NetView V{};
+        bool valid{};                     // `res` belongs to the current circuit at its current operating point
+        int n_points{}, batch{}, n_ports{};
+        std::vector<double> res;          // the six planes, [n_points][batch][n_ports][n_ports] each
+        std::vector<int> status;          // [2][n_points][batch]
+    } net;
+    long long n_factor_launches{};  // batched numeric factorisations launched by dc_solve / dc_solve_kept on this engine (its first attempt and every retry group)
     // DC sweep (pe_hip_analyze_dc_sweep, pe_dc_sweep.hpp): an engine of its own holding this circuit with batch (circuit batch) x P -- the
     // points of one pass are extra instances --, the buffers of its kernels and the stored result.  The main engine is only read.
     struct DcSweep
@@ -432,6 +456,7 @@ namespace pe_eng PE_ENG_HIDDEN
         h->ac.sweep.valid = false;
         h->noise.valid = false;
         h->sens.valid = false;
+        h->net.valid = false;
     }
     // budget of a sweep engine's automatic pass size, and the most instances one engine takes (the y extent of a launch grid)
     long long sweep_memory_budget();
@@ -441,6 +466,13 @@ namespace pe_eng PE_ENG_HIDDEN
     // the body of pe_hip_analyze_dc after its argument checks.  clear_status = false: the instances whose status is not OK are left alone
     // (a subset solve: the DC sweep parks the others)
     int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status);
+    // The same point of every instance with the factors of the last dc_solve KEPT: stamp, the two triangular solves, the residual check --
+    // for a linear engine whose matrix values have not changed since that solve (only right-hand-side slots of the value vector have).
+    // Built on the split schedule's iteration with do_factor = false, whatever schedule factored.  Where the safety net has to factor
+    // again (a retry of the instances it flagged; after a re-match, every instance under the new order) that is counted in
+    // n_factor_launches and those factors are the ones a later call keeps.  An engine that keeps no L21 (refactor_every_solve, a
+    // non-linear circuit, an overlay) takes dc_solve.  Clears every instance's status first, leaves the stream synchronised.
+    int dc_solve_kept(pe_hip_engine* h, int mode, pe_hip_run_stats* st);
     // pe_engine_newton.cpp
     bool has_overlay(pe_hip_engine const* h);
     int overlay_call(pe_hip_engine* h, int event, int mode, double t, double dt, int b = 0);

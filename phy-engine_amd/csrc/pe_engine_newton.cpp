@@ -545,7 +545,8 @@ namespace pe_eng PE_ENG_HIDDEN
         return m2_push(h, S, dt, true);
     }
 
-    int run_m2_dc(pe_hip_engine* h, int mode, int& launches, std::vector<int> const* only = nullptr)
+    // do_factor = false: the factors of the last factorisation are kept (dc_solve_kept: a linear engine with unchanged matrix values)
+    int run_m2_dc(pe_hip_engine* h, int mode, int& launches, std::vector<int> const* only = nullptr, bool do_factor = true)
     {
         M2State S;
         int rc = m2_pull(h, S);
@@ -558,7 +559,7 @@ namespace pe_eng PE_ENG_HIDDEN
         HIPCHK(h, hipMemcpy(ls.data(), h->V.last_step, B * sizeof(double), hipMemcpyDeviceToHost));
         std::vector<int> res;
         h->a_static.clear();  // (an OP / DC / TROP stamp overwrites the transient companions in the matrix)
-        rc = m2_point(h, S, mode, S.t[0], ls[0], true, res, launches);
+        rc = m2_point(h, S, mode, S.t[0], ls[0], do_factor, res, launches);
         if(rc != PE_HIP_OK) return rc;
         for(int b = 0; b < B; ++b)
         {
@@ -1309,6 +1310,7 @@ int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status
     h->fact_valid = false;
     h->a_static.clear();  // (an OP / DC / TROP solve stamps other companion values into the matrix, on either schedule)
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    ++h->n_factor_launches;
     if(split_launch(h))
     {
         int launches = 0;
@@ -1327,10 +1329,68 @@ int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status
             int launches = 0;
             for(auto const& g: groups)
             {
+                ++h->n_factor_launches;
                 rc = run_m2_dc(h, mode, launches, &g.second);
                 if(rc != PE_HIP_OK) return rc;
             }
         }
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    rc = collect_stats(h, s0, i0, st);
+    if(st)
+    {
+        st->gpu_ms = ms;
+        st->n_launches = 1;
+        bool const split = h->dominant_launches > 0;
+        st->dominant_ms = split ? h->dominant_ms : ms;
+        st->dominant_launches = split ? h->dominant_launches : 1;
+    }
+    return rc;
+}
+
+
+// dc_solve with the factors of the last factorisation kept (pe_engine_internal.hpp): the split schedule's iteration with do_factor = false
+// on every instance, then the safety net's retries exactly as dc_solve runs them -- those factor.
+int dc_solve_kept(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
+{
+    if(h->hc.nonlinear || !h->V.keep_l21 || has_overlay(h) || h->sym_class != 0) return dc_solve(h, mode, st, true);
+    probe_disarm(h);
+    ac_sweep_invalidate(h);
+    if(st) std::memset(st, 0, sizeof(*st));
+    h->dominant_ms = 0.0;
+    h->dominant_launches = 0;
+    if(h->hc.rows == 0) return PE_HIP_OK;
+    HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(h->hc.batch) * sizeof(int), h->stream));
+    std::vector<long long> s0, i0;
+    int rc = snapshot_counters(h, s0, i0);
+    if(rc != PE_HIP_OK) return rc;
+    h->a_static.clear();
+    long long const rematched0 = h->n_rematched;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    {
+        int launches = 0;
+        rc = run_m2_dc(h, mode, launches, nullptr, false);
+        if(rc != PE_HIP_OK) return rc;
+    }
+    for(int attempt = 0; attempt < 2; ++attempt)
+    {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<std::pair<int, std::vector<int>>> groups;
+        rc = prepare_inaccurate_retry(h, false, 0.0, attempt, s0, 1, groups);
+        if(rc != PE_HIP_OK) return rc;
+        if(groups.empty()) break;
+        int launches = 0;
+        for(auto const& g: groups)
+        {
+            ++h->n_factor_launches;
+            rc = run_m2_dc(h, mode, launches, &g.second);
+            if(rc != PE_HIP_OK) return rc;
+        }
+    }
+    // a re-match gave the engine another pivot order: only the retried instances hold factors of it -- every instance factors again
+    if(h->n_rematched != rematched0) return dc_solve(h, mode, st, true);
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;

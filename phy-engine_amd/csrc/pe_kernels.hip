@@ -27,6 +27,7 @@
 #include "pe_dc_sweep.hpp"
 #include "pe_op_step.hpp"
 #include "pe_noise.hpp"
+#include "pe_net.hpp"
 #include "pe_sens.hpp"
 #include "pe_lte.hpp"
 #include "pe_kernels.hpp"
@@ -1990,6 +1991,92 @@ namespace pe
         if(V.batch <= 0 || (!Z.s && !Z.weight)) return hipSuccess;
         hipLaunchKernelGGL(k_sens_accumulate, dim3(Z.n_chunks, V.batch), dim3(SENS_THREADS), 0, st, M, Z, V.rows);
         if(Z.weight && Z.n_chunks > 1) hipLaunchKernelGGL(k_sens_finish, dim3((V.batch + 255) / 256), dim3(256), 0, st, Z, V.batch);
+        return hipGetLastError();
+    }
+
+    // ---- multi-port network analysis (pe_net.hpp, pe_engine_ac.cpp pe_hip_analyze_net)
+    // port j's selector as the right-hand side of sweep-engine instance blockIdx.y (before the kept-factor solve of that port)
+    __global__ void __launch_bounds__(256) k_net_rhs(DevView V, NetView Z, int j)
+    {
+        net_rhs(GridTeam{}, V, Z, static_cast<int>(blockIdx.y), j);
+    }
+    // column j of the impedance matrices: one thread per (instance, port)
+    struct NetRowTeam
+    {
+        __device__ __forceinline__ int tid() const { return static_cast<int>(threadIdx.x) & (NET_MAX_PORTS - 1); }
+        __device__ __forceinline__ int size() const { return NET_MAX_PORTS; }
+    };
+    __global__ void __launch_bounds__(256) k_net_gather(DevView V, NetView Z, int j)
+    {
+        int const q = static_cast<int>((blockIdx.x * blockDim.x + threadIdx.x) / NET_MAX_PORTS);
+        if(q < V.batch) net_gather(NetRowTeam{}, V, Z, q, j);
+    }
+    // One wavefront per matrix: lane l holds elements (row l / 16, column l % 16) and (row l / 16 + 4, column l % 16) of the 8 x 16
+    // augmented matrix in registers; pivot search, row exchange and row broadcast go by cross-lane shuffles.  No LDS, no scratch, no
+    // atomics: the result of a matrix depends on that matrix alone.
+    struct NetWave
+    {
+        static constexpr int LANES = 64, EPL = 2;
+        __device__ __forceinline__ int lane() const { return static_cast<int>(threadIdx.x) & 63; }
+        // (row and col may differ per lane: both elements of the source lane travel, the reader picks)
+        __device__ __forceinline__ double get(double const (&a)[EPL], int row, int col) const
+        {
+            int const src = ((row & 3) << 4) | col;
+            double const lo = __shfl(a[0], src), hi = __shfl(a[1], src);
+            return (row & 4) ? hi : lo;
+        }
+        __device__ __forceinline__ void argmax(double& m, int& r) const
+        {
+#pragma unroll
+            for(int o = 32; o > 0; o >>= 1)
+            {
+                double const om = __shfl_xor(m, o);
+                int const orow = __shfl_xor(r, o);
+                if(om > m || (om == m && orow < r))
+                {
+                    m = om;
+                    r = orow;
+                }
+            }
+        }
+        __device__ __forceinline__ double nanmax(double v) const
+        {
+#pragma unroll
+            for(int o = 32; o > 0; o >>= 1) v = ac_nanmax(v, __shfl_xor(v, o));
+            return v;
+        }
+        __device__ __forceinline__ bool any(bool f) const { return __any(f ? 1 : 0) != 0; }
+    };
+    __global__ void __launch_bounds__(64 * NET_MATS_PER_GROUP) k_net_convert(int n, int n_mats, double const* __restrict__ z_re, double const* __restrict__ z_im,
+                                                                             double const* __restrict__ z0, double* __restrict__ y_re, double* __restrict__ y_im,
+                                                                             double* __restrict__ s_re, double* __restrict__ s_im, int* __restrict__ y_status,
+                                                                             int* __restrict__ s_status)
+    {
+        long long const m = static_cast<long long>(blockIdx.x) * NET_MATS_PER_GROUP + (threadIdx.x >> 6);
+        if(m >= n_mats) return;  // (the whole wavefront)
+        long long const o = m * n * n;
+        net_convert(NetWave{}, n, z_re + o, z_im + o, z0, y_re ? y_re + o : nullptr, y_im ? y_im + o : nullptr, s_re ? s_re + o : nullptr, s_im ? s_im + o : nullptr,
+                    y_status ? y_status + m : nullptr, s_status ? s_status + m : nullptr);
+    }
+    hipError_t launch_net_rhs(hipStream_t st, DevView const& V, NetView const& Z, int j)
+    {
+        if(V.batch <= 0 || V.rows <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_net_rhs, dim3(sweep_grid(V.rows), V.batch), dim3(256), 0, st, V, Z, j);
+        return hipGetLastError();
+    }
+    hipError_t launch_net_gather(hipStream_t st, DevView const& V, NetView const& Z, int j)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_net_gather, dim3((V.batch * NET_MAX_PORTS + 255) / 256), dim3(256), 0, st, V, Z, j);
+        return hipGetLastError();
+    }
+    hipError_t launch_net_convert(hipStream_t st, int n, int n_mats, double const* z_re, double const* z_im, double const* z0, double* y_re, double* y_im,
+                                  double* s_re, double* s_im, int* y_status, int* s_status)
+    {
+        if(n_mats <= 0) return hipSuccess;
+        if(n < 1 || n > NET_MAX_PORTS) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_net_convert, dim3((n_mats + NET_MATS_PER_GROUP - 1) / NET_MATS_PER_GROUP), dim3(64 * NET_MATS_PER_GROUP), 0, st, n, n_mats, z_re, z_im,
+                           z0, y_re, y_im, s_re, s_im, y_status, s_status);
         return hipGetLastError();
     }
 

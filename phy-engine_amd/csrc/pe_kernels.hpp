@@ -87,6 +87,15 @@ namespace pe
     struct SensView;
     hipError_t launch_sens_rhs(hipStream_t st, DevView const& V, SensView const& Z);
     hipError_t launch_sens_accumulate(hipStream_t st, DevView const& V, DevView const& M, SensView const& Z);
+    // multi-port network analysis (pe_net.hpp): V is the view of the sweep's engine.  rhs: port j's selector into the right-hand-side slots
+    // of every instance and into Z.b0.  gather: column j of Z.z_re / Z.z_im of every instance with Z.point[p] >= 0 from Z.xacc.  convert:
+    // Y, S and their statuses of n_mats matrices [n][n] (device pointers), one wavefront per matrix; any output may be null.  Builds
+    // without HIP: serial host definitions in pe_engine_ac.cpp.
+    struct NetView;
+    hipError_t launch_net_rhs(hipStream_t st, DevView const& V, NetView const& Z, int j);
+    hipError_t launch_net_gather(hipStream_t st, DevView const& V, NetView const& Z, int j);
+    hipError_t launch_net_convert(hipStream_t st, int n, int n_mats, double const* z_re, double const* z_im, double const* z0, double* y_re, double* y_im,
+                                  double* s_re, double* s_im, int* y_status, int* s_status);
     // variable-step transient (pe_lte.hpp): lte: q of the candidate V.x against the history ring + failed / non-finite instances into
     // L.result (cleared first); history_push: V.x of every instance into ring slot `slot`; state_copy: every (dst, src, bytes) of the table
     // (snapshot and roll-back of a step).  Builds without HIP: serial host definitions in pe_engine_newton.cpp.

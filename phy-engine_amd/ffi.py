@@ -36,12 +36,15 @@ EXPORTS = [
     "pe_hip_set_tr_method", "pe_hip_get_tr_method", "pe_hip_get_tr_history", "pe_hip_sweep_set_tr_method",
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_get_sens_params", "pe_hip_analyze_sens", "pe_hip_get_sens",
+    "pe_hip_analyze_net", "pe_hip_get_net", "pe_hip_get_net_status", "pe_hip_convert_net",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
     "pe_hip_analyze_op_stepping", "pe_hip_get_op_step_state", "pe_hip_get_op_step_log", "pe_hip_sweep_operating_point_stepping",
     "pe_hip_get_static_fronts", "pe_hip_get_static_skip_stats", "pe_hip_get_static_skip_refinement_stats",
     "pe_hip_get_matrix_ac", "pe_hip_get_ac_pass_size", "pe_hip_get_ac_analysis_omega",
 ]
 DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
+NET_MAX_PORTS = 8
+NET_Z, NET_Y, NET_S = 0, 1, 2
 # pe_hip_tr_method
 TR_TRAP, TR_BE, TR_GEAR2 = 0, 1, 2
 _TR_NAMES = {"trap": TR_TRAP, "be": TR_BE, "gear2": TR_GEAR2, "gear": TR_GEAR2}
@@ -269,6 +272,19 @@ class SensStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class NetControl(C.Structure):
+    _fields_ = [("n_ports", C.c_int), ("port_pos", C.POINTER(C.c_int)), ("port_neg", C.POINTER(C.c_int)), ("z0", C.POINTER(C.c_double))]
+
+
+class NetStats(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_ports", C.c_int), ("n_passes", C.c_int), ("points_per_pass", C.c_int), ("n_analyses", C.c_int),
+                ("n_factorisations", C.c_int), ("n_solves", C.c_int), ("n_refine_rounds", C.c_int), ("n_retried_points", C.c_int),
+                ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -328,6 +344,10 @@ def lib():
         l.pe_hip_get_sens_params.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 4
         l.pe_hip_analyze_sens.argtypes = [C.c_void_p, C.POINTER(SensControl), C.POINTER(C.c_int), C.POINTER(SensStats)]
         l.pe_hip_get_sens.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_analyze_net.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(NetControl), C.POINTER(C.c_int), C.POINTER(NetStats)]
+        l.pe_hip_get_net.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_get_net_status.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        l.pe_hip_convert_net.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 7 + [C.POINTER(C.c_int)] * 2
         l.pe_hip_set_dc_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(DcSweepControl), C.POINTER(C.c_int), C.POINTER(DcSweepStats)]
         l.pe_hip_get_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -899,6 +919,53 @@ class Engine(_Probes):
         d["rc"] = rc
         return s, rss, status[:n], d
 
+    def analyze_net(self, omegas, ports, z0=None, check=True):
+        """Impedance, admittance and scattering matrices between the ports -- (pos, neg) pairs of rows of x, -1: ground -- at every omega of
+        `omegas` (rad/s, any order) on the device (pe_hip_analyze_net); z0: reference resistance per port (None: 50 ohm each).  Returns
+        (Z, Y, S complex [n_points][batch][n][n], entry [i][j] the response at port i to an excitation at port j, y_status and s_status
+        [n_points][batch], point_status [n_points], stats dict with the return code under 'rc'); a failed point and a matrix without
+        inverse read NaN."""
+        w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        pr = np.ascontiguousarray(ports, dtype=np.int32).reshape(-1, 2)
+        pos, neg = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        n, npt = len(pos), len(w)
+        ref = None if z0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(z0, dtype=np.float64), (n,)))
+        status = np.zeros(max(npt, 1), dtype=np.int32)
+        st = NetStats()
+        ctl = NetControl(n, _ip(pos) if n else None, _ip(neg) if n else None, _dp(ref) if ref is not None else None)
+        rc = lib().pe_hip_analyze_net(self._h, npt, _dp(w), C.byref(ctl), _ip(status), C.byref(st))
+        if check:
+            self._chk(rc)
+        mats = [np.full((npt, self.batch, n, n), np.nan + 0j) for _ in range(3)]
+        ys = np.full((npt, self.batch), rc, dtype=np.int32)
+        ss = np.full((npt, self.batch), rc, dtype=np.int32)
+        if rc not in (ERR_ARG, ERR_NO_DEVICE, ERR_INTERNAL) and npt and n:
+            re, im = np.empty((npt, self.batch, n, n)), np.empty((npt, self.batch, n, n))
+            for which in (NET_Z, NET_Y, NET_S):
+                self._chk(lib().pe_hip_get_net(self._h, which, 0, npt, 0, self.batch, _dp(re), _dp(im)))
+                mats[which] = re + 1j * im
+            self._chk(lib().pe_hip_get_net_status(self._h, 0, npt, 0, self.batch, _ip(ys), _ip(ss)))
+        d = st.asdict()
+        d["rc"] = rc
+        return mats[0], mats[1], mats[2], ys, ss, status[:npt], d
+
+    def convert_net(self, Z, z0=None):
+        """Y = Z^-1 and S (power waves, real reference resistances z0, None: 50 ohm each) of caller-supplied impedance matrices
+        Z complex [..., n, n] by the device kernel of analyze_net (pe_hip_convert_net; needs no circuit).  Returns (Y, S, y_status,
+        s_status) shaped like Z / its leading dimensions; a matrix without inverse reads NaN with status ERR_SINGULAR."""
+        Zc = np.asarray(Z, dtype=np.complex128)
+        n = Zc.shape[-1]
+        if Zc.ndim < 2 or Zc.shape[-2] != n:
+            raise ValueError("Z must be [..., n, n]")
+        lead = Zc.shape[:-2]
+        m = int(np.prod(lead, dtype=np.int64))
+        zr, zi = np.ascontiguousarray(Zc.real).reshape(m, n, n), np.ascontiguousarray(Zc.imag).reshape(m, n, n)
+        ref = None if z0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(z0, dtype=np.float64), (n,)))
+        out = [np.empty((m, n, n)) for _ in range(4)]
+        ys, ss = np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1), dtype=np.int32)
+        self._chk(lib().pe_hip_convert_net(self._h, n, m, _dp(zr), _dp(zi), _dp(ref) if ref is not None else None, *[_dp(o) for o in out], _ip(ys), _ip(ss)))
+        return ((out[0] + 1j * out[1]).reshape(Zc.shape), (out[2] + 1j * out[3]).reshape(Zc.shape), ys[:m].reshape(lead), ss[:m].reshape(lead))
+
     def phase_clocks_coop(self, instance=0):
         """Per-layout breakdown of the cooperative fronts (see pe_hip_get_phase_clocks_ex), microseconds / counts."""
         t = np.zeros(48, dtype=np.int64)
@@ -1039,3 +1106,33 @@ class Sweep(_Probes):
         x = np.empty((count, self.rows))
         self._chk(lib().pe_hip_sweep_get_solution(self._h, int(first), int(count), _dp(x)))
         return x
+
+
+def write_touchstone(path, freqs_hz, S, z0):
+    """Touchstone v1 file (.sNp, `# Hz S RI R z0`) of a scattering sweep S complex [n_points][n][n] at freqs_hz; z0: the reference
+    resistance per port (or one number).  Version 1 has ONE reference: ValueError unless all z0 are equal.  Data order of the format:
+    a 2-port writes S11 S21 S12 S22 on one line; every other n writes the matrix row by row (at most four pairs per line for n >= 3)."""
+    f = np.asarray(freqs_hz, dtype=np.float64).reshape(-1)
+    Sc = np.asarray(S, dtype=np.complex128)
+    if Sc.ndim != 3 or Sc.shape[0] != len(f) or Sc.shape[1] != Sc.shape[2]:
+        raise ValueError("S must be [n_points][n][n] with one matrix per frequency")
+    n = Sc.shape[1]
+    ref = np.broadcast_to(np.asarray(z0, dtype=np.float64), (n,))
+    if not np.all(ref == ref[0]) or not np.isfinite(ref[0]) or not ref[0] > 0.0:
+        raise ValueError("Touchstone v1 has one reference resistance: all z0 must be equal, finite and positive")
+    num = lambda v: repr(float(v))
+    pair = lambda z: num(z.real) + " " + num(z.imag)
+    with open(path, "w") as fh:
+        fh.write("! %d-port scattering parameters, %d points\n" % (n, len(f)))
+        fh.write("# Hz S RI R %s\n" % num(ref[0]))
+        for k in range(len(f)):
+            M = Sc[k]
+            if n == 2:
+                fh.write(" ".join([num(f[k]), pair(M[0, 0]), pair(M[1, 0]), pair(M[0, 1]), pair(M[1, 1])]) + "\n")
+                continue
+            first = True
+            for i in range(n):
+                for c0 in range(0, n, 4):
+                    body = " ".join(pair(M[i, j]) for j in range(c0, min(n, c0 + 4)))
+                    fh.write((num(f[k]) + " " if first else "  ") + body + "\n")
+                    first = False

@@ -1432,6 +1432,67 @@ namespace phy_engine
             return rc == PE_HIP_OK || gpu_fail();
         }
 
+        // Multi-port network analysis (pe_hip_analyze_net, include/pe_hip.h): the impedance, admittance and scattering matrices between the
+        // ports -- node pairs (positive, negative; null: ground) -- at every omega, at the circuit's operating point, which is prepared and
+        // solved first (OP).  z0: one reference resistance per port, or null for 50 ohm each.  get_net(which, point) gives the n x n matrix of
+        // that point row by row (entry [i][j]: the response at port i to an excitation at port j), NaN where it does not exist;
+        // net_y_status / net_s_status per point say whether the inverse behind Y / S exists; last_net_stats the rest.
+        struct net_port
+        {
+            ::phy_engine::model::node_t const* pos{};
+            ::phy_engine::model::node_t const* neg{};
+        };
+        ::std::vector<::std::complex<double>> net_results[3]{};  // PE_HIP_NET_Z / _Y / _S: [n_points][n_ports][n_ports]
+        ::std::vector<int> net_y_status{}, net_s_status{}, net_point_status{};
+        int net_ports{};
+        pe_hip_net_stats last_net_stats{};
+        [[nodiscard]] ::std::complex<double> const* get_net(int which, ::std::size_t point) const noexcept
+        {
+            auto const nn = static_cast<::std::size_t>(net_ports) * static_cast<::std::size_t>(net_ports);
+            if(which < PE_HIP_NET_Z || which > PE_HIP_NET_S || nn == 0 || (point + 1) * nn > net_results[which].size()) return nullptr;
+            return net_results[which].data() + point * nn;
+        }
+        [[nodiscard]] bool analyze_net(::std::vector<double> const& omegas, ::std::vector<net_port> const& ports, double const* z0 = nullptr) noexcept
+        {
+            for(auto& r: net_results) r.clear();
+            net_y_status.clear();
+            net_s_status.clear();
+            net_point_status.clear();
+            net_ports = 0;
+            last_net_stats = pe_hip_net_stats{};
+            auto const saved = at;
+            at = analyze_type::OP;
+            bool ok = prepare();
+            if(ok) ok = solve();
+            at = saved;
+            if(!ok || !gpu_ || !loaded_) return false;
+            auto row = [&](::phy_engine::model::node_t const* n) { return (!n || n == &nl.ground_node) ? -1 : static_cast<int>(n->node_index); };
+            ::std::vector<int> pos, neg;
+            for(auto const& p: ports)
+            {
+                pos.push_back(row(p.pos));
+                neg.push_back(row(p.neg));
+            }
+            int const n = static_cast<int>(ports.size()), np = static_cast<int>(omegas.size());
+            net_point_status.assign(omegas.size(), 0);
+            pe_hip_net_control const ctl{n, pos.data(), neg.data(), z0};
+            int const rc = pe_hip_analyze_net(gpu_, np, omegas.data(), &ctl, net_point_status.data(), &last_net_stats);
+            if(rc == PE_HIP_ERR_ARG || rc == PE_HIP_ERR_NO_DEVICE || rc == PE_HIP_ERR_INTERNAL) return gpu_fail();
+            net_ports = n;
+            auto const total = omegas.size() * static_cast<::std::size_t>(n) * static_cast<::std::size_t>(n);
+            ::std::vector<double> re(total), im(total);
+            for(int which = PE_HIP_NET_Z; which <= PE_HIP_NET_S; ++which)
+            {
+                if(pe_hip_get_net(gpu_, which, 0, np, 0, 1, re.data(), im.data()) != PE_HIP_OK) return gpu_fail();
+                net_results[which].resize(total);
+                for(::std::size_t k = 0; k < total; ++k) net_results[which][k] = {re[k], im[k]};
+            }
+            net_y_status.assign(omegas.size(), 0);
+            net_s_status.assign(omegas.size(), 0);
+            if(pe_hip_get_net_status(gpu_, 0, np, 0, 1, net_y_status.data(), net_s_status.data()) != PE_HIP_OK) return gpu_fail();
+            return rc == PE_HIP_OK || gpu_fail();
+        }
+
         // Operating point with gmin / source stepping (pe_hip_analyze_op_stepping, include/pe_hip.h): what analyze() does for OP, DC or the
         // operating point of TROP, with the continuation of the header where the direct Newton iteration fails.  method: PE_HIP_STEP_GMIN,
         // PE_HIP_STEP_SOURCE or PE_HIP_STEP_AUTO.  The solution is scattered into the nodes and branches as after analyze();
