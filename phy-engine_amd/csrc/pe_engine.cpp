@@ -350,10 +350,7 @@ void pe_hip_destroy(pe_hip_engine* h)
     (void)hipSetDevice(h->device);
     ac_sweep_drop(h);
     dc_sweep_drop(h);
-    if(h->ac.d_xacc) (void)hipFree(h->ac.d_xacc);
-    if(h->ac.d_b0) (void)hipFree(h->ac.d_b0);
-    if(h->ac.d_worst) (void)hipFree(h->ac.d_worst);
-    if(h->ac.eng) pe_hip_destroy(h->ac.eng);
+    h->ac.drop();
     (void)hipStreamSynchronize(h->stream);
     if(h->graphs) pe::m2_graphs_destroy(h->graphs);  // (captured launch sequences: before the memory they point into and their stream go)
     h->fourier.pool.release();
@@ -560,14 +557,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     h->sym_pool.release();
     ac_sweep_drop(h);
     dc_sweep_drop(h);
-    if(h->ac.eng)
-    {
-        if(h->ac.d_xacc) (void)hipFree(h->ac.d_xacc);
-        if(h->ac.d_b0) (void)hipFree(h->ac.d_b0);
-        if(h->ac.d_worst) (void)hipFree(h->ac.d_worst);
-        pe_hip_destroy(h->ac.eng);
-        h->ac = pe_hip_engine::Ac{};
-    }
+    h->ac.drop();
     if(!pe::build_circuit(n_nodes, n_branches, batch, n_tables, tables, static_cast<int>(h->drv_node.size()), h->drv_node.data(),
                           h->drv_volt.data(), h->hc, h->overlay.empty() ? nullptr : &h->overlay))
         return fail(h, PE_HIP_ERR_ARG, "load_circuit: " + h->hc.error);

@@ -101,43 +101,97 @@ namespace pe_eng
         return 256ll << 20;
     }
 
+    // The forward sweep of h->ac (its single-point engine goes with h->ac.drop()), then the noise, sensitivity and network analyses: each
+    // its system with both engines first, then -- by assigning a fresh state, whose pools free what they hold -- tables, buffers, result.
     void ac_sweep_drop(pe_hip_engine* h)
     {
-        auto& W = h->ac.sweep;
-        sweep_engine_drop(W);
-        W.circ_pool.release();
-        W.res_pool.release();
-        if(W.d_keep) (void)hipFree(W.d_keep);
-        W = pe_hip_engine::Ac::Sweep{};
-        // the noise analysis: its adjoint system with both engines, the source table, the result
-        auto& Z = h->noise;
-        sweep_engine_drop(Z.sys.sweep);
-        if(Z.sys.eng) pe_hip_destroy(Z.sys.eng);
-        Z.sys.sweep.circ_pool.release();
-        Z.src_pool.release();
-        Z.pass_pool.release();
-        Z.res_pool.release();
-        Z = pe_hip_engine::Noise{};
-        // the sensitivity analysis likewise
-        auto& Y = h->sens;
-        sweep_engine_drop(Y.sys.sweep);
-        if(Y.sys.eng) pe_hip_destroy(Y.sys.eng);
-        Y.sys.sweep.circ_pool.release();
-        Y.tab_pool.release();
-        Y.out_pool.release();
-        Y.pass_pool.release();
-        Y.res_pool.release();
-        Y = pe_hip_engine::Sens{};
-        // the network analysis likewise
-        auto& T = h->net;
-        sweep_engine_drop(T.sys.sweep);
-        if(T.sys.eng) pe_hip_destroy(T.sys.eng);
-        T.sys.sweep.circ_pool.release();
-        T.port_pool.release();
-        T.res_pool.release();
-        T = pe_hip_engine::Net{};
+        sweep_engine_drop(h->ac.sweep);
+        h->ac.sweep = pe_hip_engine::Ac::Sweep{};
+        h->noise.sys.drop();
+        h->noise = pe_hip_engine::Noise{};
+        h->sens.sys.drop();
+        h->sens = pe_hip_engine::Sens{};
+        h->net.sys.drop();
+        h->net = pe_hip_engine::Net{};
+    }
+
+    int KeptRows::set(pe_hip_engine* h, char const* name, int n_rows, int const* rows_in)
+    {
+        if(!h->loaded || n_rows < 0 || (n_rows > 0 && !rows_in)) return fail(h, PE_HIP_ERR_ARG, std::string(name) + ": bad arguments or no circuit");
+        for(int k = 0; k < n_rows; ++k)
+            if(rows_in[k] < 0 || rows_in[k] >= h->hc.rows) return fail(h, PE_HIP_ERR_ARG, std::string(name) + ": row out of range");
+        rows.assign(rows_in, rows_in + n_rows);
+        on_device = false;
+        return PE_HIP_OK;
+    }
+
+    int KeptRows::upload(pe_hip_engine* h, int const*& keep_out)
+    {
+        if(on_device) return PE_HIP_OK;
+        keep_out = nullptr;
+        if(rows.size() > cap)
+        {
+            if(d_keep) (void)hipFree(d_keep);
+            d_keep = nullptr;
+            cap = 0;
+            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&d_keep), rows.size() * sizeof(int)));
+            cap = rows.size();
+        }
+        if(!rows.empty())
+        {
+            HIPCHK(h, hipMemcpy(d_keep, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+            keep_out = d_keep;
+        }
+        on_device = true;
+        return PE_HIP_OK;
+    }
+
+    int stored_window(pe_hip_engine* h, char const* name, char const* what, char const* noun, bool valid, int stored_batch, int n_items, int first, int n,
+                      int first_instance, int count)
+    {
+        if(!valid || stored_batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, std::string(name) + ": no " + what + " yet");
+        bool const items_ok = !noun || (first >= 0 && n >= 0 && first <= n_items - n);
+        if(!items_ok || first_instance < 0 || count < 0 || first_instance > stored_batch - count)
+            return fail(h, PE_HIP_ERR_ARG, std::string(name) + ": " + (noun ? std::string(noun) + " or " : std::string()) + "instances out of range");
+        return PE_HIP_OK;
+    }
+
+    int operating_point_status(pe_hip_engine* h, int& b_out, int& status_out)
+    {
+        int const B = h->hc.batch;
+        std::vector<int> inst(static_cast<size_t>(B), 0);
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
+        auto const bad = std::find_if(inst.begin(), inst.end(), [](int s) { return s != PE_HIP_OK; });
+        b_out = bad == inst.end() ? -1 : static_cast<int>(bad - inst.begin());
+        status_out = bad == inst.end() ? PE_HIP_OK : *bad;
+        return PE_HIP_OK;
+    }
+
+    int read_operating_point(pe_hip_engine* h, pe::AcOperatingPoint& op)
+    {
+        auto const& hc = h->hc;
+        size_t const B = static_cast<size_t>(hc.batch);
+        op.d_geq.resize(B * hc.nD());
+        op.dv.resize(B * hc.dv_len);
+        op.rl_engaged.resize(B * hc.nRl());
+        if(!op.d_geq.empty()) HIPCHK(h, hipMemcpy(op.d_geq.data(), h->V.d_geq, op.d_geq.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if(!op.dv.empty()) HIPCHK(h, hipMemcpy(op.dv.data(), h->V.dv, op.dv.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
+        return PE_HIP_OK;
     }
 }  // namespace pe_eng
+
+// Engines are destroyed BEFORE the buffers their kernels read are freed: pe_hip_destroy synchronises the engine's stream first.
+void pe_hip_engine::Ac::drop()
+{
+    sweep_engine_drop(sweep);
+    if(eng) pe_hip_destroy(eng);
+    if(d_xacc) (void)hipFree(d_xacc);
+    if(d_b0) (void)hipFree(d_b0);
+    if(d_worst) (void)hipFree(d_worst);
+    *this = Ac{};  // (the sweep's pools and kept rows free what they hold)
+}
 
 extern "C" {
 
@@ -156,12 +210,7 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
     int const B = hc.batch;
     // the linearisation the small-signal stamps refer to
     pe::AcOperatingPoint op;
-    op.d_geq.resize(static_cast<size_t>(B) * hc.nD());
-    op.dv.resize(static_cast<size_t>(B) * hc.dv_len);
-    op.rl_engaged.resize(static_cast<size_t>(B) * hc.nRl());
-    if(!op.d_geq.empty()) HIPCHK(h, hipMemcpy(op.d_geq.data(), h->V.d_geq, op.d_geq.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if(!op.dv.empty()) HIPCHK(h, hipMemcpy(op.dv.data(), h->V.dv, op.dv.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if(int const rc = read_operating_point(h, op); rc != PE_HIP_OK) return rc;
     auto const& ah = A.circ.hc;
     std::vector<double> dv(static_cast<size_t>(B) * ah.dv_len);
     if(has_overlay(h))
@@ -293,14 +342,10 @@ int pe_hip_get_solution_ac(pe_hip_engine* h, int first, int count, double* re, d
 
 int pe_hip_set_ac_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows)
 {
-    if(!h || !h->loaded || n_rows < 0 || (n_rows > 0 && !rows)) return h ? fail(h, PE_HIP_ERR_ARG, "set_ac_sweep_rows: bad arguments or no circuit") : PE_HIP_ERR_ARG;
-    for(int k = 0; k < n_rows; ++k)
-        if(rows[k] < 0 || rows[k] >= h->hc.rows) return fail(h, PE_HIP_ERR_ARG, "set_ac_sweep_rows: row out of range");
-    auto& W = h->ac.sweep;
-    W.rows.assign(rows, rows + n_rows);
-    W.rows_on_device = false;
-    W.valid = false;  // (the stored result has the layout of the rows it was made with)
-    return PE_HIP_OK;
+    if(!h) return PE_HIP_ERR_ARG;
+    int const rc = h->ac.sweep.kept.set(h, "set_ac_sweep_rows", n_rows, rows);
+    if(rc == PE_HIP_OK) h->ac.sweep.valid = false;  // (the stored result has the layout of the rows it was made with)
+    return rc;
 }
 
 }  // extern "C"
@@ -309,15 +354,25 @@ namespace
 {
     bool numerical(int rc) { return rc == PE_HIP_ERR_SINGULAR || rc == PE_HIP_ERR_INACCURATE || rc == PE_HIP_ERR_NO_CONVERGENCE; }
 
+    // Where point i of a sweep lives: doubles [i * per_point, (i + 1) * per_point) of the device array `dev`, and of the host result from
+    // offset `host` on.  check: a value that is not finite fails the point.  collect: copied back after the passes (and again after a retry
+    // of the point alone) -- the network analysis' converted planes are not: their caller fills them later.
+    struct ResultBlock
+    {
+        double const* dev;
+        size_t host, per_point;
+        bool check, collect;
+    };
+
     // What the forward sweep and the noise call do differently around the shared body below.
     struct SweepHooks
     {
         std::string name;                                       // prefix of the error messages
-        std::function<int(int P)> prepare;                      // the batched engine stands with P points per pass: result buffers on the device
+        std::function<int(int P)> prepare;                      // the batched engine stands with P points per pass: result buffers on the device (blocks[k].dev)
         std::function<int(pe_hip_engine* E)> epilogue;          // end of a pass, after refinement: gather the kept rows / accumulate the noise
-        std::function<int(std::vector<char>& failed)> collect;  // after the passes: the one device-to-host copy; marks the points that are not finite
+        std::vector<double>* res = nullptr;                     // the host result and its layout: the body copies it back after the passes, fails the
+        std::vector<ResultBlock> blocks;                        // points that are not finite, reads a retried point again, blanks a failed one
         std::function<int(int i)> single;                       // forward sweep: failed point i on the single-point path (sets its status)
-        std::function<int(int i, bool& finite)> reread;         // noise (no `single`): point i was retried alone in a pass of its own -- read it back
         std::function<int(pe_hip_engine* E)> after_fill;        // sensitivity only (else empty): the value vectors of a pass stand -- its own right-hand sides
         char const* pass_knob = "AC_SWEEP_POINTS";              // the knob that sets the points per pass
         // network analysis only: n_rhs right-hand sides per pass on ONE factorisation -- the first as everywhere, then next_rhs(E, j) writes
@@ -328,6 +383,29 @@ namespace
         int* n_factorisations = nullptr;                        // (counted from the engine's n_factor_launches)
         int* n_solves = nullptr;                                // kept-factor solves
     };
+
+    // point i of the host result: every checked value finite / every block NaN
+    bool point_finite(SweepHooks const& K, int i)
+    {
+        for(auto const& blk: K.blocks)
+            for(size_t k = 0; blk.check && k < blk.per_point; ++k)
+                if(!std::isfinite((*K.res)[blk.host + i * blk.per_point + k])) return false;
+        return true;
+    }
+    void point_blank(SweepHooks const& K, int i)
+    {
+        for(auto const& blk: K.blocks) std::fill_n(K.res->begin() + blk.host + i * blk.per_point, blk.per_point, std::nan(""));
+    }
+    // device -> host of the collected blocks: points [first, first + n)
+    int points_read(pe_hip_engine* h, SweepHooks const& K, int first, int n)
+    {
+        for(auto const& blk: K.blocks)
+        {
+            size_t const o = first * blk.per_point, len = n * blk.per_point;
+            if(blk.collect && len > 0) HIPCHK(h, hipMemcpy(K.res->data() + blk.host + o, blk.dev + o, len * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return PE_HIP_OK;
+    }
 
     // The body of a frequency sweep on the real-equivalent system A (forward: h->ac, adjoint: h->noise.sys): base vectors, bands,
     // representative values, pass size, the batched engine, the passes with their refinement, and the bookkeeping of the points that
@@ -348,12 +426,7 @@ namespace
         std::vector<int> scale(static_cast<size_t>(rhs0), pe::AC_CONST);
         {
             pe::AcOperatingPoint op;
-            op.d_geq.resize(static_cast<size_t>(B) * hc.nD());
-            op.dv.resize(static_cast<size_t>(B) * hc.dv_len);
-            op.rl_engaged.resize(static_cast<size_t>(B) * hc.nRl());
-            if(!op.d_geq.empty()) HIPCHK(h, hipMemcpy(op.d_geq.data(), h->V.d_geq, op.d_geq.size() * sizeof(double), hipMemcpyDeviceToHost));
-            if(!op.dv.empty()) HIPCHK(h, hipMemcpy(op.dv.data(), h->V.dv, op.dv.size() * sizeof(double), hipMemcpyDeviceToHost));
-            if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
+            if(int const rc = read_operating_point(h, op); rc != PE_HIP_OK) return rc;
             std::vector<double> one(static_cast<size_t>(ah.dv_len), 0.0);
             for(int b = 0; b < B; ++b)
             {
@@ -427,42 +500,37 @@ namespace
 
         // ---- points per pass: the knob, else what fits the memory budget; never more than the largest band needs
         int const knob_p = knob(h, K.pass_knob, 0);
-        long long cap = knob_p > 0 ? knob_p : 0;
-        if(cap == 0)
+        if(knob_p <= 0 && W.bytes_per_instance == 0)
         {
-            if(W.bytes_per_instance == 0)
+            // bytes of one instance of the AC system incl. its factor storage, from the single-point engine.  When that has no symbolic
+            // analysis yet one is made on a band's values and forgotten again: pe_hip_analyze_ac then analyses as it always did.  A band
+            // whose values cannot be analysed (a singular system at its omega) says nothing about the others: the next band is tried, and
+            // when none can be analysed the sweep runs one point per pass -- its bands then fail one by one into the single-point path.
+            bool const had = A.eng->sym_class >= 0;
+            int src = had ? PE_HIP_OK : PE_HIP_ERR_SINGULAR;
+            for(size_t k = 0; !had && k < bands.size() && src != PE_HIP_OK; ++k)
             {
-                // bytes of one instance of the AC system incl. its factor storage, from the single-point engine.  When that has no symbolic
-                // analysis yet one is made on a band's values and forgotten again: pe_hip_analyze_ac then analyses as it always did.  A band
-                // whose values cannot be analysed (a singular system at its omega) says nothing about the others: the next band is tried, and
-                // when none can be analysed the sweep runs one point per pass -- its bands then fail one by one into the single-point path.
-                bool const had = A.eng->sym_class >= 0;
-                int src = had ? PE_HIP_OK : PE_HIP_ERR_SINGULAR;
-                for(size_t k = 0; !had && k < bands.size() && src != PE_HIP_OK; ++k)
-                {
-                    representative(omegas[order[bands[k].first]], A.eng->sym_values_override);
-                    A.eng->sym_class = -1;
-                    src = ensure_symbolic(A.eng, false, 0.0);
-                    if(src != PE_HIP_OK && !numerical(src))
-                    {
-                        A.eng->sym_class = -1;
-                        A.sym_omega = -1.0;
-                        return fail(h, src, K.name + " (sizing): " + A.eng->err);
-                    }
-                }
-                pe_hip_info info{};
-                int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng, &info) : PE_HIP_OK;
-                if(!had)
+                representative(omegas[order[bands[k].first]], A.eng->sym_values_override);
+                A.eng->sym_class = -1;
+                src = ensure_symbolic(A.eng, false, 0.0);
+                if(src != PE_HIP_OK && !numerical(src))
                 {
                     A.eng->sym_class = -1;
                     A.sym_omega = -1.0;
+                    return fail(h, src, K.name + " (sizing): " + A.eng->err);
                 }
-                if(rc != PE_HIP_OK) return fail(h, rc, K.name + " (sizing): " + A.eng->err);
-                if(src == PE_HIP_OK) W.bytes_per_instance = std::max<long long>(1, info.bytes_per_instance);
             }
-            cap = W.bytes_per_instance > 0 ? sweep_memory_budget() / (W.bytes_per_instance * static_cast<long long>(B)) : 1;
+            pe_hip_info info{};
+            int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng, &info) : PE_HIP_OK;
+            if(!had)
+            {
+                A.eng->sym_class = -1;
+                A.sym_omega = -1.0;
+            }
+            if(rc != PE_HIP_OK) return fail(h, rc, K.name + " (sizing): " + A.eng->err);
+            if(src == PE_HIP_OK) W.bytes_per_instance = std::max<long long>(1, info.bytes_per_instance);
         }
-        cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
+        long long const cap = sweep_pass_cap(knob_p, W.bytes_per_instance, B);
         int const P = static_cast<int>(std::min<long long>(cap, largest_band));
         if(!W.eng || W.P != P)
             if(int const rc = sweep_engine_build(h, A, P, K.name, K.keep_factors); rc != PE_HIP_OK) return rc;
@@ -595,7 +663,9 @@ namespace
         }
         // ---- one copy of the results of every point, then the points that failed in their batch: the single-point path (forward sweep), or
         // alone in one pass of one point under an analysis on that point's own values (noise)
-        if(int const rc = K.collect(failed); rc != PE_HIP_OK) return rc;
+        if(int const rc = points_read(h, K, 0, n_points); rc != PE_HIP_OK) return rc;
+        for(int i = 0; i < n_points; ++i)
+            if(!failed[i] && !point_finite(K, i)) failed[i] = 1;
         for(int i = 0; i < n_points; ++i)
         {
             if(!failed[i]) continue;
@@ -617,10 +687,12 @@ namespace
             failed[i] = 0;
             if(int const rc = run_pass(&i, 1); rc != PE_HIP_OK) return rc;
             for(int b = 0; b < B && pst[i] == PE_HIP_OK; ++b) pst[i] = inst_status[static_cast<size_t>(b) * P];
-            bool finite = true;
-            if(int const rc = K.reread(i, finite); rc != PE_HIP_OK) return rc;
-            if(pst[i] == PE_HIP_OK && !finite) pst[i] = PE_HIP_ERR_INACCURATE;
+            if(int const rc = points_read(h, K, i, 1); rc != PE_HIP_OK) return rc;
+            if(pst[i] == PE_HIP_OK && !point_finite(K, i)) pst[i] = PE_HIP_ERR_INACCURATE;
         }
+        // a failed point reads NaN
+        for(int i = 0; i < n_points; ++i)
+            if(pst[i] != PE_HIP_OK) point_blank(K, i);
         return PE_HIP_OK;
     }
 }  // namespace
@@ -643,7 +715,7 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
     auto& W = A.sweep;
     W.valid = false;
     int const B = hc.batch, N = hc.rows;
-    int const K = W.rows.empty() ? N : static_cast<int>(W.rows.size());
+    int const K = W.kept.rows.empty() ? N : static_cast<int>(W.kept.rows.size());
     pe_hip_ac_sweep_stats S{};
     S.n_points = n_points;
     std::vector<int> pst(static_cast<size_t>(n_points), PE_HIP_OK);
@@ -676,7 +748,7 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
                 for(int k = 0; k < K; ++k)
                 {
                     double const* x2 = &A.x[static_cast<size_t>(b) * 2 * N];
-                    int const r = W.rows.empty() ? k : W.rows[k];
+                    int const r = W.kept.rows.empty() ? k : W.kept.rows[k];
                     re[static_cast<size_t>(b) * K + k] = x2[r];
                     im[static_cast<size_t>(b) * K + k] = x2[N + r];
                 }
@@ -700,53 +772,21 @@ int pe_hip_analyze_ac_sweep(pe_hip_engine* h, int n_points, const double* omegas
     SweepHooks hooks;
     hooks.name = "analyze_ac_sweep";
     // result buffer and kept rows on the device
+    hooks.res = &W.res;
+    hooks.blocks = {{nullptr, 0, static_cast<size_t>(B) * K, true, true}, {nullptr, plane, static_cast<size_t>(B) * K, true, true}};
     hooks.prepare = [&](int) -> int
     {
-        if(W.res_len != plane || !W.V.res_re)
-        {
-            W.res_pool.release();
-            W.V.res_re = W.V.res_im = nullptr;
-            W.res_len = 0;
-            HIPCHK(h, W.res_pool.alloc(W.V.res_re, plane, false));
-            HIPCHK(h, W.res_pool.alloc(W.V.res_im, plane, false));
-            W.res_len = plane;
-        }
-        if(!W.rows_on_device)
-        {
-            // (a buffer of its own, reused while it is large enough: a caller alternating row selections allocates nothing)
-            W.V.keep = nullptr;
-            if(W.rows.size() > W.keep_cap)
-            {
-                if(W.d_keep) (void)hipFree(W.d_keep);
-                W.d_keep = nullptr;
-                W.keep_cap = 0;
-                HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&W.d_keep), W.rows.size() * sizeof(int)));
-                W.keep_cap = W.rows.size();
-            }
-            if(!W.rows.empty())
-            {
-                HIPCHK(h, hipMemcpy(W.d_keep, W.rows.data(), W.rows.size() * sizeof(int), hipMemcpyHostToDevice));
-                W.V.keep = W.d_keep;
-            }
-            W.rows_on_device = true;
-        }
+        HIPCHK(h, W.d_re.ensure(plane, false));
+        HIPCHK(h, W.d_im.ensure(plane, false));
+        hooks.blocks[0].dev = W.V.res_re = W.d_re.p;
+        hooks.blocks[1].dev = W.V.res_im = W.d_im.p;
+        if(int const rc = W.kept.upload(h, W.V.keep); rc != PE_HIP_OK) return rc;
         W.V.n_keep = K;
         return PE_HIP_OK;
     };
     hooks.epilogue = [&](pe_hip_engine* E) -> int
     {
         HIPCHK(h, pe::launch_ac_sweep_gather(E->stream, E->V, W.V));
-        return PE_HIP_OK;
-    };
-    // one copy of the kept rows of every point
-    hooks.collect = [&](std::vector<char>& failed) -> int
-    {
-        HIPCHK(h, hipMemcpy(W.res.data(), W.V.res_re, plane * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(W.res.data() + plane, W.V.res_im, plane * sizeof(double), hipMemcpyDeviceToHost));
-        size_t const per_point = static_cast<size_t>(B) * K;
-        for(int i = 0; i < n_points; ++i)
-            for(size_t k = 0; k < per_point && !failed[i]; ++k)
-                if(!std::isfinite(W.res[i * per_point + k]) || !std::isfinite(W.res[plane + i * per_point + k])) failed[i] = 1;
         return PE_HIP_OK;
     };
     hooks.single = single;
@@ -758,9 +798,9 @@ int pe_hip_get_ac_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
 {
     if(!h || !h->loaded || !re || !im) return PE_HIP_ERR_ARG;
     auto const& W = h->ac.sweep;
-    if(!W.valid || W.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_ac_sweep: no AC sweep yet");
-    if(first_point < 0 || n_points < 0 || first_point > W.n_points - n_points || first_instance < 0 || count < 0 || first_instance > W.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_ac_sweep: points or instances out of range");
+    if(int const rc = stored_window(h, "get_ac_sweep", "AC sweep", "points", W.valid, W.batch, W.n_points, first_point, n_points, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     size_t const K = static_cast<size_t>(W.n_keep), plane = static_cast<size_t>(W.n_points) * W.batch * K;
     for(int i = 0; i < n_points; ++i)
     {
@@ -883,17 +923,25 @@ namespace
         Z.table_on_device = false;
     }
 
-    // right-hand-side lists of the adjoint system for an output pair: what build_ac_circuit makes of it (a new pair changes only these)
-    void noise_selector_lists(int rows2, int out_pos, int out_neg, std::vector<int>& b_ptr, std::vector<int>& b_src)
+    // The right-hand side of system A becomes the selector of the pair (pos, neg): its lists as build_ac_circuit makes them for an output
+    // pair (a new pair changes only these), and what the sweep engine holds of the old ones dropped -- base vectors, scale flags and the
+    // lists are uploaded again by the sweep body.
+    void select_rhs(pe_hip_engine::Ac& A, int pos, int neg)
     {
-        b_ptr.assign(static_cast<size_t>(rows2) + 1, 0);
-        b_src.clear();
+        int const rows2 = A.circ.hc.rows;
+        A.b_ptr0.assign(static_cast<size_t>(rows2) + 1, 0);
+        A.b_src0.clear();
         for(int r = 0; r < rows2; ++r)
         {
-            if(r == out_pos) b_src.push_back((pe::DV_ONE << 1) | 0);
-            if(r == out_neg) b_src.push_back((pe::DV_ONE << 1) | 1);
-            b_ptr[static_cast<size_t>(r) + 1] = static_cast<int>(b_src.size());
+            if(r == pos) A.b_src0.push_back((pe::DV_ONE << 1) | 0);
+            if(r == neg) A.b_src0.push_back((pe::DV_ONE << 1) | 1);
+            A.b_ptr0[static_cast<size_t>(r) + 1] = static_cast<int>(A.b_src0.size());
         }
+        auto& W = A.sweep;
+        W.circ_pool.release();
+        W.V.base = nullptr;
+        W.V.scale = nullptr;
+        W.V.b_ptr0 = W.V.b_src0 = nullptr;
     }
 }  // namespace
 
@@ -923,29 +971,25 @@ int pe_hip_analyze_noise(pe_hip_engine* h, int n_points, const double* omegas, c
     bool const keep = ctl->keep_contributions != 0;
 
     // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
+    int bad = -1, bad_status = PE_HIP_OK;
+    if(int const rc = operating_point_status(h, bad, bad_status); rc != PE_HIP_OK) return rc;
+    if(bad >= 0)
     {
-        std::vector<int> inst(static_cast<size_t>(B), 0);
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
-        for(int b = 0; b < B; ++b)
+        noise_table_build(h);
+        Z.res.assign(static_cast<size_t>(n_points) * B * (1 + (keep ? Z.src.size() : 0)), std::nan(""));
+        Z.integrated.assign(static_cast<size_t>(B), std::nan(""));
+        Z.n_points = n_points;
+        Z.batch = B;
+        Z.kept = keep;
+        Z.have_density = false;  // (k_noise_sources has not run: the density getter reads NaN like the points)
+        Z.valid = true;
+        if(point_status) std::fill(point_status, point_status + n_points, bad_status);
+        if(stats)
         {
-            if(inst[static_cast<size_t>(b)] == PE_HIP_OK) continue;
-            noise_table_build(h);
-            Z.res.assign(static_cast<size_t>(n_points) * B * (1 + (keep ? Z.src.size() : 0)), std::nan(""));
-            Z.integrated.assign(static_cast<size_t>(B), std::nan(""));
-            Z.n_points = n_points;
-            Z.batch = B;
-            Z.kept = keep;
-            Z.have_density = false;  // (k_noise_sources has not run: the density getter reads NaN like the points)
-            Z.valid = true;
-            if(point_status) std::fill(point_status, point_status + n_points, inst[static_cast<size_t>(b)]);
-            if(stats)
-            {
-                stats->n_points = n_points;
-                stats->n_sources = static_cast<int>(Z.src.size());
-            }
-            return fail(h, inst[static_cast<size_t>(b)], "analyze_noise: instance " + std::to_string(b) + " has no operating point (its last analysis failed)");
+            stats->n_points = n_points;
+            stats->n_sources = static_cast<int>(Z.src.size());
         }
+        return fail(h, bad_status, "analyze_noise: instance " + std::to_string(bad) + " has no operating point (its last analysis failed)");
     }
 
     // ---- the adjoint system for this output pair
@@ -955,13 +999,7 @@ int pe_hip_analyze_noise(pe_hip_engine* h, int n_points, const double* omegas, c
         if(int const rc = ensure_ac_built(h, A, &adj); rc != PE_HIP_OK) return rc;
     }
     else if(!Z.have_pair || Z.out_pos != out_pos || Z.out_neg != out_neg)
-    {
-        noise_selector_lists(A.circ.hc.rows, out_pos, out_neg, A.b_ptr0, A.b_src0);
-        W.circ_pool.release();  // (base vectors, scale flags and the lists: uploaded again by the sweep body)
-        W.V.base = nullptr;
-        W.V.scale = nullptr;
-        W.V.b_ptr0 = W.V.b_src0 = nullptr;
-    }
+        select_rhs(A, out_pos, out_neg);
     Z.have_pair = true;
     Z.out_pos = out_pos;
     Z.out_neg = out_neg;
@@ -996,31 +1034,22 @@ int pe_hip_analyze_noise(pe_hip_engine* h, int n_points, const double* omegas, c
 
     SweepHooks hooks;
     hooks.name = "analyze_noise";
+    // (a point is its row of densities -- what is not finite there fails it -- and, when they are kept, its block of contributions)
+    hooks.res = &Z.res;
+    hooks.blocks = {{nullptr, 0, static_cast<size_t>(B), true, true}};
+    if(keep) hooks.blocks.push_back({nullptr, n_psd, static_cast<size_t>(B) * n_src, false, true});
     hooks.prepare = [&](int P) -> int
     {
-        if(Z.res_len != total || !Z.d_res)
-        {
-            Z.res_pool.release();
-            Z.d_res = nullptr;
-            Z.res_len = 0;
-            HIPCHK(h, Z.res_pool.alloc(Z.d_res, total, false));
-            Z.res_len = total;
-        }
-        HIPCHK(h, hipMemset(Z.d_res, 0xff, total * sizeof(double)));  // (all ones: a NaN -- a point no pass wrote reads NaN)
-        size_t const need = static_cast<size_t>(B) * P * Z.V.n_chunks;
-        if(Z.partial_len != need || !Z.V.partial)
-        {
-            Z.pass_pool.release();
-            Z.V.partial = nullptr;
-            Z.partial_len = 0;
-            HIPCHK(h, Z.pass_pool.alloc(Z.V.partial, need));
-            Z.partial_len = need;
-        }
+        HIPCHK(h, Z.d_res.ensure(total, false));
+        HIPCHK(h, Z.d_res.fill_nan());
+        HIPCHK(h, Z.partial.ensure(static_cast<size_t>(B) * P * Z.V.n_chunks));
+        Z.V.partial = Z.partial.p;
         Z.V.P = P;
         Z.V.xacc = W.V.xacc;
         Z.V.point = W.V.point;
-        Z.V.psd = Z.d_res;
-        Z.V.contrib = keep ? Z.d_res + n_psd : nullptr;
+        hooks.blocks[0].dev = Z.V.psd = Z.d_res.p;
+        Z.V.contrib = keep ? Z.d_res.p + n_psd : nullptr;
+        if(keep) hooks.blocks[1].dev = Z.V.contrib;
         return PE_HIP_OK;
     };
     hooks.epilogue = [&](pe_hip_engine* E) -> int
@@ -1028,34 +1057,8 @@ int pe_hip_analyze_noise(pe_hip_engine* h, int n_points, const double* omegas, c
         HIPCHK(h, pe::launch_noise_accumulate(E->stream, E->V, Z.V));
         return PE_HIP_OK;
     };
-    hooks.collect = [&](std::vector<char>& failed) -> int
-    {
-        HIPCHK(h, hipMemcpy(Z.res.data(), Z.d_res, total * sizeof(double), hipMemcpyDeviceToHost));
-        for(int i = 0; i < n_points; ++i)
-            for(int b = 0; b < B && !failed[i]; ++b)
-                if(!std::isfinite(Z.res[static_cast<size_t>(i) * B + b])) failed[i] = 1;
-        return PE_HIP_OK;
-    };
-    hooks.reread = [&](int i, bool& finite) -> int
-    {
-        size_t const o = static_cast<size_t>(i) * B;
-        HIPCHK(h, hipMemcpy(&Z.res[o], Z.d_res + o, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
-        if(keep && n_src > 0)
-            HIPCHK(h, hipMemcpy(&Z.res[n_psd + o * n_src], Z.d_res + n_psd + o * n_src, static_cast<size_t>(B) * n_src * sizeof(double), hipMemcpyDeviceToHost));
-        finite = true;
-        for(int b = 0; b < B; ++b) finite = finite && std::isfinite(Z.res[o + b]);
-        return PE_HIP_OK;
-    };
     if(int const rc = sweep_body(h, A, n_points, omegas, pst, S, hooks); rc != PE_HIP_OK) return rc;
 
-    // a failed point reads NaN
-    for(int i = 0; i < n_points; ++i)
-    {
-        if(pst[i] == PE_HIP_OK) continue;
-        size_t const o = static_cast<size_t>(i) * B;
-        std::fill(Z.res.begin() + o, Z.res.begin() + o + B, std::nan(""));
-        if(keep) std::fill(Z.res.begin() + n_psd + o * n_src, Z.res.begin() + n_psd + (o + B) * n_src, std::nan(""));
-    }
     // ---- integrated noise: trapezoidal rule in linear f = omega / 2 pi over the distinct points, ascending, on the host in that fixed order
     {
         std::vector<int> order(static_cast<size_t>(n_points));
@@ -1103,9 +1106,9 @@ int pe_hip_get_noise(pe_hip_engine* h, int first_point, int n_points, int first_
 {
     if(!h || !h->loaded || !psd) return PE_HIP_ERR_ARG;
     auto const& Z = h->noise;
-    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_noise: no noise analysis yet");
-    if(first_point < 0 || n_points < 0 || first_point > Z.n_points - n_points || first_instance < 0 || count < 0 || first_instance > Z.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_noise: points or instances out of range");
+    if(int const rc = stored_window(h, "get_noise", "noise analysis", "points", Z.valid, Z.batch, Z.n_points, first_point, n_points, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     if(contrib && !Z.kept) return fail(h, PE_HIP_ERR_ARG, "get_noise: the contributions were not kept (pe_hip_noise_control.keep_contributions)");
     size_t const n_src = Z.src.size(), n_psd = static_cast<size_t>(Z.n_points) * Z.batch;
     for(int i = 0; i < n_points && count > 0; ++i)
@@ -1139,8 +1142,9 @@ int pe_hip_get_noise_source_density(pe_hip_engine* h, int first_instance, int co
 {
     if(!h || !h->loaded || !s) return PE_HIP_ERR_ARG;
     auto const& Z = h->noise;
-    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_noise_source_density: no noise analysis yet");
-    if(first_instance < 0 || count < 0 || first_instance > Z.batch - count) return fail(h, PE_HIP_ERR_ARG, "get_noise_source_density: instances out of range");
+    if(int const rc = stored_window(h, "get_noise_source_density", "noise analysis", nullptr, Z.valid, Z.batch, 0, 0, 0, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     size_t const n_src = Z.src.size();
     if(!Z.have_density) std::fill(s, s + static_cast<size_t>(count) * n_src, std::nan(""));
     else if(count > 0 && n_src > 0)
@@ -1155,8 +1159,9 @@ int pe_hip_get_noise_integrated(pe_hip_engine* h, int first_instance, int count,
 {
     if(!h || !h->loaded || !v2) return PE_HIP_ERR_ARG;
     auto const& Z = h->noise;
-    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_noise_integrated: no noise analysis yet");
-    if(first_instance < 0 || count < 0 || first_instance > Z.batch - count) return fail(h, PE_HIP_ERR_ARG, "get_noise_integrated: instances out of range");
+    if(int const rc = stored_window(h, "get_noise_integrated", "noise analysis", nullptr, Z.valid, Z.batch, 0, 0, 0, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     std::copy(Z.integrated.begin() + first_instance, Z.integrated.begin() + first_instance + count, v2);
     return PE_HIP_OK;
 }
@@ -1319,20 +1324,15 @@ int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* ctl, int* o
     };
 
     // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
-    {
-        std::vector<int> inst(static_cast<size_t>(B), 0);
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
-        for(int b = 0; b < B; ++b)
-        {
-            if(inst[static_cast<size_t>(b)] == PE_HIP_OK) continue;
-            Y.res.assign(total, std::nan(""));
-            std::vector<int> const pst(static_cast<size_t>(n_out), inst[static_cast<size_t>(b)]);
-            publish(&pst, pe_hip_ac_sweep_stats{});
-            return fail(h, inst[static_cast<size_t>(b)], "analyze_sens: instance " + std::to_string(b) + " has no operating point (its last analysis failed)");
-        }
-    }
+    int bad = -1, bad_status = PE_HIP_OK;
+    if(int const rc = operating_point_status(h, bad, bad_status); rc != PE_HIP_OK) return rc;
     Y.res.assign(total, std::nan(""));
+    if(bad >= 0)
+    {
+        std::vector<int> const pst(static_cast<size_t>(n_out), bad_status);
+        publish(&pst, pe_hip_ac_sweep_stats{});
+        return fail(h, bad_status, "analyze_sens: instance " + std::to_string(bad) + " has no operating point (its last analysis failed)");
+    }
     pe_hip_ac_sweep_stats S{};
     std::vector<int> pst(static_cast<size_t>(n_out), PE_HIP_OK);
     if(N == 0)
@@ -1364,16 +1364,10 @@ int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* ctl, int* o
     if(!hc.d_raw.empty()) HIPCHK(h, hipMemcpy(Y.d_draw, hc.d_raw.data(), hc.d_raw.size() * sizeof(double), hipMemcpyHostToDevice));
     if(!hc.gen_par.empty()) HIPCHK(h, hipMemcpy(Y.d_graw, hc.gen_par.data(), hc.gen_par.size() * sizeof(double), hipMemcpyHostToDevice));
     if(weighted && n_par > 0) HIPCHK(h, hipMemcpy(Y.d_weight, ctl->weight, static_cast<size_t>(n_par) * sizeof(double), hipMemcpyHostToDevice));
-    if(Y.out_len < static_cast<size_t>(n_out))
-    {
-        Y.out_pool.release();
-        Y.out_len = 0;
-        HIPCHK(h, Y.out_pool.alloc(Y.d_out_pos, static_cast<size_t>(n_out), false));
-        HIPCHK(h, Y.out_pool.alloc(Y.d_out_neg, static_cast<size_t>(n_out), false));
-        Y.out_len = static_cast<size_t>(n_out);
-    }
-    HIPCHK(h, hipMemcpy(Y.d_out_pos, ctl->out_pos, static_cast<size_t>(n_out) * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(Y.d_out_neg, ctl->out_neg, static_cast<size_t>(n_out) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, Y.d_out_pos.ensure_at_least(static_cast<size_t>(n_out), false));
+    HIPCHK(h, Y.d_out_neg.ensure_at_least(static_cast<size_t>(n_out), false));
+    HIPCHK(h, hipMemcpy(Y.d_out_pos.p, ctl->out_pos, static_cast<size_t>(n_out) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(Y.d_out_neg.p, ctl->out_neg, static_cast<size_t>(n_out) * sizeof(int), hipMemcpyHostToDevice));
     Y.V.n_par = n_par;
     Y.V.n_chunks = std::max(1, (n_par + pe::SENS_CHUNK - 1) / pe::SENS_CHUNK);
     Y.V.n_inst = B;
@@ -1384,38 +1378,29 @@ int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* ctl, int* o
     Y.V.d_raw = Y.d_draw;
     Y.V.g_raw = Y.d_graw;
     Y.V.weight = weighted ? Y.d_weight : nullptr;
-    Y.V.out_pos = Y.d_out_pos;
-    Y.V.out_neg = Y.d_out_neg;
+    Y.V.out_pos = Y.d_out_pos.p;
+    Y.V.out_neg = Y.d_out_neg.p;
 
     std::vector<double> const omegas(static_cast<size_t>(n_out), 0.0);  // every output is a point at omega = 0: one band, one analysis
     SweepHooks hooks;
     hooks.name = "analyze_sens";
     hooks.pass_knob = "SENS_OUTPUTS";
+    // what belongs to output i in the result buffer: its rss row (weighted), its block of sensitivities (kept)
+    hooks.res = &Y.res;
+    if(weighted) hooks.blocks.push_back({nullptr, 0, static_cast<size_t>(B), true, true});
+    if(keep) hooks.blocks.push_back({nullptr, n_rss, static_cast<size_t>(B) * n_par, true, true});
     hooks.prepare = [&](int P) -> int
     {
-        if(Y.res_len != total || !Y.d_res)
-        {
-            Y.res_pool.release();
-            Y.d_res = nullptr;
-            Y.res_len = 0;
-            HIPCHK(h, Y.res_pool.alloc(Y.d_res, total, false));
-            Y.res_len = total;
-        }
-        HIPCHK(h, hipMemset(Y.d_res, 0xff, total * sizeof(double)));  // (all ones: a NaN -- an output no pass wrote reads NaN)
-        size_t const need = static_cast<size_t>(B) * P * Y.V.n_chunks;
-        if(Y.partial_len != need || !Y.V.partial)
-        {
-            Y.pass_pool.release();
-            Y.V.partial = nullptr;
-            Y.partial_len = 0;
-            HIPCHK(h, Y.pass_pool.alloc(Y.V.partial, need));
-            Y.partial_len = need;
-        }
+        HIPCHK(h, Y.d_res.ensure(total, false));
+        HIPCHK(h, Y.d_res.fill_nan());
+        HIPCHK(h, Y.partial.ensure(static_cast<size_t>(B) * P * Y.V.n_chunks));
+        Y.V.partial = Y.partial.p;
         Y.V.P = P;
         Y.V.xacc = W.V.xacc;
         Y.V.point = W.V.point;
-        Y.V.rss = weighted ? Y.d_res : nullptr;
-        Y.V.s = keep ? Y.d_res + n_rss : nullptr;
+        Y.V.rss = weighted ? Y.d_res.p : nullptr;
+        Y.V.s = keep ? Y.d_res.p + n_rss : nullptr;
+        for(auto& blk: hooks.blocks) blk.dev = Y.d_res.p + blk.host;
         return PE_HIP_OK;
     };
     hooks.after_fill = [&](pe_hip_engine* E) -> int
@@ -1428,42 +1413,7 @@ int pe_hip_analyze_sens(pe_hip_engine* h, const pe_hip_sens_control* ctl, int* o
         HIPCHK(h, pe::launch_sens_accumulate(E->stream, E->V, h->V, Y.V));
         return PE_HIP_OK;
     };
-    // what belongs to output i in the result buffer: its rss row, its block of sensitivities
-    auto finite_output = [&](int i)
-    {
-        size_t const o = static_cast<size_t>(i) * B;
-        for(size_t k = 0; weighted && k < static_cast<size_t>(B); ++k)
-            if(!std::isfinite(Y.res[o + k])) return false;
-        for(size_t k = 0; keep && k < static_cast<size_t>(B) * n_par; ++k)
-            if(!std::isfinite(Y.res[n_rss + o * n_par + k])) return false;
-        return true;
-    };
-    hooks.collect = [&](std::vector<char>& failed) -> int
-    {
-        if(total > 0) HIPCHK(h, hipMemcpy(Y.res.data(), Y.d_res, total * sizeof(double), hipMemcpyDeviceToHost));
-        for(int i = 0; i < n_out; ++i)
-            if(!failed[i] && !finite_output(i)) failed[i] = 1;
-        return PE_HIP_OK;
-    };
-    hooks.reread = [&](int i, bool& finite) -> int
-    {
-        size_t const o = static_cast<size_t>(i) * B;
-        if(weighted) HIPCHK(h, hipMemcpy(&Y.res[o], Y.d_res + o, static_cast<size_t>(B) * sizeof(double), hipMemcpyDeviceToHost));
-        if(keep && n_par > 0)
-            HIPCHK(h, hipMemcpy(&Y.res[n_rss + o * n_par], Y.d_res + n_rss + o * n_par, static_cast<size_t>(B) * n_par * sizeof(double), hipMemcpyDeviceToHost));
-        finite = finite_output(i);
-        return PE_HIP_OK;
-    };
     if(int const rc = sweep_body(h, A, n_out, omegas.data(), pst, S, hooks); rc != PE_HIP_OK) return rc;
-
-    // a failed output reads NaN
-    for(int i = 0; i < n_out; ++i)
-    {
-        if(pst[i] == PE_HIP_OK) continue;
-        size_t const o = static_cast<size_t>(i) * B;
-        if(weighted) std::fill(Y.res.begin() + o, Y.res.begin() + o + B, std::nan(""));
-        if(keep) std::fill(Y.res.begin() + n_rss + o * n_par, Y.res.begin() + n_rss + (o + B) * n_par, std::nan(""));
-    }
     publish(&pst, S);
     for(int i = 0; i < n_out; ++i)
         if(pst[i] != PE_HIP_OK) return fail(h, pst[i], "analyze_sens: output " + std::to_string(i) + " failed");
@@ -1474,9 +1424,9 @@ int pe_hip_get_sens(pe_hip_engine* h, int first_output, int n_outputs, int first
 {
     if(!h || !h->loaded || (!s && !rss)) return PE_HIP_ERR_ARG;
     auto const& Y = h->sens;
-    if(!Y.valid || Y.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_sens: no sensitivity analysis yet");
-    if(first_output < 0 || n_outputs < 0 || first_output > Y.n_outputs - n_outputs || first_instance < 0 || count < 0 || first_instance > Y.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_sens: outputs or instances out of range");
+    if(int const rc = stored_window(h, "get_sens", "sensitivity analysis", "outputs", Y.valid, Y.batch, Y.n_outputs, first_output, n_outputs, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     if(s && !Y.kept) return fail(h, PE_HIP_ERR_ARG, "get_sens: the sensitivities were not kept (pe_hip_sens_control.keep_sensitivities)");
     if(rss && !Y.weighted) return fail(h, PE_HIP_ERR_ARG, "get_sens: no weighted sum was formed (pe_hip_sens_control.weight)");
     size_t const n_par = Y.par.size(), n_rss = Y.weighted ? static_cast<size_t>(Y.n_outputs) * Y.batch : 0;
@@ -1561,28 +1511,27 @@ int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, con
             stats->gpu_ms = S.gpu_ms;
         }
     };
-    // what belongs to point i: its block of every plane, its statuses
+    // what belongs to point i: its block of every plane -- the sweep body copies and checks the two of Z; Y and S are made after it --, its statuses
+    SweepHooks hooks;
+    hooks.res = &Z.res;
+    for(size_t pl = 0; pl < 6; ++pl) hooks.blocks.push_back({nullptr, pl * plane, static_cast<size_t>(B) * nn, pl < 2, pl < 2});
     auto blank = [&](int i, int status)
     {
-        for(int pl = 0; pl < 6; ++pl) std::fill_n(Z.res.begin() + pl * plane + static_cast<size_t>(i) * B * nn, static_cast<size_t>(B) * nn, std::nan(""));
+        point_blank(hooks, i);
         for(int w = 0; w < 2; ++w) std::fill_n(Z.status.begin() + w * n_mats + static_cast<size_t>(i) * B, static_cast<size_t>(B), status);
     };
     Z.res.assign(6 * plane, std::nan(""));
     Z.status.assign(2 * n_mats, PE_HIP_OK);
 
     // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
+    int bad = -1, bad_status = PE_HIP_OK;
+    if(int const rc = operating_point_status(h, bad, bad_status); rc != PE_HIP_OK) return rc;
+    if(bad >= 0)
     {
-        std::vector<int> inst(static_cast<size_t>(B), 0);
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(inst.data(), h->V.status, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToHost));
-        for(int b = 0; b < B; ++b)
-        {
-            if(inst[static_cast<size_t>(b)] == PE_HIP_OK) continue;
-            std::fill(pst.begin(), pst.end(), inst[static_cast<size_t>(b)]);
-            for(int i = 0; i < n_points; ++i) blank(i, inst[static_cast<size_t>(b)]);
-            publish();
-            return fail(h, inst[static_cast<size_t>(b)], "analyze_net: instance " + std::to_string(b) + " has no operating point (its last analysis failed)");
-        }
+        std::fill(pst.begin(), pst.end(), bad_status);
+        for(int i = 0; i < n_points; ++i) blank(i, bad_status);
+        publish();
+        return fail(h, bad_status, "analyze_net: instance " + std::to_string(bad) + " has no operating point (its last analysis failed)");
     }
 
     // ---- the forward system; its right-hand-side lists select port 0 (the circuit's own AC sources are switched off)
@@ -1592,14 +1541,7 @@ int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, con
         if(int const rc = ensure_ac_built(h, A); rc != PE_HIP_OK) return rc;
         Z.have_port0 = false;
     }
-    if(!Z.have_port0 || Z.pos0 != pos0 || Z.neg0 != neg0)
-    {
-        noise_selector_lists(A.circ.hc.rows, pos0, neg0, A.b_ptr0, A.b_src0);
-        W.circ_pool.release();  // (base vectors, scale flags and the lists: uploaded again by the sweep body)
-        W.V.base = nullptr;
-        W.V.scale = nullptr;
-        W.V.b_ptr0 = W.V.b_src0 = nullptr;
-    }
+    if(!Z.have_port0 || Z.pos0 != pos0 || Z.neg0 != neg0) select_rhs(A, pos0, neg0);
     Z.have_port0 = true;
     Z.pos0 = pos0;
     Z.neg0 = neg0;
@@ -1620,7 +1562,6 @@ int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, con
     }
 
     int cur = 0;  // the port whose right-hand side the pass is solving
-    SweepHooks hooks;
     hooks.name = "analyze_net";
     hooks.pass_knob = "NET_POINTS";
     hooks.n_rhs = n;
@@ -1630,19 +1571,15 @@ int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, con
     hooks.prepare = [&](int P) -> int
     {
         // (the planes are sized by n_points x batch x n^2, the statuses by n_points x batch: two calls can agree in one and not in the other)
-        if(Z.res_len != plane || Z.status_len != 2 * n_mats || !Z.d_res || !Z.d_status)
+        if(Z.d_res.len != 6 * plane || Z.d_status.len != 2 * n_mats)
         {
-            Z.res_pool.release();
-            Z.d_res = nullptr;
-            Z.d_status = nullptr;
-            Z.res_len = 0;
-            Z.status_len = 0;
-            HIPCHK(h, Z.res_pool.alloc(Z.d_res, 6 * plane, false));
-            HIPCHK(h, Z.res_pool.alloc(Z.d_status, 2 * n_mats, false));
-            Z.res_len = plane;
-            Z.status_len = 2 * n_mats;
+            Z.d_res.release();
+            Z.d_status.release();
         }
-        HIPCHK(h, hipMemset(Z.d_res, 0xff, 6 * plane * sizeof(double)));  // (all ones: a NaN -- a point no pass wrote reads NaN)
+        HIPCHK(h, Z.d_res.ensure(6 * plane, false));
+        HIPCHK(h, Z.d_status.ensure(2 * n_mats, false));
+        HIPCHK(h, Z.d_res.fill_nan());
+        for(auto& blk: hooks.blocks) blk.dev = Z.d_res.p + blk.host;
         Z.V.n_ports = n;
         Z.V.P = P;
         Z.V.n_inst = B;
@@ -1654,8 +1591,8 @@ int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, con
         Z.V.point = W.V.point;
         Z.V.xacc = W.V.xacc;
         Z.V.b0 = W.V.b0;
-        Z.V.z_re = Z.d_res;
-        Z.V.z_im = Z.d_res + plane;
+        Z.V.z_re = Z.d_res.p;
+        Z.V.z_im = Z.d_res.p + plane;
         cur = 0;
         return PE_HIP_OK;
     };
@@ -1671,43 +1608,21 @@ int pe_hip_analyze_net(pe_hip_engine* h, int n_points, const double* omegas, con
         if(cur == n - 1) cur = 0;
         return PE_HIP_OK;
     };
-    auto finite_point = [&](int i)
-    {
-        size_t const o = static_cast<size_t>(i) * B * nn;
-        for(size_t k = 0; k < static_cast<size_t>(B) * nn; ++k)
-            if(!std::isfinite(Z.res[o + k]) || !std::isfinite(Z.res[plane + o + k])) return false;
-        return true;
-    };
-    hooks.collect = [&](std::vector<char>& failed) -> int
-    {
-        HIPCHK(h, hipMemcpy(Z.res.data(), Z.d_res, 2 * plane * sizeof(double), hipMemcpyDeviceToHost));
-        for(int i = 0; i < n_points; ++i)
-            if(!failed[i] && !finite_point(i)) failed[i] = 1;
-        return PE_HIP_OK;
-    };
-    hooks.reread = [&](int i, bool& finite) -> int
-    {
-        size_t const o = static_cast<size_t>(i) * B * nn;
-        HIPCHK(h, hipMemcpy(&Z.res[o], Z.d_res + o, static_cast<size_t>(B) * nn * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(&Z.res[plane + o], Z.d_res + plane + o, static_cast<size_t>(B) * nn * sizeof(double), hipMemcpyDeviceToHost));
-        finite = finite_point(i);
-        return PE_HIP_OK;
-    };
     if(int const rc = sweep_body(h, A, n_points, omegas, pst, S, hooks); rc != PE_HIP_OK) return rc;
 
     // ---- Y and S of every (point, instance) on the device, from the impedance matrices as they stand there
     {
-        double* const d = Z.d_res;
+        double* const d = Z.d_res.p;
         HIPCHK(h, hipEventRecord(h->ev0, h->stream));
         HIPCHK(h, pe::launch_net_convert(h->stream, n, static_cast<int>(n_mats), d, d + plane, Z.d_z0, d + 2 * plane, d + 3 * plane, d + 4 * plane, d + 5 * plane,
-                                         Z.d_status, Z.d_status + n_mats));
+                                         Z.d_status.p, Z.d_status.p + n_mats));
         HIPCHK(h, hipEventRecord(h->ev1, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
         S.gpu_ms += ms;
         HIPCHK(h, hipMemcpy(Z.res.data() + 2 * plane, d + 2 * plane, 4 * plane * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(Z.status.data(), Z.d_status, 2 * n_mats * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(Z.status.data(), Z.d_status.p, 2 * n_mats * sizeof(int), hipMemcpyDeviceToHost));
     }
     // a failed point reads NaN and carries its status
     for(int i = 0; i < n_points; ++i)
@@ -1722,9 +1637,9 @@ int pe_hip_get_net(pe_hip_engine* h, int which, int first_point, int n_points, i
 {
     if(!h || !h->loaded || !re || !im || which < PE_HIP_NET_Z || which > PE_HIP_NET_S) return PE_HIP_ERR_ARG;
     auto const& Z = h->net;
-    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_net: no network analysis yet");
-    if(first_point < 0 || n_points < 0 || first_point > Z.n_points - n_points || first_instance < 0 || count < 0 || first_instance > Z.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_net: points or instances out of range");
+    if(int const rc = stored_window(h, "get_net", "network analysis", "points", Z.valid, Z.batch, Z.n_points, first_point, n_points, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     size_t const nn = static_cast<size_t>(Z.n_ports) * Z.n_ports, plane = static_cast<size_t>(Z.n_points) * Z.batch * nn;
     for(int i = 0; i < n_points && count > 0; ++i)
     {
@@ -1739,9 +1654,9 @@ int pe_hip_get_net_status(pe_hip_engine* h, int first_point, int n_points, int f
 {
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;
     auto const& Z = h->net;
-    if(!Z.valid || Z.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_net_status: no network analysis yet");
-    if(first_point < 0 || n_points < 0 || first_point > Z.n_points - n_points || first_instance < 0 || count < 0 || first_instance > Z.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_net_status: points or instances out of range");
+    if(int const rc = stored_window(h, "get_net_status", "network analysis", "points", Z.valid, Z.batch, Z.n_points, first_point, n_points, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     size_t const n_mats = static_cast<size_t>(Z.n_points) * Z.batch;
     for(int i = 0; i < n_points && count > 0; ++i)
     {

@@ -5,7 +5,8 @@
 //   pe_engine_policy.cpp      launch geometry by batch size, symbolic analysis + its upload (the PHY_ENGINE_HIP_* knobs live here)
 //   pe_engine_newton.cpp      host-driven Newton / transient loops of the split schedule, residual safety net, pe_hip_analyze_tr / _dc
 //   pe_engine_checkpoint.cpp  pe_hip_checkpoint_*
-//   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep, pe_hip_analyze_noise / pe_hip_get_noise*
+//   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep, pe_hip_analyze_noise / pe_hip_get_noise*,
+//                             pe_hip_analyze_sens / pe_hip_get_sens*, pe_hip_analyze_net / pe_hip_get_net*; the helpers of every stored result (KeptRows, stored_window)
 //   pe_engine_seam.cpp        pe_hip_solve_csr_complex (the complex twin of the solver seam)
 #pragma once
 // (the helpers below are shared between the engine's translation units only: not exported from libpe_hip.so)
@@ -39,6 +40,7 @@
 
 #include <map>
 #include <thread>
+#include <utility>
 
 namespace pe_eng  // (Pool is a member type of the engine object: default visibility, header-only)
 {
@@ -49,7 +51,25 @@ namespace pe_eng  // (Pool is a member type of the engine object: default visibi
     {
         std::vector<void*> ptrs;
         size_t bytes{};
+        Pool() = default;
+        Pool(Pool&& o) noexcept : ptrs(std::move(o.ptrs)), bytes(o.bytes) { o.forget(); }
+        Pool& operator=(Pool&& o) noexcept  // (what this pool held is freed: a state struct is reset by assigning a fresh one)
+        {
+            if(this != &o)
+            {
+                release();
+                ptrs = std::move(o.ptrs);
+                bytes = o.bytes;
+                o.forget();
+            }
+            return *this;
+        }
         ~Pool() { release(); }
+        void forget()
+        {
+            ptrs.clear();
+            bytes = 0;
+        }
         void release()
         {
             for(void* p: ptrs) (void)hipFree(p);
@@ -84,6 +104,61 @@ namespace pe_eng  // (Pool is a member type of the engine object: default visibi
             out = p;
             return e;
         }
+    };
+
+    // a device buffer sized by the call that fills it: kept while the next call asks for the same length
+    template <class T>
+    struct DevBuf
+    {
+        Pool pool;
+        T* p{};
+        size_t len{};
+        void release()
+        {
+            pool.release();
+            p = nullptr;
+            len = 0;
+        }
+        hipError_t ensure(size_t n, bool zero = true)
+        {
+            if(len == n && p) return hipSuccess;
+            release();
+            hipError_t const e = pool.alloc(p, n, zero);
+            if(e == hipSuccess) len = n;
+            return e;
+        }
+        hipError_t ensure_at_least(size_t n, bool zero = true) { return len >= n && p ? hipSuccess : ensure(n, zero); }
+        hipError_t fill_nan() { return hipMemset(p, 0xff, len * sizeof(T)); }  // (all ones: a NaN -- what no pass wrote reads NaN)
+    };
+
+    // the rows of x a sweep keeps (pe_hip_set_ac_sweep_rows / pe_hip_set_dc_sweep_rows; empty: all rows) and their device copy -- a buffer of
+    // its own, reused while it is large enough: a caller alternating row selections allocates nothing
+    struct KeptRows
+    {
+        std::vector<int> rows;
+        int* d_keep{};
+        size_t cap{};
+        bool on_device{};  // d_keep holds `rows`
+        KeptRows() = default;
+        KeptRows(KeptRows&& o) noexcept { *this = std::move(o); }
+        KeptRows& operator=(KeptRows&& o) noexcept
+        {
+            if(this != &o)
+            {
+                if(d_keep) (void)hipFree(d_keep);
+                rows = std::move(o.rows);
+                d_keep = std::exchange(o.d_keep, nullptr);
+                cap = std::exchange(o.cap, 0);
+                on_device = std::exchange(o.on_device, false);
+            }
+            return *this;
+        }
+        ~KeptRows()
+        {
+            if(d_keep) (void)hipFree(d_keep);
+        }
+        int set(pe_hip_engine* h, char const* name, int n_rows, int const* rows_in);  // (the owner's stored result is the caller's to invalidate)
+        int upload(pe_hip_engine* h, int const*& keep_out);                            // keep_out: the device copy, nullptr for all rows
     };
 }  // namespace pe_eng
 using pe_eng::Pool;
@@ -225,18 +300,15 @@ struct pe_hip_engine
             bool b0_valid{};                  // V.b0 holds the right-hand sides of the last pass as stamped (pe_hip_get_matrix_ac)
             Pool pass_pool;                   // sized by batch x P: xacc, b0, worst, omega, point, n_above
             Pool circ_pool;                   // sized by the circuit: base vectors, scale flags, right-hand-side lists
-            Pool res_pool;                    // sized by the sweep: the result planes
-            size_t res_len{};                 // doubles in each of res_re / res_im
-            bool rows_on_device{};            // V.keep holds `rows`
-            int* d_keep{};                    // device copy of `rows` (own allocation, reused while large enough)
-            size_t keep_cap{};
+            pe_eng::DevBuf<double> d_re, d_im;  // sized by the sweep: the result planes
+            pe_eng::KeptRows kept;            // pe_hip_set_ac_sweep_rows
             pe::AcSweepView V{};
             long long bytes_per_instance{};   // of the AC system (pe_hip_info), measured once per circuit for the automatic P
-            std::vector<int> rows;            // pe_hip_set_ac_sweep_rows; empty: all rows
             bool valid{};                     // `res` is the sweep of the current circuit at its current operating point
             int n_points{}, n_keep{}, batch{};
             std::vector<double> res;          // [2][n_points][batch][n_keep]: real parts, then imaginary parts
         } sweep;
+        void drop();  // both engines, then every buffer: back to a fresh Ac (pe_engine_ac.cpp)
     } ac;
     // noise analysis (pe_hip_analyze_noise, pe_noise.hpp): the ADJOINT real-equivalent system with sweep state of its own -- its AcCircuit,
     // its single-point engine (only the automatic pass size is measured on it), its batched engine and pass buffers -- so that a stored
@@ -250,11 +322,8 @@ struct pe_hip_engine
         std::vector<pe::NoiseSource> src; // definition order: resistors, junctions, three-pin devices
         std::vector<int> kind, index, part;
         Pool src_pool;                    // sized by the circuit: source table, row pairs, densities
-        Pool pass_pool;                   // sized by batch x P x chunks: chunk sums
-        size_t partial_len{};
-        Pool res_pool;                    // sized by the call: [psd | contributions]
-        size_t res_len{};
-        double* d_res{};
+        pe_eng::DevBuf<double> partial;   // sized by batch x P x chunks: chunk sums
+        pe_eng::DevBuf<double> d_res;     // sized by the call: [psd | contributions]
         pe::NoiseView V{};
         bool valid{};                     // `res` is the noise of the current circuit at its current operating point
         bool kept{};                      // ... with contributions
@@ -275,15 +344,10 @@ struct pe_hip_engine
         std::vector<int> sl_ptr;          // stamps of every value slot of the main engine (pe_sens.hpp)
         std::vector<pe::SensEnt> sl_ent;
         Pool tab_pool;                    // sized by the circuit: parameter table, stamp lists, raw columns, weights
-        Pool out_pool;                    // sized by n_outputs: the output rows
-        size_t out_len{};
-        int *d_out_pos{}, *d_out_neg{};
+        pe_eng::DevBuf<int> d_out_pos, d_out_neg;  // the output rows: grown to the most outputs a call has had
         double *d_draw{}, *d_graw{}, *d_weight{};
-        Pool pass_pool;                   // sized by batch x P x chunks: chunk sums
-        size_t partial_len{};
-        Pool res_pool;                    // sized by the call: [rss | sensitivities]
-        size_t res_len{};
-        double* d_res{};
+        pe_eng::DevBuf<double> partial;   // sized by batch x P x chunks: chunk sums
+        pe_eng::DevBuf<double> d_res;     // sized by the call: [rss | sensitivities]
         pe::SensView V{};
         bool valid{};                     // `res` belongs to the current circuit at its current operating point
         bool kept{}, weighted{};
@@ -301,11 +365,8 @@ struct pe_hip_engine
         Pool port_pool;                   // port rows and reference resistances (PE_HIP_NET_MAX_PORTS each)
         int *d_pos{}, *d_neg{};
         double* d_z0{};
-        Pool res_pool;                    // sized by the call: [Z re | Z im | Y re | Y im | S re | S im] and the two statuses
-        size_t res_len{};                 // doubles of one plane
-        size_t status_len{};              // ints of d_status
-        double* d_res{};
-        int* d_status{};                  // [2][n_points][batch]: Y, then S
+        pe_eng::DevBuf<double> d_res;     // sized by the call: [Z re | Z im | Y re | Y im | S re | S im]
+        pe_eng::DevBuf<int> d_status;     // [2][n_points][batch]: Y, then S -- released together with d_res
         pe::NetView V{};
         bool valid{};                     // `res` belongs to the current circuit at its current operating point
         int n_points{}, batch{}, n_ports{};
@@ -323,11 +384,8 @@ struct pe_hip_engine
         Pool pass_pool;                   // sized by batch x P
         Pool res_pool;                    // sized by the sweep: result and per-pair bookkeeping in the caller's order
         size_t res_pairs{}, res_len{};
-        int* d_keep{};                    // device copy of `rows` (own allocation, reused while large enough)
-        size_t keep_cap{};
-        bool rows_on_device{};
+        pe_eng::KeptRows kept;            // pe_hip_set_dc_sweep_rows
         pe::DcSweepView V{};
-        std::vector<int> rows;            // pe_hip_set_dc_sweep_rows; empty: all rows
         bool valid{};
         int n_points{}, n_keep{}, batch{};
         std::vector<double> res;          // [n_points][batch][n_keep]
@@ -450,7 +508,9 @@ namespace pe_eng PE_ENG_HIDDEN
     void tr_adaptive_drop(pe_hip_engine* h);  // shadow state, history ring and step log gone (pe_hip_load_circuit)
     void op_step_drop(pe_hip_engine* h);      // controller arrays, shadow and log of the stepped operating point gone (pe_hip_load_circuit)
     // pe_engine_ac.cpp: the stored AC sweep
-    void ac_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy); the noise and sensitivity state too
+    // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy); the noise, sensitivity and network state
+    // (each with its system, both engines, its tables and its result) too
+    void ac_sweep_drop(pe_hip_engine* h);
     inline void ac_sweep_invalidate(pe_hip_engine* h)  // whatever moves the operating point or the circuit: the stored sweep, the stored noise and sensitivity results
     {
         h->ac.sweep.valid = false;
@@ -458,9 +518,28 @@ namespace pe_eng PE_ENG_HIDDEN
         h->sens.valid = false;
         h->net.valid = false;
     }
+    // The check every getter of a stored result makes: there is one (`valid`, made at the batch the engine has now) -- else "<name>: no
+    // <what> yet" --, and items [first, first + n) of its n_items and instances [first_instance, first_instance + count) lie inside it --
+    // else "<name>: <noun> or instances out of range" (noun == nullptr, a per-instance getter: "<name>: instances out of range").
+    // Compared as first > total - n: first + n may overflow.
+    int stored_window(pe_hip_engine* h, char const* name, char const* what, char const* noun, bool valid, int stored_batch, int n_items, int first, int n,
+                      int first_instance, int count);
+    // the status of the main engine's instances: b_out = the first whose last analysis failed (it has no operating point to linearise at)
+    // with its status, or -1
+    int operating_point_status(pe_hip_engine* h, int& b_out, int& status_out);
+    // the linearisation the small-signal stamps refer to, from the main engine's device state
+    int read_operating_point(pe_hip_engine* h, pe::AcOperatingPoint& op);
     // budget of a sweep engine's automatic pass size, and the most instances one engine takes (the y extent of a launch grid)
     long long sweep_memory_budget();
     constexpr long long SWEEP_MAX_INSTANCES = 65535;
+    // points (slots) per pass of a sweep engine at circuit batch B: the knob's value when it is set, else what fits the memory budget at
+    // bytes_per_instance (0: unknown -- one per pass); never more than one engine takes as instances
+    inline long long sweep_pass_cap(int knob_value, long long bytes_per_instance, int B)
+    {
+        long long cap = knob_value > 0 ? knob_value : 0;
+        if(cap == 0) cap = bytes_per_instance > 0 ? sweep_memory_budget() / (bytes_per_instance * static_cast<long long>(B)) : 1;
+        return std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
+    }
     // pe_engine_newton.cpp: the DC sweep
     void dc_sweep_drop(pe_hip_engine* h);  // its engine, buffers, row selection and result gone (pe_hip_load_circuit, pe_hip_destroy)
     // the body of pe_hip_analyze_dc after its argument checks.  clear_status = false: the instances whose status is not OK are left alone

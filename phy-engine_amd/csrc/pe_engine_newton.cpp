@@ -788,6 +788,60 @@ namespace pe
 
 namespace pe_eng PE_ENG_HIDDEN
 {
+    // ---- the shell around a DC point (dc_solve, dc_solve_kept) and around a run of transient steps (pe_hip_analyze_tr, tr_run_steps)
+    struct SolveRun
+    {
+        std::vector<long long> s0, i0;  // n_steps and n_iters of every instance before the solve
+    };
+    // a call's statistics start from zero -- before anything that can end the call early
+    void solve_reset(pe_hip_engine* h, pe_hip_run_stats* st)
+    {
+        if(st) std::memset(st, 0, sizeof(*st));
+        h->dominant_ms = 0.0;
+        h->dominant_launches = 0;
+    }
+    // the counters before the solve (after the caller has cleared the status it wants cleared), then the event in front of its first launch
+    int solve_begin(pe_hip_engine* h, SolveRun& run)
+    {
+        if(int const rc = snapshot_counters(h, run.s0, run.i0); rc != PE_HIP_OK) return rc;
+        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+        return PE_HIP_OK;
+    }
+    // the event behind its last launch, the stream synchronised, and what the call reports; launches: launches of the resident kernel
+    int solve_end(pe_hip_engine* h, pe_hip_run_stats* st, SolveRun const& run, int launches)
+    {
+        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        int const rc = collect_stats(h, run.s0, run.i0, st);
+        if(st)
+        {
+            st->gpu_ms = ms;
+            st->n_launches = launches;
+            bool const split = h->dominant_launches > 0;
+            st->dominant_ms = split ? h->dominant_ms : ms;
+            st->dominant_launches = split ? h->dominant_launches : launches;
+        }
+        return rc;
+    }
+    // The residual safety net around a solve that has been launched: at most two rounds of prepare_inaccurate_retry, each followed by
+    // rerun(group) -- run_m2_dc / run_m2_tr on the group's instances for the steps they owe -- for every group it returns.
+    template <class Rerun>
+    int retry_inaccurate(pe_hip_engine* h, bool tr, double dt, int nsteps, std::vector<long long> const& s0, Rerun&& rerun)
+    {
+        for(int attempt = 0; attempt < 2; ++attempt)
+        {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            std::vector<std::pair<int, std::vector<int>>> groups;
+            if(int const rc = prepare_inaccurate_retry(h, tr, dt, attempt, s0, nsteps, groups); rc != PE_HIP_OK) return rc;
+            if(groups.empty()) break;
+            for(auto const& g: groups)
+                if(int const rc = rerun(g); rc != PE_HIP_OK) return rc;
+        }
+        return PE_HIP_OK;
+    }
+
     // The stepping part of pe_hip_analyze_tr: `nsteps` steps of dt on the schedule in effect, then the residual safety net's retries of
     // the instances whose solve stayed inaccurate.  The caller has run ensure_symbolic and cleared the status; s0 = n_steps before the
     // steps.  Leaves the stream synchronised.  pe_hip_analyze_tr_adaptive takes its single steps through here too.
@@ -828,20 +882,13 @@ namespace pe_eng PE_ENG_HIDDEN
             }
             if(integ) h->integ_hp = dt;  // (put right below should an instance have failed)
         }
-        for(int attempt = 0; attempt < 2; ++attempt)
-        {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            std::vector<std::pair<int, std::vector<int>>> groups;
-            rc = prepare_inaccurate_retry(h, true, dt, attempt, s0, nsteps, groups);
-            if(rc != PE_HIP_OK) return rc;
-            if(groups.empty()) break;
-            if(integ) h->integ_hp = std::nan("");  // (instances stepped alone)
-            for(auto const& g: groups)
-            {
-                rc = run_m2_tr(h, dt, g.first, launches, &g.second);
-                if(rc != PE_HIP_OK) return rc;
-            }
-        }
+        rc = retry_inaccurate(h, true, dt, nsteps, s0,
+                              [&](auto const& g)
+                              {
+                                  if(integ) h->integ_hp = std::nan("");  // (instances stepped alone)
+                                  return run_m2_tr(h, dt, g.first, launches, &g.second);
+                              });
+        if(rc != PE_HIP_OK) return rc;
         if(integ && nsteps > 0)
         {
             // every instance that is OK has taken its nsteps steps of dt: h_p = dt.  One that failed holds the point its failed step stored:
@@ -1014,9 +1061,7 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     HIPCHK(h, hipSetDevice(h->device));
     ac_sweep_invalidate(h);
     h->tra.n_pts = 0;  // (fixed steps restart the history of the variable-step transient)
-    if(st) std::memset(st, 0, sizeof(*st));
-    h->dominant_ms = 0.0;
-    h->dominant_launches = 0;
+    solve_reset(h, st);
     if(h->hc.rows == 0 || nsteps == 0) return PE_HIP_OK;
     int rc = ensure_symbolic(h, true, integ_sym_dt(h, dt));
     if(rc != PE_HIP_OK) return rc;
@@ -1025,29 +1070,15 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     // A failed solve is not sticky (circuit.h:242-254: the reference rolls tr_duration back, returns false, and the next
     // analyze() simply tries again from that state -- e.g. after the caller raised g_min): every run starts with all instances live.
     HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(h->hc.batch) * sizeof(int), h->stream));
-    std::vector<long long> s0, i0;
-    rc = snapshot_counters(h, s0, i0);
+    SolveRun run;
+    rc = solve_begin(h, run);
     if(rc != PE_HIP_OK) return rc;
     bool const may_reuse = !h->hc.nonlinear && !h->opt.refactor_every_solve && !has_overlay(h);
     int launches = 0;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    rc = tr_run_steps(h, dt, nsteps, s0, launches);
+    rc = tr_run_steps(h, dt, nsteps, run.s0, launches);
     if(rc != PE_HIP_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
     if(!may_reuse) h->fact_valid = false;
-    rc = collect_stats(h, s0, i0, st);
-    if(st)
-    {
-        st->gpu_ms = ms;
-        st->n_launches = launches;
-        bool const split = h->dominant_launches > 0;
-        st->dominant_ms = split ? h->dominant_ms : ms;
-        st->dominant_launches = split ? h->dominant_launches : launches;
-    }
-    return rc;
+    return solve_end(h, st, run, launches);
 }
 
 int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_control* c, pe_hip_tr_adaptive_stats* out)
@@ -1293,118 +1324,55 @@ namespace pe_eng
 // The solving part of pe_hip_analyze_dc: one OP / DC / TROP point of every instance whose status is OK on the schedule in effect, then the
 // residual safety net's retries.  clear_status: every instance takes part (what pe_hip_analyze_dc does); else the instances that are not OK
 // stay as they are -- the DC sweep solves subsets that way, with the others parked.  Leaves the stream synchronised.
-int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status)
+// kept (dc_solve_kept, pe_engine_internal.hpp): the factors of the last factorisation are kept -- the split schedule's iteration with
+// do_factor = false on every instance, whatever schedule factored; the safety net's retries run exactly as without it, and those factor.
+namespace
+{
+int dc_point(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status, bool kept)
 {
     probe_disarm(h);  // (moves x: ends a probe window)
     ac_sweep_invalidate(h);
-    if(st) std::memset(st, 0, sizeof(*st));
-    h->dominant_ms = 0.0;
-    h->dominant_launches = 0;
+    solve_reset(h, st);
     if(h->hc.rows == 0) return PE_HIP_OK;
-    int rc = ensure_symbolic(h, false, 0.0);
+    int rc = kept ? PE_HIP_OK : ensure_symbolic(h, false, 0.0);
     if(rc != PE_HIP_OK) return rc;
     if(clear_status) HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(h->hc.batch) * sizeof(int), h->stream));  // no sticky failure (see analyze_tr)
-    std::vector<long long> s0, i0;
-    rc = snapshot_counters(h, s0, i0);
+    SolveRun run;
+    rc = solve_begin(h, run);
     if(rc != PE_HIP_OK) return rc;
-    h->fact_valid = false;
+    if(!kept) h->fact_valid = false;
     h->a_static.clear();  // (an OP / DC / TROP solve stamps other companion values into the matrix, on either schedule)
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    ++h->n_factor_launches;
-    if(split_launch(h))
-    {
-        int launches = 0;
-        rc = run_m2_dc(h, mode, launches);
-        if(rc != PE_HIP_OK) return rc;
-    }
+    long long const rematched0 = h->n_rematched;
+    int launches = 0;
+    if(kept) rc = run_m2_dc(h, mode, launches, nullptr, false);  // (no factorisation: n_factor_launches does not count this attempt)
     else
-        HIPCHK(h, pe::launch_dc_point(h->stream, h->V, mode));
-    for(int attempt = 0; attempt < 2; ++attempt)
-        {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            std::vector<std::pair<int, std::vector<int>>> groups;
-            rc = prepare_inaccurate_retry(h, false, 0.0, attempt, s0, 1, groups);
-            if(rc != PE_HIP_OK) return rc;
-            if(groups.empty()) break;
-            int launches = 0;
-            for(auto const& g: groups)
-            {
-                ++h->n_factor_launches;
-                rc = run_m2_dc(h, mode, launches, &g.second);
-                if(rc != PE_HIP_OK) return rc;
-            }
-        }
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    rc = collect_stats(h, s0, i0, st);
-    if(st)
     {
-        st->gpu_ms = ms;
-        st->n_launches = 1;
-        bool const split = h->dominant_launches > 0;
-        st->dominant_ms = split ? h->dominant_ms : ms;
-        st->dominant_launches = split ? h->dominant_launches : 1;
+        ++h->n_factor_launches;
+        if(split_launch(h)) rc = run_m2_dc(h, mode, launches);
+        else
+            HIPCHK(h, pe::launch_dc_point(h->stream, h->V, mode));
     }
-    return rc;
+    if(rc != PE_HIP_OK) return rc;
+    rc = retry_inaccurate(h, false, 0.0, 1, run.s0,
+                          [&](auto const& g)
+                          {
+                              ++h->n_factor_launches;
+                              return run_m2_dc(h, mode, launches, &g.second);
+                          });
+    if(rc != PE_HIP_OK) return rc;
+    // a re-match gave the engine another pivot order: only the retried instances hold factors of it -- every instance factors again
+    if(kept && h->n_rematched != rematched0) return dc_point(h, mode, st, true, false);
+    return solve_end(h, st, run, 1);
 }
+}  // namespace
 
+int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status) { return dc_point(h, mode, st, clear_status, false); }
 
-// dc_solve with the factors of the last factorisation kept (pe_engine_internal.hpp): the split schedule's iteration with do_factor = false
-// on every instance, then the safety net's retries exactly as dc_solve runs them -- those factor.
 int dc_solve_kept(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
 {
-    if(h->hc.nonlinear || !h->V.keep_l21 || has_overlay(h) || h->sym_class != 0) return dc_solve(h, mode, st, true);
-    probe_disarm(h);
-    ac_sweep_invalidate(h);
-    if(st) std::memset(st, 0, sizeof(*st));
-    h->dominant_ms = 0.0;
-    h->dominant_launches = 0;
-    if(h->hc.rows == 0) return PE_HIP_OK;
-    HIPCHK(h, hipMemsetAsync(h->V.status, 0, static_cast<size_t>(h->hc.batch) * sizeof(int), h->stream));
-    std::vector<long long> s0, i0;
-    int rc = snapshot_counters(h, s0, i0);
-    if(rc != PE_HIP_OK) return rc;
-    h->a_static.clear();
-    long long const rematched0 = h->n_rematched;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    {
-        int launches = 0;
-        rc = run_m2_dc(h, mode, launches, nullptr, false);
-        if(rc != PE_HIP_OK) return rc;
-    }
-    for(int attempt = 0; attempt < 2; ++attempt)
-    {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<std::pair<int, std::vector<int>>> groups;
-        rc = prepare_inaccurate_retry(h, false, 0.0, attempt, s0, 1, groups);
-        if(rc != PE_HIP_OK) return rc;
-        if(groups.empty()) break;
-        int launches = 0;
-        for(auto const& g: groups)
-        {
-            ++h->n_factor_launches;
-            rc = run_m2_dc(h, mode, launches, &g.second);
-            if(rc != PE_HIP_OK) return rc;
-        }
-    }
-    // a re-match gave the engine another pivot order: only the retried instances hold factors of it -- every instance factors again
-    if(h->n_rematched != rematched0) return dc_solve(h, mode, st, true);
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    rc = collect_stats(h, s0, i0, st);
-    if(st)
-    {
-        st->gpu_ms = ms;
-        st->n_launches = 1;
-        bool const split = h->dominant_launches > 0;
-        st->dominant_ms = split ? h->dominant_ms : ms;
-        st->dominant_launches = split ? h->dominant_launches : 1;
-    }
-    return rc;
+    // an engine that keeps no L21, or whose factors are not those of a DC point of a linear circuit, factors: dc_solve
+    bool const keeps = !h->hc.nonlinear && h->V.keep_l21 && !has_overlay(h) && h->sym_class == 0;
+    return dc_point(h, mode, st, true, keeps);
 }
 
 }  // namespace pe_eng
@@ -1712,11 +1680,8 @@ namespace pe_eng
     void dc_sweep_drop(pe_hip_engine* h)
     {
         auto& D = h->dcs;
-        if(D.eng) pe_hip_destroy(D.eng);  // (synchronises its stream first: nothing reads the buffers below any more)
-        D.pass_pool.release();
-        D.res_pool.release();
-        if(D.d_keep) (void)hipFree(D.d_keep);
-        D = pe_hip_engine::DcSweep{};
+        if(D.eng) pe_hip_destroy(D.eng);  // (synchronises its stream first: nothing reads the buffers freed next any more)
+        D = pe_hip_engine::DcSweep{};     // (its pools and kept rows free what they hold)
     }
 }  // namespace pe_eng
 
@@ -1793,14 +1758,10 @@ extern "C" {
 
 int pe_hip_set_dc_sweep_rows(pe_hip_engine* h, int n_rows, const int* rows)
 {
-    if(!h || !h->loaded || n_rows < 0 || (n_rows > 0 && !rows)) return h ? fail(h, PE_HIP_ERR_ARG, "set_dc_sweep_rows: bad arguments or no circuit") : PE_HIP_ERR_ARG;
-    for(int k = 0; k < n_rows; ++k)
-        if(rows[k] < 0 || rows[k] >= h->hc.rows) return fail(h, PE_HIP_ERR_ARG, "set_dc_sweep_rows: row out of range");
-    auto& D = h->dcs;
-    D.rows.assign(rows, rows + n_rows);
-    D.rows_on_device = false;
-    D.valid = false;  // (the stored result has the layout of the rows it was made with)
-    return PE_HIP_OK;
+    if(!h) return PE_HIP_ERR_ARG;
+    int const rc = h->dcs.kept.set(h, "set_dc_sweep_rows", n_rows, rows);
+    if(rc == PE_HIP_OK) h->dcs.valid = false;  // (the stored result has the layout of the rows it was made with)
+    return rc;
 }
 
 int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values, const pe_hip_dc_sweep_control* c, int* point_status,
@@ -1824,7 +1785,7 @@ int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values
     auto& D = h->dcs;
     D.valid = false;
     int const B = hc.batch, N = hc.rows;
-    int const K = D.rows.empty() ? N : static_cast<int>(D.rows.size());
+    int const K = D.kept.rows.empty() ? N : static_cast<int>(D.kept.rows.size());
     pe_hip_dc_sweep_stats T{};
     T.n_points = n_points;
     size_t const pairs = static_cast<size_t>(n_points) * B;
@@ -1863,16 +1824,10 @@ int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values
     int P = 2;
     if(!trace)
     {
-        long long cap = std::max(0, knob(h, "DC_SWEEP_POINTS", 0));
-        if(cap == 0)
-        {
-            // (the main engine's arrays per instance; its factor storage is part of them once it has been analysed)
-            long long bpi = static_cast<long long>((h->circ_pool.bytes + h->sym_pool.bytes) / static_cast<size_t>(std::max(1, B)));
-            if(h->sym_class < 0) bpi = 4 * static_cast<long long>(h->circ_pool.bytes / static_cast<size_t>(std::max(1, B)));
-            cap = sweep_memory_budget() / (std::max<long long>(1, bpi) * B);
-        }
-        cap = std::clamp<long long>(cap, 1, std::max<long long>(1, SWEEP_MAX_INSTANCES / B));
-        P = static_cast<int>(std::min<long long>(cap, n_points));
+        // (the main engine's arrays per instance; its factor storage is part of them once it has been analysed)
+        long long bpi = static_cast<long long>((h->circ_pool.bytes + h->sym_pool.bytes) / static_cast<size_t>(std::max(1, B)));
+        if(h->sym_class < 0) bpi = 4 * static_cast<long long>(h->circ_pool.bytes / static_cast<size_t>(std::max(1, B)));
+        P = static_cast<int>(std::min<long long>(sweep_pass_cap(knob(h, "DC_SWEEP_POINTS", 0), std::max<long long>(1, bpi), B), n_points));
     }
     else if(2ll * B > SWEEP_MAX_INSTANCES)
         return fail(h, PE_HIP_ERR_ARG, "analyze_dc_sweep: the batch is too large for a TRACE sweep");
@@ -1930,24 +1885,7 @@ int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values
     HIPCHK(h, hipMemcpy(d_val, val_h.data(), L * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(d_pt, pt_h.data(), L * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(d_rk, rk_h.data(), L * sizeof(int), hipMemcpyHostToDevice));
-    if(!D.rows_on_device)
-    {
-        S.keep = nullptr;
-        if(D.rows.size() > D.keep_cap)
-        {
-            if(D.d_keep) (void)hipFree(D.d_keep);
-            D.d_keep = nullptr;
-            D.keep_cap = 0;
-            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&D.d_keep), D.rows.size() * sizeof(int)));
-            D.keep_cap = D.rows.size();
-        }
-        if(!D.rows.empty())
-        {
-            HIPCHK(h, hipMemcpy(D.d_keep, D.rows.data(), D.rows.size() * sizeof(int), hipMemcpyHostToDevice));
-            S.keep = D.d_keep;
-        }
-        D.rows_on_device = true;
-    }
+    if(int const rc = D.kept.upload(h, S.keep); rc != PE_HIP_OK) return rc;
     S.P = P;
     S.n_inst = B;
     S.slot = slot;
@@ -2065,9 +2003,9 @@ int pe_hip_get_dc_sweep(pe_hip_engine* h, int first_point, int n_points, int fir
 {
     if(!h || !h->loaded || !x) return PE_HIP_ERR_ARG;
     auto const& D = h->dcs;
-    if(!D.valid || D.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep: no DC sweep yet");
-    if(first_point < 0 || n_points < 0 || first_point > D.n_points - n_points || first_instance < 0 || count < 0 || first_instance > D.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep: points or instances out of range");
+    if(int const rc = stored_window(h, "get_dc_sweep", "DC sweep", "points", D.valid, D.batch, D.n_points, first_point, n_points, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     size_t const K = static_cast<size_t>(D.n_keep);
     for(int i = 0; i < n_points && count * K != 0; ++i)
         std::memcpy(x + static_cast<size_t>(i) * count * K, &D.res[(static_cast<size_t>(first_point + i) * D.batch + first_instance) * K],
@@ -2080,9 +2018,9 @@ int pe_hip_get_dc_sweep_status(pe_hip_engine* h, int first_point, int n_points, 
 {
     if(!h || !h->loaded) return PE_HIP_ERR_ARG;
     auto const& D = h->dcs;
-    if(!D.valid || D.batch != h->hc.batch) return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep_status: no DC sweep yet");
-    if(first_point < 0 || n_points < 0 || first_point > D.n_points - n_points || first_instance < 0 || count < 0 || first_instance > D.batch - count)
-        return fail(h, PE_HIP_ERR_ARG, "get_dc_sweep_status: points or instances out of range");
+    if(int const rc = stored_window(h, "get_dc_sweep_status", "DC sweep", "points", D.valid, D.batch, D.n_points, first_point, n_points, first_instance, count);
+       rc != PE_HIP_OK)
+        return rc;
     for(int i = 0; i < n_points; ++i)
         for(int b = 0; b < count; ++b)
         {
