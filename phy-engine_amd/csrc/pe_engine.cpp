@@ -183,20 +183,12 @@ int finish_load(pe_hip_engine* h)
         // scratch of pe_hip_sweep_statistics, allocated with the circuit: a first-call hipMalloc costs milliseconds (7.6 ms measured
         // at 128 instances), the statistics themselves 0.05-0.1 ms
         size_t const need = static_cast<size_t>(stats_chunks(static_cast<int>(B)) + 1) * 4 * hc.rows;
-        HIPCHK(h, P.alloc(h->stats_scratch, need, false));
-        h->stats_doubles = need;
+        HIPCHK(h, P.alloc(h->resident.stats_scratch, need, false));
+        h->resident.stats_doubles = need;
         // ... and a pinned landing buffer for its 4 x rows result: the first asynchronous copy into PAGEABLE host memory makes the runtime
         // set up its staging path -- 7.4 ms on the first pe_hip_sweep_statistics call against 0.07 ms on the following ones (round 4,
         // scripts/r4_reduce_probe.py); that call is the sweep's one exchange step and sits on every rank's critical path before the all-reduce
-        size_t const out_bytes = static_cast<size_t>(4) * hc.rows * sizeof(double);
-        if(h->stats_pinned_bytes < out_bytes)
-        {
-            if(h->stats_pinned) (void)hipHostFree(h->stats_pinned);
-            h->stats_pinned = nullptr;
-            h->stats_pinned_bytes = 0;
-            HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->stats_pinned), std::max<size_t>(out_bytes, 8), hipHostMallocDefault));
-            h->stats_pinned_bytes = out_bytes;
-        }
+        HIPCHK(h, h->stats_pinned.ensure_at_least(static_cast<size_t>(4) * hc.rows));
     }
     HIPCHK(h, P.alloc(V.active, 5 * B));  // the mask + the quad list of the lane-group kernel behind it (upload_active)
     HIPCHK(h, P.alloc(V.flags, B));
@@ -228,15 +220,32 @@ int finish_load(pe_hip_engine* h)
     // zeroed solution: the first use of that path costs the runtime 7-8 ms (first asynchronous device-to-host copy of the stream: copy-queue
     // set-up; measured with scripts/r4_reduce_probe.py: 7.4 ms, then 0.07 ms) -- paid here, with the load, instead of on every rank's
     // critical path in front of the all-reduce.
-    if(hc.rows > 0 && h->stats_pinned)
+    if(hc.rows > 0 && h->stats_pinned.data())
     {
         int const n_chunks = stats_chunks(hc.batch);
-        double* dev_out = h->stats_scratch + static_cast<size_t>(n_chunks) * 4 * hc.rows;
-        HIPCHK(h, pe::launch_sweep_statistics(h->stream, h->V, n_chunks, h->stats_scratch, dev_out));
-        HIPCHK(h, hipMemcpyAsync(h->stats_pinned, dev_out, static_cast<size_t>(4) * hc.rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        double* dev_out = h->resident.stats_scratch + static_cast<size_t>(n_chunks) * 4 * hc.rows;
+        HIPCHK(h, pe::launch_sweep_statistics(h->stream, h->V, n_chunks, h->resident.stats_scratch, dev_out));
+        HIPCHK(h, hipMemcpyAsync(h->stats_pinned.data(), dev_out, static_cast<size_t>(4) * hc.rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return PE_HIP_OK;
+}
+
+int engine_build(int device, EnginePtr& out, pe_hip_engine* h, std::string const& name, pe_hip_options const* opt, pe::HostCircuit hc)
+{
+    out.reset();
+    pe_hip_engine* e{};
+    int rc = pe_hip_create(device, &e);
+    if(rc != PE_HIP_OK) return h ? fail(h, PE_HIP_ERR_NO_DEVICE, name + ": " + std::string(pe_hip_last_error(nullptr))) : rc;
+    out.reset(e);
+    if(!h) return PE_HIP_OK;
+    e->knobs = h->knobs;
+    e->opt = *opt;
+    e->hc = std::move(hc);
+    if(rc = finish_load(e); rc == PE_HIP_OK) return rc;
+    std::string const msg = e->err;
+    out.reset();
+    return fail(h, rc, name + ": " + msg);
 }
 
 // ---------------- transient probes (pe_probe.hpp)
@@ -259,42 +268,26 @@ void fourier_drop(pe_hip_engine* h)
 {
     auto& F = h->fourier;
     if(F.configured) (void)hipStreamSynchronize(h->stream);  // (a recording launch may still write the accumulators)
-    F.pool.release();
-    F.configured = false;
-    F.n_fp = F.H = 0;
-    F.fv = pe::FourierView{};
-    F.dev = nullptr;
-    F.out_coef = F.out_thd = nullptr;
+    F = pe_hip_engine::Fourier{};  // (its pool frees what it holds)
 }
 void probe_drop(pe_hip_engine* h)
 {
     auto& P = h->probe;
     fourier_drop(h);  // (its probe indices and its window belong to this configuration)
     if(P.configured) (void)hipStreamSynchronize(h->stream);  // (a recording launch may still read the buffers)
-    P.pool.release();
-    P.configured = P.armed = false;
-    P.n_probes = P.n_meas = P.capacity = P.stride = P.batch = 0;
-    P.kind.clear();
-    P.pv = pe::ProbeView{};
+    P = pe_hip_engine::Probes{};  // (its pool frees what it holds; the pinned staging of the accepted set stays with the engine)
 }
 int probe_record_step(pe_hip_engine* h, std::vector<int> const& accepted, double t)
 {
     auto& P = h->probe;
     if(!P.armed || std::find(accepted.begin(), accepted.end(), 1) == accepted.end()) return PE_HIP_OK;
     size_t const B = accepted.size();
-    if(P.pin_cap < B)
-    {
-        if(P.pin_accept) (void)hipHostFree(P.pin_accept);
-        P.pin_accept = nullptr;
-        P.pin_cap = 0;
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&P.pin_accept), B * sizeof(int), hipHostMallocDefault));
-        P.pin_cap = B;
-    }
+    HIPCHK(h, h->pin_accept.ensure_at_least(B));
     // the staging buffer of the previous step may still be in flight (its copy is stream-ordered); a private device array keeps
     // upload_active's cache of the `active` mask and the quad list behind it intact
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::copy(accepted.begin(), accepted.end(), P.pin_accept);
-    HIPCHK(h, hipMemcpyAsync(const_cast<int*>(P.pv.accept), P.pin_accept, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    std::copy(accepted.begin(), accepted.end(), h->pin_accept.data());
+    HIPCHK(h, hipMemcpyAsync(const_cast<int*>(P.pv.accept), h->pin_accept.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, pe::launch_probe_record(h->stream, probe_view(h), t));
     return PE_HIP_OK;
 }
@@ -329,9 +322,9 @@ int pe_hip_create(int device, pe_hip_engine** out)
     }
     auto h = std::make_unique<pe_hip_engine>();
     h->device = device;
-    if(hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
-       hipEventCreate(&h->ev1) != hipSuccess || hipEventCreate(&h->evk0) != hipSuccess || hipEventCreate(&h->evk1) != hipSuccess)
-    {
+    if(hipSetDevice(device) != hipSuccess || h->stream.create() != hipSuccess || h->ev0.create() != hipSuccess || h->ev1.create() != hipSuccess ||
+       h->evk0.create() != hipSuccess || h->evk1.create() != hipSuccess)
+    {  // (what was created goes with h)
         g_create_error = "HIP runtime initialisation failed";
         return PE_HIP_ERR_NO_DEVICE;
     }
@@ -348,28 +341,8 @@ void pe_hip_destroy(pe_hip_engine* h)
 {
     if(!h) return;
     (void)hipSetDevice(h->device);
-    ac_sweep_drop(h);
-    dc_sweep_drop(h);
-    h->ac.drop();
     (void)hipStreamSynchronize(h->stream);
-    if(h->graphs) pe::m2_graphs_destroy(h->graphs);  // (captured launch sequences: before the memory they point into and their stream go)
-    h->fourier.pool.release();
-    h->probe.pool.release();
-    h->integ_pool.release();
-    h->circ_pool.release();
-    h->sym_pool.release();
-    h->csr.pool.release();
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
-    (void)hipEventDestroy(h->evk0);
-    (void)hipEventDestroy(h->evk1);
-    (void)hipStreamDestroy(h->stream);
-    if(h->pin_active) (void)hipHostFree(h->pin_active);
-    if(h->pin_flags) (void)hipHostFree(h->pin_flags);
-    if(h->pub_host) (void)hipHostFree(h->pub_host);
-    if(h->stats_pinned) (void)hipHostFree(h->stats_pinned);
-    if(h->probe.pin_accept) (void)hipHostFree(h->probe.pin_accept);
-    delete h;
+    delete h;  // (the members free what they own, in the order pe_engine_internal.hpp states)
 }
 
 int pe_hip_set_options(pe_hip_engine* h, const pe_hip_options* o)
@@ -392,8 +365,7 @@ int pe_hip_set_options(pe_hip_engine* h, const pe_hip_options* o)
                 HIPCHK(h, hipMemcpy2D(h->V.dv + g.dv, h->hc.dv_len * sizeof(double), col.data(), sizeof(double), sizeof(double), h->hc.batch,
                                       hipMemcpyHostToDevice));
             }
-        h->fact_valid = false;
-        h->a_static.clear();
+        invalidate_factors(h);
     }
     if(h->loaded && gmin_changed)
     {
@@ -401,8 +373,7 @@ int pe_hip_set_options(pe_hip_engine* h, const pe_hip_options* o)
         std::vector<double> col(h->hc.batch, o->g_min);
         HIPCHK(h, hipMemcpy2D(h->V.dv + pe::DV_GMIN, h->hc.dv_len * sizeof(double), col.data(), sizeof(double), sizeof(double), h->hc.batch,
                               hipMemcpyHostToDevice));
-        h->fact_valid = false;
-        h->a_static.clear();
+        invalidate_factors(h);
     }
     return PE_HIP_OK;
 }
@@ -462,7 +433,7 @@ int pe_hip_set_knob(pe_hip_engine* h, const char* name, int value)
     if(key.empty()) return fail(h, PE_HIP_ERR_ARG, "set_knob: empty name");
     h->knobs[key] = value;
     ++h->param_epoch;
-    h->sym_class = -1;  // the launch geometry and the symbolic analysis are chosen again at the next analysis
+    h->resident.sym_class = -1;  // the launch geometry and the symbolic analysis are chosen again at the next analysis
     return PE_HIP_OK;
 }
 
@@ -533,27 +504,14 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     if(!h || (n_tables > 0 && !tables)) return PE_HIP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     h->loaded = false;
-    h->sym_class = -1;
-    h->fact_valid = false;
-    h->a_static.clear();
-    pe::m2_graphs_clear(h->graphs);  // (captured launch sequences point into the circuit being replaced)
-    probe_drop(h);                   // (a probe configuration belongs to the circuit: rows, batch)
-    tr_adaptive_drop(h);             // (... and so do the shadow state and the history of the variable-step transient)
-    op_step_drop(h);                 // (... and the controller arrays of the stepped operating point)
-    h->integ_pool.release();         // (... and the history of the BE / GEAR2 rules; the rule itself stays)
+    h->resident = {};                      // (everything that spoke of the circuit being replaced: pe_engine_internal.hpp Resident)
+    pe::m2_graphs_clear(h->graphs.get());  // (captured launch sequences point into it)
+    probe_drop(h);                         // (a probe configuration belongs to the circuit: rows, batch)
+    tr_adaptive_drop(h);                   // (... and so do the shadow state and the history of the variable-step transient)
+    op_step_drop(h);                       // (... and the controller arrays of the stepped operating point)
+    h->integ_pool.release();               // (... and the history of the BE / GEAR2 rules; the rule itself stays)
     h->V.tr_hist = nullptr;
-    h->integ_hp = 0.0;
     h->circ_pool.release();
-    h->stats_scratch = nullptr;
-    h->stats_doubles = 0;
-    h->active_dev.clear();
-    h->singular_rematched = false;
-    h->sym_dt = 0.0;
-    h->careful = false;  // (a false alarm on the previous circuit must not pin this one to the host-driven schedule)
-    h->n_refined = h->n_rematched = 0;
-    h->quad_skipped_launches = h->quad_full_launches = 0;
-    h->quad_launches_after_refinement = h->quad_skipped_after_refinement = 0;
-    h->static_skip = pe::StaticSkip{};
     h->sym_pool.release();
     ac_sweep_drop(h);
     dc_sweep_drop(h);
@@ -577,7 +535,7 @@ int pe_hip_get_info(pe_hip_engine* h, pe_hip_info* out)
     out->nnz_a = static_cast<int>(hc.ci.size());
     out->n_r = hc.nR(); out->n_c = hc.nC(); out->n_l = hc.nL(); out->n_v = hc.nVdc() + hc.nVac() + hc.n_drives; out->n_i = hc.nIdc(); out->n_d = hc.nD();
     out->nonlinear = hc.nonlinear;
-    if(h->sym_class >= 0)
+    if(h->resident.sym_class >= 0)
     {
         out->nnz_lu = h->sym.nnz_LU;
         out->nnz_lu_stored = h->sym.nnz_LU_stored;
@@ -616,7 +574,7 @@ int pe_hip_get_front_table(pe_hip_engine* h, int which, int capacity, int* pivot
     if(!h || !n_fronts || capacity < 0) return PE_HIP_ERR_ARG;
     pe::Symbolic const* S = nullptr;
     pe::DevView const* V = nullptr;
-    if(which == 0 && h->loaded && h->sym_class >= 0) S = &h->sym, V = &h->V;
+    if(which == 0 && h->loaded && h->resident.sym_class >= 0) S = &h->sym, V = &h->V;
     else if(which == 1 && h->csr.have) S = &h->csr.sym, V = &h->csr.V;
     else if(which == 2 && h->csrz.have) S = &h->csrz.sym, V = &h->csrz.V;
     if(!S) return fail(h, PE_HIP_ERR_ARG, "get_front_table: no such analysis");
@@ -640,7 +598,7 @@ int pe_hip_get_static_fronts(pe_hip_engine* h, int which, int capacity, int* is_
 {
     if(!h || !n_fronts || capacity < 0) return PE_HIP_ERR_ARG;
     pe::Symbolic const* S = nullptr;
-    if(which == 0 && h->loaded && h->sym_class >= 0) S = &h->sym;
+    if(which == 0 && h->loaded && h->resident.sym_class >= 0) S = &h->sym;
     else if(which == 1 && h->csr.have) S = &h->csr.sym;
     else if(which == 2 && h->csrz.have) S = &h->csrz.sym;
     if(!S) return fail(h, PE_HIP_ERR_ARG, "get_static_fronts: no such analysis");
@@ -652,16 +610,16 @@ int pe_hip_get_static_fronts(pe_hip_engine* h, int which, int capacity, int* is_
 int pe_hip_get_static_skip_stats(pe_hip_engine* h, long long* skipped_launches, long long* full_launches)
 {
     if(!h) return PE_HIP_ERR_ARG;
-    if(skipped_launches) *skipped_launches = h->quad_skipped_launches;
-    if(full_launches) *full_launches = h->quad_full_launches;
+    if(skipped_launches) *skipped_launches = h->resident.quad_skipped_launches;
+    if(full_launches) *full_launches = h->resident.quad_full_launches;
     return PE_HIP_OK;
 }
 
 int pe_hip_get_static_skip_refinement_stats(pe_hip_engine* h, long long* launches_after_refinement, long long* skipped_after_refinement)
 {
     if(!h) return PE_HIP_ERR_ARG;
-    if(launches_after_refinement) *launches_after_refinement = h->quad_launches_after_refinement;
-    if(skipped_after_refinement) *skipped_after_refinement = h->quad_skipped_after_refinement;
+    if(launches_after_refinement) *launches_after_refinement = h->resident.quad_launches_after_refinement;
+    if(skipped_after_refinement) *skipped_after_refinement = h->resident.quad_skipped_after_refinement;
     return PE_HIP_OK;
 }
 
@@ -700,8 +658,7 @@ int pe_hip_reset(pe_hip_engine* h)
     HIPCHK(h, hipMemset(V.n_iters, 0, B * sizeof(long long)));
     HIPCHK(h, hipMemset(V.trace_len, 0, sizeof(int)));
     HIPCHK(h, hipMemset(V.prof, 0, B * pe::PE_PROF * sizeof(long long)));
-    h->fact_valid = false;
-    h->a_static.clear();
+    invalidate_factors(h);
     return PE_HIP_OK;
 }
 
@@ -751,9 +708,9 @@ int pe_hip_get_newton_trace(pe_hip_engine* h, int capacity, int* iters, int* n_o
 int pe_hip_get_safety_net_counters(pe_hip_engine* h, long long* refined, long long* rematched, int* careful)
 {
     if(!h) return PE_HIP_ERR_ARG;
-    if(refined) *refined = h->n_refined;
-    if(rematched) *rematched = h->n_rematched;
-    if(careful) *careful = h->careful ? 1 : 0;
+    if(refined) *refined = h->resident.n_refined;
+    if(rematched) *rematched = h->resident.n_rematched;
+    if(careful) *careful = h->resident.careful ? 1 : 0;
     return PE_HIP_OK;
 }
 
@@ -785,19 +742,19 @@ int pe_hip_sweep_statistics(pe_hip_engine* h, double* out)
     if(rows == 0) return PE_HIP_OK;
     int const n_chunks = stats_chunks(B);
     size_t const need = static_cast<size_t>(n_chunks + 1) * 4 * rows;
-    if(h->stats_doubles < need)  // scratch kept with the resident circuit (an allocation per call would cost more than the kernels)
+    if(h->resident.stats_doubles < need)  // scratch kept with the resident circuit (an allocation per call would cost more than the kernels)
     {
-        HIPCHK(h, h->circ_pool.alloc(h->stats_scratch, need, false));
-        h->stats_doubles = need;
+        HIPCHK(h, h->circ_pool.alloc(h->resident.stats_scratch, need, false));
+        h->resident.stats_doubles = need;
     }
-    double* partial = h->stats_scratch;
-    double* dev_out = h->stats_scratch + static_cast<size_t>(n_chunks) * 4 * rows;
+    double* partial = h->resident.stats_scratch;
+    double* dev_out = h->resident.stats_scratch + static_cast<size_t>(n_chunks) * 4 * rows;
     HIPCHK(h, pe::launch_sweep_statistics(h->stream, h->V, n_chunks, partial, dev_out));
     size_t const out_bytes = static_cast<size_t>(4) * rows * sizeof(double);
-    bool const pinned = h->stats_pinned && h->stats_pinned_bytes >= out_bytes;
-    HIPCHK(h, hipMemcpyAsync(pinned ? static_cast<void*>(h->stats_pinned) : static_cast<void*>(out), dev_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    bool const pinned = h->stats_pinned.data() && h->stats_pinned.capacity() >= static_cast<size_t>(4) * rows;
+    HIPCHK(h, hipMemcpyAsync(pinned ? static_cast<void*>(h->stats_pinned.data()) : static_cast<void*>(out), dev_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if(pinned) std::memcpy(out, h->stats_pinned, out_bytes);
+    if(pinned) std::memcpy(out, h->stats_pinned.data(), out_bytes);
     return PE_HIP_OK;
 }
 
@@ -810,7 +767,7 @@ int pe_hip_get_matrix(pe_hip_engine* h, int instance, int* row_ptr, int* col_ind
     HIPCHK(h, hipSetDevice(h->device));
     if(vals)
     {
-        if(h->sym_class < 0) return fail(h, PE_HIP_ERR_ARG, "get_matrix: no analysis has run yet");
+        if(h->resident.sym_class < 0) return fail(h, PE_HIP_ERR_ARG, "get_matrix: no analysis has run yet");
         std::vector<double> tmp(hc.ci.size());  // device order = front-assembly order (ensure_symbolic)
         HIPCHK(h, hipMemcpy(tmp.data(), h->V.aval + static_cast<size_t>(instance) * hc.ci.size(), hc.ci.size() * sizeof(double), hipMemcpyDeviceToHost));
         for(size_t e = 0; e < tmp.size(); ++e) vals[h->sym.asm_slot[e]] = tmp[e];
@@ -854,8 +811,7 @@ int pe_hip_update_param(pe_hip_engine* h, int kind, int index, int column, const
         auto const& d = hc.gen[g];
         if(kind == PE_HIP_VGEN && column == 0) return fail(h, PE_HIP_ERR_ARG, "update_param: the generator type is fixed at load time");
         std::vector<double> col(B);
-        h->fact_valid = false;
-        h->a_static.clear();
+        invalidate_factors(h);
         for(int b = 0; b < B; ++b)
         {
             hc.gen_par[static_cast<size_t>(b) * hc.gen_par_len + d.par + column] = val(b);
@@ -896,8 +852,7 @@ int pe_hip_update_param(pe_hip_engine* h, int kind, int index, int column, const
     int const j = (*map)[index];
     if(j < 0) return PE_HIP_OK;  // device with an unconnected pin: nothing resident
     std::vector<double> col(B);
-    h->fact_valid = false;
-    h->a_static.clear();
+    invalidate_factors(h);
     switch(kind)
     {
         case PE_HIP_R:

@@ -19,8 +19,6 @@ namespace
         auto& hc = h->hc;
         if(A.built) return PE_HIP_OK;
         if(!pe::build_ac_circuit(hc, A.circ, has_overlay(h) ? &h->overlay : nullptr, adjoint)) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_ac: could not build the AC system");
-        if(pe_hip_create(h->device, &A.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_ac: " + std::string(pe_hip_last_error(nullptr)));
-        A.eng->knobs = h->knobs;  // (the real-equivalent system is analysed under the same tuning knobs)
         // The right-hand side of the device copy comes from one value slot per row: the host evaluates the sources' lists
         // and, for the refinement steps below, writes residuals there.
         {
@@ -34,10 +32,8 @@ namespace
             for(int r = 0; r <= c.rows; ++r) c.b_ptr[r] = r;
             for(int r = 0; r < c.rows; ++r) c.b_src[r] = (A.rhs0 + r) << 1;
         }
-        A.eng->opt = h->opt;
-        A.eng->hc = A.circ.hc;
-        int const rc = finish_load(A.eng);
-        if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac: " + A.eng->err);
+        // (the real-equivalent system is analysed under the same tuning knobs)
+        if(int const rc = engine_build(h->device, A.eng, h, "analyze_ac", &h->opt, A.circ.hc); rc != PE_HIP_OK) return rc;
         A.built = true;
         A.sym_omega = -1.0;
         return PE_HIP_OK;
@@ -47,8 +43,7 @@ namespace
     // ---- frequency-batched sweep (pe_hip_analyze_ac_sweep, and on the adjoint system pe_hip_analyze_noise)
     void sweep_engine_drop(pe_hip_engine::Ac::Sweep& W)
     {
-        if(W.eng) pe_hip_destroy(W.eng);  // (synchronises its stream first: nothing reads the buffers below any more)
-        W.eng = nullptr;
+        W.eng.reset();  // (synchronises its stream first: nothing reads the buffers below any more)
         W.P = 0;
         W.b0_valid = false;
         W.pass_pool.release();
@@ -61,14 +56,11 @@ namespace
     {
         auto& W = A.sweep;
         sweep_engine_drop(W);
-        if(pe_hip_create(h->device, &W.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, name + ": " + std::string(pe_hip_last_error(nullptr)));
-        W.eng->knobs = h->knobs;
-        W.eng->opt = h->opt;
-        if(keep_factors) W.eng->opt.refactor_every_solve = 0;
-        W.eng->hc = A.circ.hc;
-        W.eng->hc.batch = h->hc.batch * P;
-        int const rc = finish_load(W.eng);
-        if(rc != PE_HIP_OK) return fail(h, rc, name + ": " + W.eng->err);
+        pe_hip_options opt = h->opt;
+        if(keep_factors) opt.refactor_every_solve = 0;
+        pe::HostCircuit c = A.circ.hc;
+        c.batch = h->hc.batch * P;
+        if(int const rc = engine_build(h->device, W.eng, h, name, &opt, std::move(c)); rc != PE_HIP_OK) return rc;
         size_t const Q = static_cast<size_t>(h->hc.batch) * P, R2 = static_cast<size_t>(A.circ.hc.rows);
         double* omega{};
         int* point{};
@@ -105,8 +97,7 @@ namespace pe_eng
     // its system with both engines first, then -- by assigning a fresh state, whose pools free what they hold -- tables, buffers, result.
     void ac_sweep_drop(pe_hip_engine* h)
     {
-        sweep_engine_drop(h->ac.sweep);
-        h->ac.sweep = pe_hip_engine::Ac::Sweep{};
+        h->ac.sweep.drop();
         h->noise.sys.drop();
         h->noise = pe_hip_engine::Noise{};
         h->sens.sys.drop();
@@ -182,17 +173,6 @@ namespace pe_eng
     }
 }  // namespace pe_eng
 
-// Engines are destroyed BEFORE the buffers their kernels read are freed: pe_hip_destroy synchronises the engine's stream first.
-void pe_hip_engine::Ac::drop()
-{
-    sweep_engine_drop(sweep);
-    if(eng) pe_hip_destroy(eng);
-    if(d_xacc) (void)hipFree(d_xacc);
-    if(d_b0) (void)hipFree(d_b0);
-    if(d_worst) (void)hipFree(d_worst);
-    *this = Ac{};  // (the sweep's pools and kept rows free what they hold)
-}
-
 extern "C" {
 
 /* Small-signal AC at angular frequency omega (circult::solve_once with iterate_ac, run once per sweep point by
@@ -252,7 +232,7 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
             }
             A.eng->sym_values_override[s] = acc;
         }
-        A.eng->sym_class = -1;
+        A.eng->resident.sym_class = -1;
         A.sym_omega = omega;
     };
     bool const stale = A.sym_omega < 0.0 || (omega == 0.0) != (A.sym_omega == 0.0) ||
@@ -271,23 +251,16 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
         double* d = &dv[static_cast<size_t>(b) * ah.dv_len];
         for(int r = 0; r < R2; ++r) d[A.rhs0 + r] = gather(A.b_ptr0.data(), A.b_src0.data(), d, r);
     }
-    if(A.d_len != static_cast<size_t>(B) * R2)
-    {
-        if(A.d_xacc) (void)hipFree(A.d_xacc);
-        if(A.d_b0) (void)hipFree(A.d_b0);
-        A.d_xacc = A.d_b0 = nullptr;
-        A.d_len = static_cast<size_t>(B) * R2;
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&A.d_xacc), A.d_len * sizeof(double)));
-        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&A.d_b0), A.d_len * sizeof(double)));
-        if(!A.d_worst) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&A.d_worst), sizeof(double)));
-    }
+    HIPCHK(h, A.d_xacc.ensure(static_cast<size_t>(B) * R2, false));
+    HIPCHK(h, A.d_b0.ensure(static_cast<size_t>(B) * R2, false));
+    HIPCHK(h, A.d_worst.ensure(1, false));
     auto solve = [&](bool upload) -> int
     {
         // every AC point is an independent linear solve: no sticky failure state, no history.  A correction solve keeps the device's
         // value vector: its right-hand-side slots hold the residual the kernel before wrote there.
         if(upload) HIPCHK(h, hipMemcpy(A.eng->V.dv, dv.data(), dv.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(h, hipMemset(A.eng->V.status, 0, static_cast<size_t>(B) * sizeof(int)));
-        return pe_hip_analyze_dc(A.eng, PE_HIP_MODE_DC, st);
+        return pe_hip_analyze_dc(A.eng.get(), PE_HIP_MODE_DC, st);
     };
     A.b0_valid = false;
     int rc = solve(true);
@@ -305,22 +278,22 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
     // (pe::ac_needs_refinement), the iterate the last correction produced gets a residual evaluation of its own, and phasors whose final
     // backward error is not finite are not returned as PE_HIP_OK.
     hipStream_t const es = A.eng->stream;
-    HIPCHK(h, pe::launch_ac_accumulate(es, A.eng->V, A.d_xacc, A.d_b0, true));
+    HIPCHK(h, pe::launch_ac_accumulate(es, A.eng->V, A.d_xacc.p, A.d_b0.p, true));
     A.b0_valid = true;
     double worst = 0.0;
     for(int round = 0;; ++round)
     {
-        HIPCHK(h, pe::launch_ac_residual(es, A.eng->V, A.d_xacc, A.d_b0, A.rhs0, A.d_worst));
-        HIPCHK(h, hipMemcpyAsync(&worst, A.d_worst, sizeof(double), hipMemcpyDeviceToHost, es));
+        HIPCHK(h, pe::launch_ac_residual(es, A.eng->V, A.d_xacc.p, A.d_b0.p, A.rhs0, A.d_worst.p));
+        HIPCHK(h, hipMemcpyAsync(&worst, A.d_worst.p, sizeof(double), hipMemcpyDeviceToHost, es));
         HIPCHK(h, hipStreamSynchronize(es));
         if(!pe::ac_needs_refinement(worst) || round == 3) break;
         rc = solve(false);
         if(rc != PE_HIP_OK) return fail(h, rc, "analyze_ac (refinement): " + A.eng->err);
-        HIPCHK(h, pe::launch_ac_accumulate(es, A.eng->V, A.d_xacc, A.d_b0, false));
+        HIPCHK(h, pe::launch_ac_accumulate(es, A.eng->V, A.d_xacc.p, A.d_b0.p, false));
     }
     if(!std::isfinite(worst)) return fail(h, PE_HIP_ERR_INACCURATE, "analyze_ac: the backward error of the refined solution is not finite");
-    A.x.resize(A.d_len);
-    HIPCHK(h, hipMemcpyAsync(A.x.data(), A.d_xacc, A.d_len * sizeof(double), hipMemcpyDeviceToHost, es));
+    A.x.resize(A.d_xacc.len);
+    HIPCHK(h, hipMemcpyAsync(A.x.data(), A.d_xacc.p, A.d_xacc.len * sizeof(double), hipMemcpyDeviceToHost, es));
     HIPCHK(h, hipStreamSynchronize(es));
     return PE_HIP_OK;
 }
@@ -506,25 +479,25 @@ namespace
             // analysis yet one is made on a band's values and forgotten again: pe_hip_analyze_ac then analyses as it always did.  A band
             // whose values cannot be analysed (a singular system at its omega) says nothing about the others: the next band is tried, and
             // when none can be analysed the sweep runs one point per pass -- its bands then fail one by one into the single-point path.
-            bool const had = A.eng->sym_class >= 0;
+            bool const had = A.eng->resident.sym_class >= 0;
             int src = had ? PE_HIP_OK : PE_HIP_ERR_SINGULAR;
             for(size_t k = 0; !had && k < bands.size() && src != PE_HIP_OK; ++k)
             {
                 representative(omegas[order[bands[k].first]], A.eng->sym_values_override);
-                A.eng->sym_class = -1;
-                src = ensure_symbolic(A.eng, false, 0.0);
+                A.eng->resident.sym_class = -1;
+                src = ensure_symbolic(A.eng.get(), false, 0.0);
                 if(src != PE_HIP_OK && !numerical(src))
                 {
-                    A.eng->sym_class = -1;
+                    A.eng->resident.sym_class = -1;
                     A.sym_omega = -1.0;
                     return fail(h, src, K.name + " (sizing): " + A.eng->err);
                 }
             }
             pe_hip_info info{};
-            int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng, &info) : PE_HIP_OK;
+            int const rc = src == PE_HIP_OK ? pe_hip_get_info(A.eng.get(), &info) : PE_HIP_OK;
             if(!had)
             {
-                A.eng->sym_class = -1;
+                A.eng->resident.sym_class = -1;
                 A.sym_omega = -1.0;
             }
             if(rc != PE_HIP_OK) return fail(h, rc, K.name + " (sizing): " + A.eng->err);
@@ -539,7 +512,7 @@ namespace
         // ---- result buffers on the device
         if(int const rc = K.prepare(P); rc != PE_HIP_OK) return rc;
 
-        pe_hip_engine* const E = W.eng;
+        pe_hip_engine* const E = W.eng.get();
         hipStream_t const es = E->stream;
         int const Q = B * P;
         std::vector<char> failed(static_cast<size_t>(n_points), 0);
@@ -551,9 +524,9 @@ namespace
         auto solve = [&](bool kept = false) -> int
         {
             HIPCHK(h, hipMemset(E->V.status, 0, static_cast<size_t>(Q) * sizeof(int)));
-            long long const f0 = E->n_factor_launches, r0 = E->n_rematched;
+            long long const f0 = E->n_factor_launches, r0 = E->resident.n_rematched;
             int rc = kept ? dc_solve_kept(E, PE_HIP_MODE_DC, nullptr) : pe_hip_analyze_dc(E, PE_HIP_MODE_DC, nullptr);
-            if(K.keep_factors && !kept && E->n_rematched != r0 && (rc == PE_HIP_OK || numerical(rc)))
+            if(K.keep_factors && !kept && E->resident.n_rematched != r0 && (rc == PE_HIP_OK || numerical(rc)))
             {
                 // the safety net re-matched the pivot order inside the factoring solve: only the instances it retried hold factors of the new
                 // order, and the solves that follow keep them -- every instance factors again under it (as dc_solve_kept does for its own)
@@ -650,7 +623,7 @@ namespace
             // (a structurally or numerically singular system at w0, e.g. a node held by capacitors only at omega = 0) fail the BAND, not the
             // sweep: nothing is launched for it and each of its points goes to the single-point path, which reports that point's own status.
             representative(omegas[order[bd.first]], E->sym_values_override);
-            E->sym_class = -1;
+            E->resident.sym_class = -1;
             ++S.n_analyses;
             if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK)
             {
@@ -676,7 +649,7 @@ namespace
                 continue;
             }
             representative(omegas[i], E->sym_values_override);
-            E->sym_class = -1;
+            E->resident.sym_class = -1;
             ++S.n_analyses;
             if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK)
             {
@@ -820,7 +793,7 @@ int pe_hip_get_matrix_ac(pe_hip_engine* h, int which, int instance, int nnz_capa
     if(!h || !h->loaded || which < 0 || which > 4 || nnz_capacity < 0) return PE_HIP_ERR_ARG;
     auto& A = which < 2 ? h->ac : which < 4 ? h->noise.sys : h->sens.sys;
     bool const batched = (which & 1) != 0 || which == 4;
-    pe_hip_engine* const E = batched ? A.sweep.eng : A.eng;
+    pe_hip_engine* const E = batched ? A.sweep.eng.get() : A.eng.get();
     if(!A.built || !E || !E->loaded) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: that engine does not exist yet");
     int const R2 = E->hc.rows, nz = static_cast<int>(E->hc.ci.size());
     if(n_rows) *n_rows = R2;
@@ -831,8 +804,8 @@ int pe_hip_get_matrix_ac(pe_hip_engine* h, int which, int instance, int nnz_capa
     if(int const rc = pe_hip_get_matrix(E, instance, row_ptr, col_ind, vals, nullptr); rc != PE_HIP_OK) return fail(h, rc, "get_matrix_ac: " + E->err);
     if(rhs)
     {
-        double const* b0 = batched ? A.sweep.V.b0 : A.d_b0;
-        bool const valid = batched ? A.sweep.b0_valid : (A.b0_valid && A.d_len == static_cast<size_t>(E->hc.batch) * R2);
+        double const* b0 = batched ? A.sweep.V.b0 : A.d_b0.p;
+        bool const valid = batched ? A.sweep.b0_valid : (A.b0_valid && A.d_xacc.len == static_cast<size_t>(E->hc.batch) * R2);
         if(!b0 || !valid) return fail(h, PE_HIP_ERR_ARG, "get_matrix_ac: no right-hand side has been stamped on that engine (its last solve failed, or none ran)");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipMemcpy(rhs, b0 + static_cast<size_t>(instance) * R2, static_cast<size_t>(R2) * sizeof(double), hipMemcpyDeviceToHost));

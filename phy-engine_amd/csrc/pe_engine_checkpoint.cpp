@@ -167,11 +167,10 @@ int pe_hip_checkpoint_load(pe_hip_engine* h, const void* buffer, size_t size)
     if(has_history)
     {
         HIPCHK(h, hipMemcpy(h->V.tr_hist, static_cast<char const*>(buffer) + trap_size + sizeof(long long), ck_hist_bytes(h), hipMemcpyHostToDevice));
-        h->integ_hp = std::nan("");  // (per instance in the blob: the host knows no common one)
+        h->resident.integ_hp = std::nan("");  // (per instance in the blob: the host knows no common one)
         h->integ_failed = true;      // (... nor whether a saved status is a failed step's: looked at before the next steps)
     }
-    h->fact_valid = false;
-    h->a_static.clear();
+    invalidate_factors(h);
     return PE_HIP_OK;
 }
 

@@ -1,13 +1,16 @@
 // pe_engine_internal.hpp -- what the translation units of the engine share: the engine object behind the opaque pe_hip_engine handle of
 // include/pe_hip.h, its device-memory pools, the error convention, and the helpers that cross file boundaries.  Not installed, not part
 // of the C ABI.
-//   pe_engine.cpp             handle life cycle, options, circuit load, getters / setters, the solve_csr_real seam
+// The owning types come first (Pool, DevBuf, KeptRows for device memory; Pinned, Event, Stream, EnginePtr, GraphsPtr for what else the
+// engine holds), then the engine object -- whose declaration order IS its destruction order --, then the shared helpers.
+//   pe_engine.cpp             handle life cycle (pe_hip_create, pe_hip_destroy, engine_build), options, circuit load, getters / setters, the solve_csr_real seam
 //   pe_engine_policy.cpp      launch geometry by batch size, symbolic analysis + its upload (the PHY_ENGINE_HIP_* knobs live here)
 //   pe_engine_newton.cpp      host-driven Newton / transient loops of the split schedule, residual safety net, pe_hip_analyze_tr / _dc
 //   pe_engine_checkpoint.cpp  pe_hip_checkpoint_*
 //   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep, pe_hip_analyze_noise / pe_hip_get_noise*,
 //                             pe_hip_analyze_sens / pe_hip_get_sens*, pe_hip_analyze_net / pe_hip_get_net*; the helpers of every stored result (KeptRows, stored_window)
 //   pe_engine_seam.cpp        pe_hip_solve_csr_complex (the complex twin of the solver seam)
+//   pe_sweep.cpp              pe_hip_sweep_*: the multi-device handle (uses EnginePtr and engine_build only; everything else through the C ABI)
 #pragma once
 // (the helpers below are shared between the engine's translation units only: not exported from libpe_hip.so)
 #define PE_ENG_HIDDEN __attribute__((visibility("hidden")))
@@ -160,15 +163,102 @@ namespace pe_eng  // (Pool is a member type of the engine object: default visibi
         int set(pe_hip_engine* h, char const* name, int n_rows, int const* rows_in);  // (the owner's stored result is the caller's to invalidate)
         int upload(pe_hip_engine* h, int const*& keep_out);                            // keep_out: the device copy, nullptr for all rows
     };
+
+    // a pinned host buffer of n T, kept while it is large enough (flags: hipHostMallocCoherent | hipHostMallocMapped for memory the device
+    // writes and the host polls -- device() is then the same memory as the device sees it)
+    template <class T>
+    struct Pinned
+    {
+        Pinned() = default;
+        Pinned(Pinned&& o) noexcept { *this = std::move(o); }
+        Pinned& operator=(Pinned&& o) noexcept
+        {
+            if(this != &o) release(), p = std::exchange(o.p, nullptr), dev = std::exchange(o.dev, nullptr), cap = std::exchange(o.cap, 0);
+            return *this;
+        }
+        ~Pinned() { release(); }
+        void release()
+        {
+            if(p) (void)hipHostFree(p);
+            p = dev = nullptr;
+            cap = 0;
+        }
+        hipError_t ensure_at_least(size_t n, unsigned flags = hipHostMallocDefault)
+        {
+            if(cap >= n && p) return hipSuccess;
+            release();
+            void* q{};
+            hipError_t e = hipHostMalloc(&q, std::max<size_t>(n, 1) * sizeof(T), flags);
+            if(e != hipSuccess) return e;
+            p = static_cast<T*>(q);
+            if(flags & hipHostMallocMapped)
+            {
+                if(e = hipHostGetDevicePointer(&q, p, 0); e != hipSuccess) return release(), e;
+                dev = static_cast<T*>(q);
+            }
+            cap = n;
+            return hipSuccess;
+        }
+        T* data() const { return p; }
+        T* device() const { return dev; }
+        size_t capacity() const { return cap; }
+
+    private:
+        T *p{}, *dev{};
+        size_t cap{};
+    };
+
+    // an event / a stream: made by create() (a default-constructed one holds nothing), destroyed with its owner
+    template <class H, hipError_t (*Destroy)(H)>
+    struct Handle
+    {
+        H h{};
+        Handle() = default;
+        Handle(Handle&& o) noexcept : h(std::exchange(o.h, H{})) {}
+        Handle& operator=(Handle&& o) noexcept
+        {
+            if(this != &o) reset(), h = std::exchange(o.h, H{});
+            return *this;
+        }
+        ~Handle() { reset(); }
+        void reset() { h = h ? ((void)Destroy(h), H{}) : H{}; }
+        operator H() const { return h; }
+    };
+    struct Event : Handle<hipEvent_t, hipEventDestroy>
+    {
+        hipError_t create() { return reset(), hipEventCreate(&h); }
+    };
+    struct Stream : Handle<hipStream_t, hipStreamDestroy>
+    {
+        hipError_t create() { return reset(), hipStreamCreate(&h); }
+    };
+
+    // an engine owned by another object (the sub-engines of the analyses, the engines of a pe_hip_sweep: pe_hip_destroy synchronises its
+    // stream before anything of it goes), and the captured-graph cache of an engine (pe_kernels.hpp)
+    template <class T, void (*Destroy)(T*)>
+    struct Deleter
+    {
+        void operator()(T* p) const { Destroy(p); }
+    };
+    using EnginePtr = std::unique_ptr<pe_hip_engine, Deleter<pe_hip_engine, pe_hip_destroy>>;
+    using GraphsPtr = std::unique_ptr<pe::M2GraphCache, Deleter<pe::M2GraphCache, pe::m2_graphs_destroy>>;
 }  // namespace pe_eng
 using pe_eng::Pool;
 
+// Everything the engine owns is a member that frees itself, and pe_hip_destroy is "set the device, synchronise the stream, delete".  The
+// ORDER of destruction is the reverse of the declaration order below, and it matters:
+//   - stream and events are declared first: they go last, after everything that was enqueued on them;
+//   - the pools are declared before the captured-graph cache: the graphs go before the memory their nodes point into and before the stream;
+//   - the sub-engines (ac, noise, sens, net, dcs) are declared after the pools and buffers their kernels read: each goes first, and
+//     synchronises its own stream in its pe_hip_destroy.
+// A state struct that holds a sub-engine beside buffers of its own (Ac, Ac::Sweep, DcSweep) does not leave that to its member order: its
+// destructor and its drop() reset the engine explicitly before anything else goes.  Noise, Sens and Net declare their Ac last.
 struct pe_hip_engine
 {
     int device{};
-    hipStream_t stream{};
-    hipEvent_t ev0{}, ev1{};
-    hipEvent_t evk0{}, evk1{};  // around the dominant launch of one split-schedule iteration
+    pe_eng::Stream stream;
+    pe_eng::Event ev0, ev1;
+    pe_eng::Event evk0, evk1;   // around the dominant launch of one split-schedule iteration
     double dominant_ms{};       // accumulated over the current analyze call
     int dominant_launches{};
     std::string err;
@@ -185,27 +275,47 @@ struct pe_hip_engine
     pe_hip_overlay_fn overlay_fn{};
     void* overlay_user{};
     std::vector<double> ov_x, ov_a, ov_b;  // staging of the callback
-    bool singular_rematched{};    // the one re-match after a singular pivot has been spent for this resident circuit
-    bool careful{};               // residual safety net tripped on the resident kernel: stay on the host-driven (refining) schedule
-    long long n_refined{}, n_rematched{};  // solves repaired by refinement / symbolic re-analyses on an instance's own values (diagnostics)
-    // host-driven Newton loop (split schedule): pinned staging for the per-iteration `active` upload / `flags` read-back, and what
-    // the device's `active` array currently holds (an unchanged mask is not uploaded again)
-    int* pin_active{};
-    int* pin_flags{};
-    size_t pin_cap{};
+    // What belongs to the resident circuit and is not a buffer: pe_hip_load_circuit resets ALL of it by assigning a fresh Resident, so a
+    // field added here cannot carry one circuit's state into the next.  Reset: the class and dt of the symbolic analysis (the next analysis
+    // is made again), the validity of the factors and of the static matrix stamps (the matrix is gone), what the device's `active` array
+    // holds (the array is gone), the safety net's verdicts and counters and the launch counters (they speak of the circuit), the tables of
+    // the static fronts and the statistics scratch (pointers into pools the load releases), and the host's view of the BE / GEAR2 history.
+    // NOT here, because a load keeps them: device, lds_limit, opt, knobs, tr_method (engine settings); the overlay, its callback and the
+    // digital drives (part of the pattern of the NEXT load); param_epoch, n_symbolic, analyze_ms, dominant_* (monotone or per-call
+    // diagnostics); graph_mode (chosen again by the next solve point; only active_dev is cleared beside it); pub_seq and the pinned
+    // buffers (sized by the largest batch so far, content per call); csr / csrz (the seam's own state).  fact_dt, a_static_dt, integ_failed,
+    // refined_in_point and n_factor_launches stay as a load has always left them: read behind a flag reset here, written before use, or read as a difference.
+    struct Resident
+    {
+        int sym_class{-1};  // 0: static (OP/DC/TROP) pattern weights, 1: TR
+        double sym_dt{};    // time step whose companion values the TR analysis was matched on
+        bool fact_valid{};
+        // split schedule: instances whose matrix (aval) holds a FULL transient stamp at step size a_static_dt -- their next steps at that dt
+        // stamp the x-dependent slots only (pe_engine_newton.cpp run_m2_tr); cleared together with fact_valid wherever a static value may
+        // change (invalidate_factors)
+        std::vector<char> a_static;
+        std::vector<int> active_dev;  // what the device's `active` array currently holds (an unchanged mask is not uploaded again)
+        bool singular_rematched{};    // the one re-match after a singular pivot has been spent for this resident circuit
+        bool careful{};               // residual safety net tripped on the resident kernel: stay on the host-driven (refining) schedule
+        long long n_refined{}, n_rematched{};  // solves repaired by refinement / symbolic re-analyses on an instance's own values (diagnostics)
+        // static fronts of the lane-group kernel (pe_device.hpp StaticSkip): the tables of the current analysis (sym_pool; all null
+        // when it has no static quad front) and the quad factor launches since the circuit was loaded, by program
+        pe::StaticSkip static_skip{};
+        long long quad_skipped_launches{}, quad_full_launches{};
+        // iteration launches of the lane-group factor kernel issued after a refinement round of their own solve point, and those of them
+        // that skipped the static fronts (must stay 0: pe_hip_get_static_skip_refinement_stats)
+        long long quad_launches_after_refinement{}, quad_skipped_after_refinement{};
+        double* stats_scratch{};      // pe_hip_sweep_statistics: partial sums + result (device, owned by circ_pool)
+        size_t stats_doubles{};
+        double integ_hp{};            // (see tr_method below)
+    } resident;
+    // host-driven Newton loop (split schedule): pinned staging for the per-iteration `active` upload / `flags` read-back (grown together)
+    pe_eng::Pinned<int> pin_active, pin_flags;
     // results published by the last launch of an iteration straight into pinned host memory (k_m2_publish): [sequence number][flags][norms]
-    void* pub_host{};
-    void* pub_dev{};  // the same memory as the device sees it
-    size_t pub_cap{};
+    pe_eng::Pinned<char> pub;
     unsigned long long pub_seq{};
-    std::vector<int> active_dev;
-    // captured launch sequences of the split schedule's Newton iteration (small sweeps; pe_kernels.hip launch_m2_iteration_graph)
-    pe::M2GraphCache* graphs{};
     bool graph_mode{};            // the quad list behind the device's `active` mask is laid out for a captured sequence (full grid)
-    double* stats_scratch{};      // pe_hip_sweep_statistics: partial sums + result (device, owned by circ_pool)
-    size_t stats_doubles{};
-    double* stats_pinned{};       // pinned host landing buffer of its result (owned by the engine)
-    size_t stats_pinned_bytes{};
+    pe_eng::Pinned<double> stats_pinned;  // pinned host landing buffer of the result of pe_hip_sweep_statistics
     // transient probes (pe_hip_set_probes / pe_hip_arm_probes, pe_probe.hpp): configuration and device buffers (dropped by a circuit
     // load) and the armed window.  The engine's view V never carries them; the launches that record get probe_view(h).
     struct Probes
@@ -215,9 +325,8 @@ struct pe_hip_engine
         int n_probes{}, n_meas{}, capacity{}, stride{}, batch{};
         std::vector<int> kind;     // per measure (the host finishes AVG / RMS)
         pe::ProbeView pv{};        // device buffers
-        int* pin_accept{};         // pinned staging of the split schedule's accepted set
-        size_t pin_cap{};
     } probe;
+    pe_eng::Pinned<int> pin_accept;  // pinned staging of the split schedule's accepted set of the probes (kept across loads)
     // Fourier analysis of probes (pe_hip_set_fourier, pe_fourier.hpp): rides on the probe configuration and its armed window; dropped with it
     struct Fourier
     {
@@ -253,49 +362,37 @@ struct pe_hip_engine
     // alone -- and then nothing that is keyed on the companion conductance a0 is reused.
     int tr_method{};
     Pool integ_pool;
-    double integ_hp{};
     bool integ_failed{};  // some instance's last step failed under BE / GEAR2: its history restarts before its next step
     long long n_symbolic{};  // symbolic analyses of the resident circuit so far (ensure_symbolic)
     Pool circ_pool;  // topology, params, state
     Pool sym_pool;   // symbolic arrays + factor storage
     pe::Symbolic sym;
-    int sym_class{-1};  // 0: static (OP/DC/TROP) pattern weights, 1: TR
-    double sym_dt{};    // time step whose companion values the TR analysis was matched on
     pe::DevView V{};
-    bool fact_valid{};
-    double fact_dt{};
-    // split schedule: instances whose matrix (aval) holds a FULL transient stamp at step size a_static_dt -- their next steps at that dt stamp
-    // the x-dependent slots only (pe_engine_newton.cpp run_m2_tr); cleared together with fact_valid wherever a static value may change
-    std::vector<char> a_static;
-    double a_static_dt{-1.0};
+    double fact_dt{};           // (of resident.fact_valid)
+    double a_static_dt{-1.0};   // (of resident.a_static)
     double analyze_ms{};
-    // static fronts of the lane-group kernel (pe_device.hpp StaticSkip): the tables of the current analysis (sym_pool; all null when
-    // it has no static quad front) and the quad factor launches since the circuit was loaded, by program
-    pe::StaticSkip static_skip{};
-    long long quad_skipped_launches{}, quad_full_launches{};
-    // iteration launches of the lane-group factor kernel issued after a refinement round of their own solve point, and those of them that
-    // skipped the static fronts (must stay 0: pe_hip_get_static_skip_refinement_stats)
-    long long quad_launches_after_refinement{}, quad_skipped_after_refinement{};
     bool refined_in_point{};  // a refinement round has run since the first iteration of the current solve point (m2_point)
+    // captured launch sequences of the split schedule's Newton iteration (small sweeps; pe_kernels.hip launch_m2_iteration_graph): after
+    // the pools above, so that it goes before them
+    pe_eng::GraphsPtr graphs;
 
     // small-signal AC: a second engine holding the real-equivalent 2N system (pe_ac.hpp), built on first use
     struct Ac
     {
-        pe_hip_engine* eng{};
+        pe_eng::EnginePtr eng;
         pe::AcCircuit circ;
         bool built{};
         double sym_omega{-1.0};  // frequency whose values the pivot matching of the current symbolic analysis saw
         std::vector<int> b_ptr0, b_src0;  // right-hand-side lists of the AC system (the device copy reads one slot per row)
         int rhs0{};                       // first of the 2N right-hand-side slots of the AC value vector
         std::vector<double> x;            // refined solution [batch][2N]
-        double *d_xacc{}, *d_b0{}, *d_worst{};  // device: accumulated solution, the point's right-hand side, worst backward error (refinement)
-        size_t d_len{};
+        pe_eng::DevBuf<double> d_xacc, d_b0, d_worst;  // device: accumulated solution, the point's right-hand side, worst backward error (refinement)
         bool b0_valid{};  // d_b0 holds the right-hand side of the last pe_hip_analyze_ac as stamped (pe_hip_get_matrix_ac)
         // frequency-batched sweep (pe_hip_analyze_ac_sweep): a third engine holding the same system with batch (circuit batch) x P -- the
         // points of one pass are extra instances --, the buffers of its kernels (pe_ac_sweep.hpp) and the stored result
         struct Sweep
         {
-            pe_hip_engine* eng{};
+            pe_eng::EnginePtr eng;
             int P{};                          // points per pass the engine was built for
             bool b0_valid{};                  // V.b0 holds the right-hand sides of the last pass as stamped (pe_hip_get_matrix_ac)
             Pool pass_pool;                   // sized by batch x P: xacc, b0, worst, omega, point, n_above
@@ -307,15 +404,19 @@ struct pe_hip_engine
             bool valid{};                     // `res` is the sweep of the current circuit at its current operating point
             int n_points{}, n_keep{}, batch{};
             std::vector<double> res;          // [2][n_points][batch][n_keep]: real parts, then imaginary parts
+            Sweep& operator=(Sweep&&) = default;
+            ~Sweep() { eng.reset(); }
+            void drop() { eng.reset(), *this = Sweep{}; }  // the engine first (it synchronises its stream), then every buffer: a fresh Sweep
         } sweep;
-        void drop();  // both engines, then every buffer: back to a fresh Ac (pe_engine_ac.cpp)
+        Ac& operator=(Ac&&) = default;
+        ~Ac() { sweep.eng.reset(), eng.reset(); }
+        void drop() { sweep.eng.reset(), eng.reset(), *this = Ac{}; }  // both engines, then every buffer: a fresh Ac
     } ac;
     // noise analysis (pe_hip_analyze_noise, pe_noise.hpp): the ADJOINT real-equivalent system with sweep state of its own -- its AcCircuit,
     // its single-point engine (only the automatic pass size is measured on it), its batched engine and pass buffers -- so that a stored
     // forward sweep is not disturbed; the source table of the circuit, the densities of the last call and its result
     struct Noise
     {
-        Ac sys;
         bool have_pair{};
         int out_pos{-1}, out_neg{-1};     // the output pair the right-hand-side lists of `sys` select
         bool table_built{}, table_on_device{};
@@ -331,13 +432,13 @@ struct pe_hip_engine
         int n_points{}, batch{};
         std::vector<double> res;          // [n_points][batch] densities, then [n_points][batch][n_src] contributions when kept
         std::vector<double> integrated;   // [batch]
+        Ac sys;                           // (declared last: its engines go before the tables and buffers above)
     } noise;
     // DC sensitivity analysis (pe_hip_analyze_sens, pe_sens.hpp): the adjoint system at omega = 0 with sweep state of its own, like the noise
     // analysis -- the outputs of a call are the points of its passes --, the parameter table and the by-slot stamp lists of the circuit,
     // the raw columns of the last call and its result
     struct Sens
     {
-        Ac sys;
         bool table_built{}, table_on_device{};
         std::vector<pe::SensParam> par;   // definition order of include/pe_hip.h
         std::vector<int> kind, index, column;
@@ -353,13 +454,13 @@ struct pe_hip_engine
         bool kept{}, weighted{};
         int n_outputs{}, batch{};
         std::vector<double> res;          // [n_outputs][batch] rss (weighted), then [n_outputs][batch][n_par] sensitivities (kept)
+        Ac sys;                           // (declared last: its engines go before the tables and buffers above)
     } sens;
     // multi-port network analysis (pe_hip_analyze_net, pe_net.hpp): the FORWARD real-equivalent system with sweep state of its own, like the
     // noise analysis -- its right-hand-side lists hold port 0's selector instead of the circuit's AC sources, the other ports' selectors are
     // written per pass (k_net_rhs) --, the ports of the last call on the device and its result
     struct Net
     {
-        Ac sys;
         bool have_port0{};
         int pos0{-1}, neg0{-1};           // the port the right-hand-side lists of `sys` select
         Pool port_pool;                   // port rows and reference resistances (PE_HIP_NET_MAX_PORTS each)
@@ -372,13 +473,14 @@ struct pe_hip_engine
         int n_points{}, batch{}, n_ports{};
         std::vector<double> res;          // the six planes, [n_points][batch][n_ports][n_ports] each
         std::vector<int> status;          // [2][n_points][batch]
+        Ac sys;                           // (declared last: its engines go before the tables and buffers above)
     } net;
     long long n_factor_launches{};  // batched numeric factorisations launched by dc_solve / dc_solve_kept on this engine (its first attempt and every retry group)
     // DC sweep (pe_hip_analyze_dc_sweep, pe_dc_sweep.hpp): an engine of its own holding this circuit with batch (circuit batch) x P -- the
     // points of one pass are extra instances --, the buffers of its kernels and the stored result.  The main engine is only read.
     struct DcSweep
     {
-        pe_hip_engine* eng{};
+        pe_eng::EnginePtr eng;
         int P{};                          // slots per pass the engine was built for
         long long epoch{-1};              // param_epoch of the main engine it was built from (parameters, options, knobs)
         Pool pass_pool;                   // sized by batch x P
@@ -390,6 +492,9 @@ struct pe_hip_engine
         int n_points{}, n_keep{}, batch{};
         std::vector<double> res;          // [n_points][batch][n_keep]
         std::vector<int> status, iters, seed;  // [n_points][batch]
+        DcSweep& operator=(DcSweep&&) = default;
+        ~DcSweep() { eng.reset(); }
+        void drop() { eng.reset(), *this = DcSweep{}; }  // the engine first (it synchronises its stream), then every buffer: a fresh DcSweep
     } dcs;
     // operating point with gmin / source stepping (pe_hip_analyze_op_stepping, pe_op_step.hpp): the controller's per-instance arrays and
     // the shadow of the state a DC solve reads (allocated at the first call, dropped by a circuit load), the log (sized by the call's
@@ -469,6 +574,16 @@ namespace pe_eng PE_ENG_HIDDEN
     void apply_options(pe_hip_engine* h, pe::DevView& V);
     int stats_chunks(int batch);
     int finish_load(pe_hip_engine* h);
+    // The one builder of an owned engine: a fresh one on `device` into `out`, emptied first.  With a parent h: under h's knobs and `opt`,
+    // holding `hc`, loaded (finish_load) -- a failure is h's error "<name>: ...".  Without (pe_hip_sweep): the defaults, nothing loaded, the
+    // message is pe_hip_last_error(nullptr).  On any failure `out` stays empty: nothing half-built is kept.
+    int engine_build(int device, EnginePtr& out, pe_hip_engine* h = nullptr, std::string const& name = {}, pe_hip_options const* opt = nullptr, pe::HostCircuit hc = {});
+    // a static value of the matrix may have changed: neither the factors nor the full transient stamps of the split schedule stand
+    inline void invalidate_factors(pe_hip_engine* h)
+    {
+        h->resident.fact_valid = false;
+        h->resident.a_static.clear();
+    }
     void fill_static_dv(pe_hip_engine const* h, std::vector<double>& dv);
     int collect_stats(pe_hip_engine* h, std::vector<long long> const& steps0, std::vector<long long> const& iters0, pe_hip_run_stats* st);
     int snapshot_counters(pe_hip_engine* h, std::vector<long long>& s0, std::vector<long long>& i0);

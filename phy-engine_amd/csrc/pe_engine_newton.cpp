@@ -95,14 +95,8 @@ namespace pe_eng PE_ENG_HIDDEN
 
     int ensure_pinned(pe_hip_engine* h, size_t n)
     {
-        if(h->pin_cap >= n) return PE_HIP_OK;
-        if(h->pin_active) (void)hipHostFree(h->pin_active);
-        if(h->pin_flags) (void)hipHostFree(h->pin_flags);
-        h->pin_active = h->pin_flags = nullptr;
-        h->pin_cap = 0;
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_active), n * sizeof(int), hipHostMallocDefault));
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_flags), n * sizeof(int), hipHostMallocDefault));
-        h->pin_cap = n;
+        HIPCHK(h, h->pin_active.ensure_at_least(n));
+        HIPCHK(h, h->pin_flags.ensure_at_least(n));
         return PE_HIP_OK;
     }
     // `active` mask of the next launches (stream-ordered).  The caller synchronises the stream before it changes the mask again,
@@ -112,17 +106,17 @@ namespace pe_eng PE_ENG_HIDDEN
     // takes instances inside that window (a sparse tail of a sweep gives short quads, padded with -1).
     int upload_active(pe_hip_engine* h, std::vector<int> const& mask)
     {
-        if(h->active_dev == mask) return PE_HIP_OK;
+        if(h->resident.active_dev == mask) return PE_HIP_OK;
         size_t const B = mask.size();
         if(int const rc = ensure_pinned(h, 5 * B); rc != PE_HIP_OK) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier upload from the staging buffer may still be in flight)
-        std::copy(mask.begin(), mask.end(), h->pin_active);
+        std::copy(mask.begin(), mask.end(), h->pin_active.data());
         size_t words = B;
         if(h->V.quad)
         {
             long long const stride = 8 * std::max({static_cast<long long>(h->V.nnzA), h->V.factor_doubles, h->V.arena_doubles, static_cast<long long>(h->V.rows)});
             long long const span = std::max<long long>(0, ((1ll << 32) - 1) / std::max<long long>(stride, 1) - 2);
-            int* ql = h->pin_active + B;
+            int* ql = h->pin_active.data() + B;
             int nq = 0, cnt = 0, first = 0;
             for(size_t b = 0; b < B; ++b)
             {
@@ -146,16 +140,16 @@ namespace pe_eng PE_ENG_HIDDEN
             h->V.q_list = h->V.active + B;
             words = B + 4 * static_cast<size_t>(nq);
         }
-        HIPCHK(h, hipMemcpyAsync(h->V.active, h->pin_active, words * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        h->active_dev = mask;
+        HIPCHK(h, hipMemcpyAsync(h->V.active, h->pin_active.data(), words * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        h->resident.active_dev = mask;
         return PE_HIP_OK;
     }
     int download_flags(pe_hip_engine* h, std::vector<int>& flags)
     {
         if(int const rc = ensure_pinned(h, flags.size()); rc != PE_HIP_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->pin_flags, h->V.flags, flags.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->pin_flags.data(), h->V.flags, flags.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::copy(h->pin_flags, h->pin_flags + flags.size(), flags.begin());
+        std::copy(h->pin_flags.data(), h->pin_flags.data() + flags.size(), flags.begin());
         return PE_HIP_OK;
     }
 
@@ -176,16 +170,11 @@ namespace pe_eng PE_ENG_HIDDEN
     int ensure_published(pe_hip_engine* h, size_t B)
     {
         size_t const need = 64 + ((B * sizeof(int) + 63) / 64) * 64 + 4 * B * sizeof(double);
-        if(h->pub_cap >= need) return PE_HIP_OK;
-        if(h->pub_host) (void)hipHostFree(h->pub_host);
-        h->pub_host = h->pub_dev = nullptr;
-        h->pub_cap = 0;
+        if(h->pub.capacity() >= need && h->pub.data()) return PE_HIP_OK;
         // (coherent + mapped, explicitly: the device's system-scope release of the sequence word must reach the polling host even where
         //  HIP_HOST_COHERENT=0 makes default pinned allocations non-coherent)
-        HIPCHK(h, hipHostMalloc(&h->pub_host, need, hipHostMallocCoherent | hipHostMallocMapped));
-        HIPCHK(h, hipHostGetDevicePointer(&h->pub_dev, h->pub_host, 0));
-        std::memset(h->pub_host, 0, need);
-        h->pub_cap = need;
+        HIPCHK(h, h->pub.ensure_at_least(need, hipHostMallocCoherent | hipHostMallocMapped));
+        std::memset(h->pub.data(), 0, need);
         return PE_HIP_OK;
     }
     // waits for the publication with sequence number `seq` (launched by the caller: launch_m2_publish, or the last node of a captured
@@ -193,7 +182,7 @@ namespace pe_eng PE_ENG_HIDDEN
     int wait_published(pe_hip_engine* h, std::vector<int>& flags, std::vector<double>* eta, unsigned long long seq)
     {
         size_t const B = flags.size();
-        auto const host = pub_view(h->pub_host, B);
+        auto const host = pub_view(h->pub.data(), B);
         for(unsigned spins = 0; __atomic_load_n(host.seq, __ATOMIC_ACQUIRE) != seq; ++spins)
         {
             if((spins & 1023u) == 1023u)
@@ -217,7 +206,7 @@ namespace pe_eng PE_ENG_HIDDEN
     {
         size_t const B = flags.size();
         if(int const rc = ensure_published(h, B); rc != PE_HIP_OK) return rc;
-        auto const dev = pub_view(h->pub_dev, B);
+        auto const dev = pub_view(h->pub.device(), B);
         unsigned long long const seq = ++h->pub_seq;
         HIPCHK(h, pe::launch_m2_publish(h->stream, h->V, dev.flags, dev.eta, dev.seq, seq));
         return wait_published(h, flags, eta, seq);
@@ -279,7 +268,7 @@ namespace pe_eng PE_ENG_HIDDEN
             // (a refactorisation with the residual riding along: the update vectors of the static roots and the kept forward-substituted
             //  pivots no longer belong to this point's right-hand side -- no later iteration of the point may skip the static fronts)
             h->refined_in_point = true;
-            if(h->V.quad && h->V.n_quads > 0) ++h->quad_full_launches;
+            if(h->V.quad && h->V.n_quads > 0) ++h->resident.quad_full_launches;
             HIPCHK(h, hipStreamSynchronize(h->stream));
             if(int const rc = pull_eta(); rc != PE_HIP_OK) return rc;
             std::vector<int> fl(B);
@@ -290,7 +279,7 @@ namespace pe_eng PE_ENG_HIDDEN
                 S.flags[b] = fl[b];
                 if((fl[b] & 5) == 0 && bad(b)) still.push_back(b);
                 else
-                    ++h->n_refined;
+                    ++h->resident.n_refined;
             }
             todo.swap(still);
         }
@@ -330,13 +319,13 @@ namespace pe_eng PE_ENG_HIDDEN
         if(graph_mode != h->graph_mode)
         {
             h->graph_mode = graph_mode;
-            h->active_dev.clear();  // (the quad list behind the mask is laid out differently)
+            h->resident.active_dev.clear();  // (the quad list behind the mask is laid out differently)
         }
-        if(graph_mode && !h->graphs) h->graphs = pe::m2_graphs_create();
+        if(graph_mode && !h->graphs) h->graphs.reset(pe::m2_graphs_create());
         // Static fronts of the lane-group kernel: the iterations after the first of this point skip them -- unless anything but the
         // x-dependent stamp may have touched the matrix, the right-hand side or what the first iteration left behind.  Knob STATIC_SKIP = 0: never.
         h->refined_in_point = false;
-        bool const may_skip_static = h->static_skip.q_prog_dyn && h->hc.nonlinear && do_factor && !has_overlay(h) && h->V.quad && h->V.n_mid == 0 &&
+        bool const may_skip_static = h->resident.static_skip.q_prog_dyn && h->hc.nonlinear && do_factor && !has_overlay(h) && h->V.quad && h->V.n_mid == 0 &&
                                      h->V.q_lds_stride == 0 && h->V.dyn_a && h->V.dyn_b && knob(h, "STATIC_SKIP", 1) != 0;
         for(int it = 0; it < max_it && n_active > 0; ++it)
         {
@@ -347,25 +336,25 @@ namespace pe_eng PE_ENG_HIDDEN
             static bool const full_stamp = env_int0("PHY_ENGINE_HIP_FULL_STAMP", 0) != 0;
             int const dyn = full_stamp ? 0 : (it > 0 ? 1 : (a_static_ok ? 2 : 0));
             bool const comp = it == 0 && companion_dt != nullptr;
-            pe::StaticSkip sk = h->static_skip;
+            pe::StaticSkip sk = h->resident.static_skip;
             sk.save = (may_skip_static && !full_stamp && it == 0) ? 1 : 0;
             sk.skip = (may_skip_static && !full_stamp && it > 0 && dyn == 1 && !h->refined_in_point) ? 1 : 0;
             if(do_factor && h->V.quad && h->V.n_quads > 0)
             {
-                ++(sk.skip ? h->quad_skipped_launches : h->quad_full_launches);
+                ++(sk.skip ? h->resident.quad_skipped_launches : h->resident.quad_full_launches);
                 if(it > 0 && h->refined_in_point)  // (counted whatever the knob says: the second must stay 0)
                 {
-                    ++h->quad_launches_after_refinement;
-                    if(sk.skip) ++h->quad_skipped_after_refinement;
+                    ++h->resident.quad_launches_after_refinement;
+                    if(sk.skip) ++h->resident.quad_skipped_after_refinement;
                 }
             }
             std::vector<double> eta_now;
             if(graph_mode)
             {
                 if(int const prc = ensure_published(h, static_cast<size_t>(B)); prc != PE_HIP_OK) return prc;
-                auto const dev = pub_view(h->pub_dev, static_cast<size_t>(B));
+                auto const dev = pub_view(h->pub.device(), static_cast<size_t>(B));
                 unsigned long long const seq = ++h->pub_seq;
-                HIPCHK(h, pe::launch_m2_iteration_graph_static(h->stream, h->graphs, h->V, mode, t, last_step, do_factor, dyn, comp, companion_dt ? *companion_dt : 0.0,
+                HIPCHK(h, pe::launch_m2_iteration_graph_static(h->stream, h->graphs.get(), h->V, mode, t, last_step, do_factor, dyn, comp, companion_dt ? *companion_dt : 0.0,
                                                                dev.flags, dev.eta, dev.seq, seq, sk));
                 ++launches;
                 if(int const prc = wait_published(h, S.flags, &eta_now, seq); prc != PE_HIP_OK) return prc;
@@ -489,30 +478,30 @@ namespace pe_eng PE_ENG_HIDDEN
             // (what the companion conductances of this step are a function of: dt under the trapezoidal rule, a0 under BE / GEAR2 -- a GEAR2 step after
             //  a restart has a0 = 1 / h, the following ones 3 / (2 h) at the same dt; NaN, equal to nothing, where the instances may differ)
             double const key = integ_key(h, dt);
-            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == key;
+            bool const reuse = may_reuse && h->resident.fact_valid && h->fact_dt == key;
             // The matrix of a transient step differs from the last step's only in its x-dependent slots while dt and the parameters stay (the
             // companion conductances 2C/dt, 2L/dt are constants of the step size): instances whose matrix holds a full stamp of this dt skip the
             // other 97 % of the matrix gather on the first iteration too (k_m2_stamp 0.56 -> 0.2 ms per time point at 1 024 instances).  The
-            // set is cleared wherever a static value can change (a_static_invalidate: parameters, options, load, checkpoint, re-analysis,
+            // set is cleared wherever a static value can change (invalidate_factors: parameters, options, load, checkpoint, re-analysis,
             // any OP / DC / TROP solve -- they stamp other companions); knob STATIC_A=0: always the full stamp.
             static bool const static_a = env_int0("PHY_ENGINE_HIP_STATIC_A", 1) != 0;
-            bool a_static_ok = static_a && h->a_static_dt == key && h->a_static.size() == static_cast<size_t>(B);
+            bool a_static_ok = static_a && h->a_static_dt == key && h->resident.a_static.size() == static_cast<size_t>(B);
             for(int b = 0; b < B && a_static_ok; ++b)
-                if(S.active[b] && !h->a_static[static_cast<size_t>(b)]) a_static_ok = false;
+                if(S.active[b] && !h->resident.a_static[static_cast<size_t>(b)]) a_static_ok = false;
             rc = m2_point(h, S, PE_HIP_MODE_TR, t, dt, !reuse, res, launches, (with_companion && !own_launch) ? &dt : nullptr, a_static_ok);
             if(rc == PE_HIP_OK && !a_static_ok)
             {
                 // the first iteration of this step stamped everything for the instances that were active at its start (S.active is spent by now:
                 // the mask of the step is status OK && (!only || only[b]) -- recomputed)
-                if(h->a_static_dt != key || h->a_static.size() != static_cast<size_t>(B)) h->a_static.assign(static_cast<size_t>(B), 0);
+                if(h->a_static_dt != key || h->resident.a_static.size() != static_cast<size_t>(B)) h->resident.a_static.assign(static_cast<size_t>(B), 0);
                 h->a_static_dt = key;
                 for(int b = 0; b < B; ++b)
-                    if(res[b] != 0) h->a_static[static_cast<size_t>(b)] = 1;  // (res != 0: the instance took part in this point)
+                    if(res[b] != 0) h->resident.a_static[static_cast<size_t>(b)] = 1;  // (res != 0: the instance took part in this point)
             }
             if(rc != PE_HIP_OK) return rc;
             if(may_reuse)
             {
-                h->fact_valid = true;
+                h->resident.fact_valid = true;
                 h->fact_dt = key;
             }
             if(h->tr_method != PE_HIP_TR_TRAP)
@@ -520,7 +509,7 @@ namespace pe_eng PE_ENG_HIDDEN
                 // every instance took this step and holds h_p = dt now, or the host no longer knows one h_p for all of them
                 bool all = !only;
                 for(int b = 0; b < B && all; ++b) all = S.status[b] == PE_HIP_OK && res[b] > 0;
-                h->integ_hp = all ? dt : std::nan("");
+                h->resident.integ_hp = all ? dt : std::nan("");
             }
             if(h->probe.armed) accepted.assign(B, 0);
             for(int b = 0; b < B; ++b)
@@ -558,7 +547,7 @@ namespace pe_eng PE_ENG_HIDDEN
         std::vector<double> ls(B);
         HIPCHK(h, hipMemcpy(ls.data(), h->V.last_step, B * sizeof(double), hipMemcpyDeviceToHost));
         std::vector<int> res;
-        h->a_static.clear();  // (an OP / DC / TROP stamp overwrites the transient companions in the matrix)
+        h->resident.a_static.clear();  // (an OP / DC / TROP stamp overwrites the transient companions in the matrix)
         rc = m2_point(h, S, mode, S.t[0], ls[0], do_factor, res, launches);
         if(rc != PE_HIP_OK) return rc;
         for(int b = 0; b < B; ++b)
@@ -592,16 +581,16 @@ namespace pe_eng PE_ENG_HIDDEN
         std::vector<int> failed;
         bool any_inaccurate = false;
         for(int b = 0; b < B; ++b)
-            if(status[b] == PE_HIP_ERR_INACCURATE || (status[b] == PE_HIP_ERR_SINGULAR && !h->singular_rematched))
+            if(status[b] == PE_HIP_ERR_INACCURATE || (status[b] == PE_HIP_ERR_SINGULAR && !h->resident.singular_rematched))
             {
                 failed.push_back(b);
                 any_inaccurate = any_inaccurate || status[b] == PE_HIP_ERR_INACCURATE;
             }
         if(failed.empty() || attempt >= 2) return PE_HIP_OK;
-        if(!any_inaccurate) h->singular_rematched = true;  // (once per resident circuit: a structurally singular system stays singular)
+        if(!any_inaccurate) h->resident.singular_rematched = true;  // (once per resident circuit: a structurally singular system stays singular)
         // (knob SPLIT = 0 keeps the first attempt of every call on the resident kernel, which only detects: the first retry of such a call
         //  is the one that refines, whether an earlier call had tripped the net already or not)
-        if(any_inaccurate && attempt == 0 && (!h->careful || !split_launch(h))) h->careful = true;
+        if(any_inaccurate && attempt == 0 && (!h->resident.careful || !split_launch(h))) h->resident.careful = true;
         else
         {
             // re-match on the failing instance's own assembled values (device order = front-assembly order -> CSR slots)
@@ -615,11 +604,11 @@ namespace pe_eng PE_ENG_HIDDEN
                 double const v = std::fabs(tmp[e]);
                 h->sym_values_override[h->sym.asm_slot[e]] = v <= 1.7976931348623157e308 ? v : 1.0;  // (a non-finite entry says nothing about magnitude)
             }
-            h->sym_class = -1;
+            h->resident.sym_class = -1;
             int const rc = ensure_symbolic(h, tr, dt);
             h->sym_values_override.clear();
             if(rc != PE_HIP_OK) return rc;
-            ++h->n_rematched;
+            ++h->resident.n_rematched;
         }
         for(int b: failed) status[b] = PE_HIP_OK;
         HIPCHK(h, hipMemcpy(h->V.status, status.data(), B * sizeof(int), hipMemcpyHostToDevice));
@@ -857,15 +846,15 @@ namespace pe_eng PE_ENG_HIDDEN
             if(rc != PE_HIP_OK) return rc;
             done = nsteps;
         }
-        if(done < nsteps) h->a_static.clear();  // (the resident kernel stamps the matrix itself: what the split schedule knew about it is void)
+        if(done < nsteps) h->resident.a_static.clear();  // (the resident kernel stamps the matrix itself: what the split schedule knew about it is void)
         bool const integ = h->tr_method != PE_HIP_TR_TRAP;
         while(done < nsteps)
         {
             double const key = integ_key(h, dt);
-            bool const reuse = may_reuse && h->fact_valid && h->fact_dt == key;
+            bool const reuse = may_reuse && h->resident.fact_valid && h->fact_dt == key;
             int n = reuse || !may_reuse ? std::min(chunk, nsteps - done) : 1;  // first step factors, the rest may reuse
             // (GEAR2: one launch reuses one factorisation -- a step whose a0 is not that of the steps behind it, the first after a restart, goes alone)
-            if(integ && reuse && !(h->integ_hp == dt)) n = 1;
+            if(integ && reuse && !(h->resident.integ_hp == dt)) n = 1;
             if(h->probe.armed)
             {
                 pe::ProbedView const pv = probe_view(h);
@@ -877,15 +866,15 @@ namespace pe_eng PE_ENG_HIDDEN
             done += n;
             if(may_reuse)
             {
-                h->fact_valid = true;
+                h->resident.fact_valid = true;
                 h->fact_dt = key;
             }
-            if(integ) h->integ_hp = dt;  // (put right below should an instance have failed)
+            if(integ) h->resident.integ_hp = dt;  // (put right below should an instance have failed)
         }
         rc = retry_inaccurate(h, true, dt, nsteps, s0,
                               [&](auto const& g)
                               {
-                                  if(integ) h->integ_hp = std::nan("");  // (instances stepped alone)
+                                  if(integ) h->resident.integ_hp = std::nan("");  // (instances stepped alone)
                                   return run_m2_tr(h, dt, g.first, launches, &g.second);
                               });
         if(rc != PE_HIP_OK) return rc;
@@ -897,7 +886,7 @@ namespace pe_eng PE_ENG_HIDDEN
             std::vector<int> status(static_cast<size_t>(h->hc.batch));
             HIPCHK(h, hipMemcpy(status.data(), h->V.status, status.size() * sizeof(int), hipMemcpyDeviceToHost));
             bool const all_ok = std::all_of(status.begin(), status.end(), [](int v) { return v == PE_HIP_OK; });
-            h->integ_hp = all_ok ? dt : std::nan("");
+            h->resident.integ_hp = all_ok ? dt : std::nan("");
             if(!all_ok) h->integ_failed = true;
         }
         return PE_HIP_OK;
@@ -909,9 +898,8 @@ namespace pe_eng PE_ENG_HIDDEN
         if(h->tr_method == PE_HIP_TR_TRAP || !h->integ_failed) return PE_HIP_OK;
         HIPCHK(h, pe::launch_integ_restart(h->stream, h->V, true));
         h->integ_failed = false;
-        h->integ_hp = std::nan("");
-        h->fact_valid = false;
-        h->a_static.clear();
+        h->resident.integ_hp = std::nan("");
+        invalidate_factors(h);
         return PE_HIP_OK;
     }
 
@@ -921,13 +909,12 @@ namespace pe_eng PE_ENG_HIDDEN
         if(!h->loaded) return PE_HIP_OK;
         // whatever was keyed on the other rule's companion conductances is void; captured launch sequences hold the old view; the snapshot
         // table of the variable-step transient is built again, with or without the history array
-        h->fact_valid = false;
-        h->a_static.clear();
-        h->sym_dt = 0.0;
-        pe::m2_graphs_clear(h->graphs);
+        invalidate_factors(h);
+        h->resident.sym_dt = 0.0;
+        pe::m2_graphs_clear(h->graphs.get());
         tr_adaptive_drop(h);
         h->integ_failed = false;
-        h->integ_hp = 0.0;
+        h->resident.integ_hp = 0.0;
         if(h->tr_method == PE_HIP_TR_TRAP)
         {
             h->integ_pool.release();
@@ -945,24 +932,23 @@ namespace pe_eng PE_ENG_HIDDEN
         (void)pe::launch_integ_restart(h->stream, h->V, false);
         (void)hipStreamSynchronize(h->stream);  // (the calls that restart go on with blocking copies)
         h->integ_failed = false;
-        h->integ_hp = 0.0;
+        h->resident.integ_hp = 0.0;
         if(h->tr_method != PE_HIP_TR_TRAP)
         {
-            h->fact_valid = false;  // (the a0 of the coming step is another)
-            h->a_static.clear();
+            invalidate_factors(h);  // (the a0 of the coming step is another)
         }
     }
 
     double integ_key(pe_hip_engine const* h, double dt)
     {
         if(h->tr_method == PE_HIP_TR_TRAP) return dt;
-        if(std::isnan(h->integ_hp)) return h->integ_hp;
-        return pe::integ_coef(h->tr_method, dt, h->integ_hp).a0;
+        if(std::isnan(h->resident.integ_hp)) return h->resident.integ_hp;
+        return pe::integ_coef(h->tr_method, dt, h->resident.integ_hp).a0;
     }
     double integ_sym_dt(pe_hip_engine const* h, double dt)
     {
         if(h->tr_method == PE_HIP_TR_TRAP) return dt;
-        return 2.0 / pe::integ_coef(h->tr_method, dt, std::isnan(h->integ_hp) ? 0.0 : h->integ_hp).a0;
+        return 2.0 / pe::integ_coef(h->tr_method, dt, std::isnan(h->resident.integ_hp) ? 0.0 : h->resident.integ_hp).a0;
     }
 }  // namespace pe_eng
 
@@ -972,8 +958,7 @@ namespace pe_eng PE_ENG_HIDDEN
     {
         auto& A = h->tra;
         if(A.allocated) (void)hipStreamSynchronize(h->stream);
-        A.pool.release();
-        A = pe_hip_engine::TrAdaptive{};
+        A = pe_hip_engine::TrAdaptive{};  // (its pool frees what it holds)
     }
 
     // shadow set of the state of a step (tr_state_parts = the arrays of a checkpoint, + the cursor of the Newton trace so that the trace
@@ -1077,7 +1062,7 @@ int pe_hip_analyze_tr(pe_hip_engine* h, double dt, int nsteps, pe_hip_run_stats*
     int launches = 0;
     rc = tr_run_steps(h, dt, nsteps, run.s0, launches);
     if(rc != PE_HIP_OK) return rc;
-    if(!may_reuse) h->fact_valid = false;
+    if(!may_reuse) h->resident.fact_valid = false;
     return solve_end(h, st, run, launches);
 }
 
@@ -1149,16 +1134,15 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     // (the controller's exponent: the trapezoidal rule and GEAR2 are of second order, err ~ h^3; BE of first, err ~ h^2)
     double const q_exp = method == PE_HIP_TR_BE ? -1.0 / 2.0 : -1.0 / 3.0;
-    double hp_snapshot = h->integ_hp;
+    double hp_snapshot = h->resident.integ_hp;
     bool failed_snapshot = h->integ_failed;
     auto const roll_back = [&]() -> int
     {
         // the state of the snapshot; the host side as pe_hip_checkpoint_load leaves it (what the step spent came with the LTE result)
         HIPCHK(h, pe::launch_tr_state_copy(h->stream, A.restore));
-        h->integ_hp = hp_snapshot;  // (the history array of BE / GEAR2 is part of the snapshot: the host's knowledge of its h_p goes back with it)
+        h->resident.integ_hp = hp_snapshot;  // (the history array of BE / GEAR2 is part of the snapshot: the host's knowledge of its h_p goes back with it)
         h->integ_failed = failed_snapshot;
-        h->fact_valid = false;
-        h->a_static.clear();
+        invalidate_factors(h);
         return PE_HIP_OK;
     };
     // (the loop in a function of its own: whichever way it ends, the statistics below are filled -- the log and t may have advanced)
@@ -1174,7 +1158,7 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
             rc = integ_before_steps(h);
             if(rc != PE_HIP_OK) return rc;
             HIPCHK(h, pe::launch_tr_state_copy(h->stream, A.save));
-            hp_snapshot = h->integ_hp;
+            hp_snapshot = h->resident.integ_hp;
             failed_snapshot = h->integ_failed;
             rc = ensure_symbolic(h, true, integ_sym_dt(h, hs));
             if(rc != PE_HIP_OK) return rc;
@@ -1184,7 +1168,7 @@ int pe_hip_analyze_tr_adaptive(pe_hip_engine* h, double t_stop, const pe_hip_tr_
             rc = tr_run_steps(h, hs, 1, s_now, launches);
             h->probe.armed = armed;
             if(rc != PE_HIP_OK) return rc;
-            if(!may_reuse) h->fact_valid = false;
+            if(!may_reuse) h->resident.fact_valid = false;
             // the test on the device, the decision from one small copy
             bool const test = lte_on && A.n_pts >= 3;
             double const t_new = t + hs;
@@ -1340,9 +1324,9 @@ int dc_point(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status
     SolveRun run;
     rc = solve_begin(h, run);
     if(rc != PE_HIP_OK) return rc;
-    if(!kept) h->fact_valid = false;
-    h->a_static.clear();  // (an OP / DC / TROP solve stamps other companion values into the matrix, on either schedule)
-    long long const rematched0 = h->n_rematched;
+    if(!kept) h->resident.fact_valid = false;
+    h->resident.a_static.clear();  // (an OP / DC / TROP solve stamps other companion values into the matrix, on either schedule)
+    long long const rematched0 = h->resident.n_rematched;
     int launches = 0;
     if(kept) rc = run_m2_dc(h, mode, launches, nullptr, false);  // (no factorisation: n_factor_launches does not count this attempt)
     else
@@ -1361,7 +1345,7 @@ int dc_point(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status
                           });
     if(rc != PE_HIP_OK) return rc;
     // a re-match gave the engine another pivot order: only the retried instances hold factors of it -- every instance factors again
-    if(kept && h->n_rematched != rematched0) return dc_point(h, mode, st, true, false);
+    if(kept && h->resident.n_rematched != rematched0) return dc_point(h, mode, st, true, false);
     return solve_end(h, st, run, 1);
 }
 }  // namespace
@@ -1371,7 +1355,7 @@ int dc_solve(pe_hip_engine* h, int mode, pe_hip_run_stats* st, bool clear_status
 int dc_solve_kept(pe_hip_engine* h, int mode, pe_hip_run_stats* st)
 {
     // an engine that keeps no L21, or whose factors are not those of a DC point of a linear circuit, factors: dc_solve
-    bool const keeps = !h->hc.nonlinear && h->V.keep_l21 && !has_overlay(h) && h->sym_class == 0;
+    bool const keeps = !h->hc.nonlinear && h->V.keep_l21 && !has_overlay(h) && h->resident.sym_class == 0;
     return dc_point(h, mode, st, true, keeps);
 }
 
@@ -1396,9 +1380,7 @@ namespace pe_eng
     {
         auto& O = h->ops;
         if(O.allocated) (void)hipStreamSynchronize(h->stream);
-        O.pool.release();
-        O.log_pool.release();
-        O = pe_hip_engine::OpStep{};
+        O = pe_hip_engine::OpStep{};  // (its pools free what they hold)
     }
 }  // namespace pe_eng
 
@@ -1514,13 +1496,9 @@ int pe_hip_analyze_op_stepping(pe_hip_engine* h, int mode, const pe_hip_op_step_
 
     pe_hip_op_step_stats T{};
     hipStream_t const st = h->stream;
-    hipEvent_t ev_a{}, ev_b{};  // (dc_solve records the engine's own pair)
-    HIPCHK(h, hipEventCreate(&ev_a));
-    if(hipError_t const e = hipEventCreate(&ev_b); e != hipSuccess)
-    {
-        (void)hipEventDestroy(ev_a);
-        HIPCHK(h, e);
-    }
+    pe_eng::Event ev_a, ev_b;  // (dc_solve records the engine's own pair)
+    HIPCHK(h, ev_a.create());
+    HIPCHK(h, ev_b.create());
     pe::OpStepRecord rec{};
     auto control = [&](int role) -> int
     {
@@ -1583,13 +1561,10 @@ int pe_hip_analyze_op_stepping(pe_hip_engine* h, int mode, const pe_hip_op_step_
         if(rc == PE_HIP_OK) rc = frc;
         else
             h->err = err;
-        h->fact_valid = false;
-        h->a_static.clear();
+        invalidate_factors(h);
     }
     float ms = 0.f;
     if(hipEventRecord(ev_b, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) (void)hipEventElapsedTime(&ms, ev_a, ev_b);
-    (void)hipEventDestroy(ev_a);
-    (void)hipEventDestroy(ev_b);
     T.gpu_ms = ms;
     if(rc != PE_HIP_OK)
     {
@@ -1679,9 +1654,7 @@ namespace pe_eng
 {
     void dc_sweep_drop(pe_hip_engine* h)
     {
-        auto& D = h->dcs;
-        if(D.eng) pe_hip_destroy(D.eng);  // (synchronises its stream first: nothing reads the buffers freed next any more)
-        D = pe_hip_engine::DcSweep{};     // (its pools and kept rows free what they hold)
+        h->dcs.drop();
     }
 }  // namespace pe_eng
 
@@ -1705,16 +1678,10 @@ namespace
     int dc_sweep_engine_build(pe_hip_engine* h, int P, int kind, int j, double first_value)
     {
         auto& D = h->dcs;
-        if(D.eng) pe_hip_destroy(D.eng);
-        D.eng = nullptr;
+        D.eng.reset();  // (synchronises its stream first: nothing reads the buffers freed next any more)
         D.P = 0;
         D.pass_pool.release();
-        if(pe_hip_create(h->device, &D.eng) != PE_HIP_OK) return fail(h, PE_HIP_ERR_NO_DEVICE, "analyze_dc_sweep: " + std::string(pe_hip_last_error(nullptr)));
-        pe_hip_engine* const E = D.eng;
-        E->knobs = h->knobs;
-        E->opt = h->opt;
-        E->hc = h->hc;
-        auto& c = E->hc;
+        pe::HostCircuit c = h->hc;
         int const B = h->hc.batch;
         repeat_instances(c.r_g, B, P);
         repeat_instances(c.c_cap, B, P);
@@ -1738,8 +1705,7 @@ namespace
             else
                 c.idc_i[static_cast<size_t>(j)] = first_value;
         }
-        int const rc = finish_load(E);
-        if(rc != PE_HIP_OK) return fail(h, rc, "analyze_dc_sweep: " + E->err);
+        if(int const rc = engine_build(h->device, D.eng, h, "analyze_dc_sweep", &h->opt, std::move(c)); rc != PE_HIP_OK) return rc;
         size_t const Q = static_cast<size_t>(B) * P;
         auto& S = D.V;
         HIPCHK(h, D.pass_pool.alloc(S.seed_of, Q));
@@ -1826,7 +1792,7 @@ int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values
     {
         // (the main engine's arrays per instance; its factor storage is part of them once it has been analysed)
         long long bpi = static_cast<long long>((h->circ_pool.bytes + h->sym_pool.bytes) / static_cast<size_t>(std::max(1, B)));
-        if(h->sym_class < 0) bpi = 4 * static_cast<long long>(h->circ_pool.bytes / static_cast<size_t>(std::max(1, B)));
+        if(h->resident.sym_class < 0) bpi = 4 * static_cast<long long>(h->circ_pool.bytes / static_cast<size_t>(std::max(1, B)));
         P = static_cast<int>(std::min<long long>(sweep_pass_cap(knob(h, "DC_SWEEP_POINTS", 0), std::max<long long>(1, bpi), B), n_points));
     }
     else if(2ll * B > SWEEP_MAX_INSTANCES)
@@ -1857,7 +1823,7 @@ int pe_hip_analyze_dc_sweep(pe_hip_engine* h, int n_points, const double* values
     // ---- the sweep engine (rebuilt when P or anything it was built from has changed), its one symbolic analysis
     if(!D.eng || D.P != P || D.epoch != h->param_epoch)
         if(int const rc = dc_sweep_engine_build(h, P, c->kind, j, values[order[0]]); rc != PE_HIP_OK) return rc;
-    pe_hip_engine* const E = D.eng;
+    pe_hip_engine* const E = D.eng.get();
     hipStream_t const es = E->stream;
     long long const analyses0 = E->n_symbolic;
     if(int const rc = ensure_symbolic(E, false, 0.0); rc != PE_HIP_OK) return fail(h, rc, "analyze_dc_sweep (symbolic analysis): " + E->err);

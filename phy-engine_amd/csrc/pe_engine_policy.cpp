@@ -18,7 +18,7 @@ namespace pe_eng PE_ENG_HIDDEN
         if(v == 1) return true;
         if(v == 0) return false;
         if(h->overlay_fn && (h->hc.n_ov_a || h->hc.n_ov_b)) return true;  // host-stamped models: the host drives the Newton loop
-        if(h->careful) return true;  // an inaccurate solve was detected: the host-driven loop refines / re-matches
+        if(h->resident.careful) return true;  // an inaccurate solve was detected: the host-driven loop refines / re-matches
         return h->V.n_parts > 1 || h->hc.rows >= 3000;
     }
 
@@ -448,9 +448,9 @@ namespace pe_eng PE_ENG_HIDDEN
         int const cls = tr ? 1 : 0;
         // the static pivot order was matched on representative values at ONE dt (capacitor / inductor companions scale with 1/dt):
         // a time step more than a decade away from it gets a fresh analysis, like a change of class
-        bool const dt_moved = tr && h->sym_dt > 0.0 && dt > 0.0 && (dt > 10.0 * h->sym_dt || dt < 0.1 * h->sym_dt) && h->sym_values_override.empty();
-        if(h->sym_class == cls && !dt_moved) return PE_HIP_OK;
-        if(tr) h->sym_dt = dt;
+        bool const dt_moved = tr && h->resident.sym_dt > 0.0 && dt > 0.0 && (dt > 10.0 * h->resident.sym_dt || dt < 0.1 * h->resident.sym_dt) && h->sym_values_override.empty();
+        if(h->resident.sym_class == cls && !dt_moved) return PE_HIP_OK;
+        if(tr) h->resident.sym_dt = dt;
         auto const t0 = clk::now();
         std::vector<double> av;
         if(!h->sym_values_override.empty()) av = h->sym_values_override;
@@ -481,7 +481,7 @@ namespace pe_eng PE_ENG_HIDDEN
                                            h->hc.nonlinear ? &dyn_slots : nullptr, h->hc.nonlinear ? &dyn_rows : nullptr);
             if(rc != PE_HIP_OK)
             {
-                h->sym_class = -1;
+                h->resident.sym_class = -1;
                 return rc;
             }
         }
@@ -540,12 +540,12 @@ namespace pe_eng PE_ENG_HIDDEN
                 std::fprintf(stderr, "\n");
             }
         }
-        pe::m2_graphs_clear(h->graphs);  // (captured sequences hold the old view: its tables are about to be freed)
+        pe::m2_graphs_clear(h->graphs.get());  // (captured sequences hold the old view: its tables are about to be freed)
         h->sym_pool.release();
-        h->static_skip = pe::StaticSkip{};
+        h->resident.static_skip = pe::StaticSkip{};
         int const rc = upload_symbolic(h, h->sym_pool, h->sym, so, h->V, h->hc.batch);
         if(rc != PE_HIP_OK) return rc;
-        h->active_dev.clear();  // (the quad list behind the mask depends on this analysis' strides)
+        h->resident.active_dev.clear();  // (the quad list behind the mask depends on this analysis' strides)
         if(char const* dump = std::getenv("PHY_ENGINE_HIP_DUMP_SCHEDULE"); dump && *dump == '1')
         {
             auto const& S = h->sym;
@@ -624,10 +624,10 @@ namespace pe_eng PE_ENG_HIDDEN
                 // across the later iterations of a point, and that vector (arena_doubles has grown by S.static_root_doubles for their roots)
                 if(S.quad && S.n_static_quad > 0)
                 {
-                    HIPCHK(h, h->sym_pool.upload(h->static_skip.q_prog_dyn, S.q_prog_dyn));
-                    HIPCHK(h, h->sym_pool.upload(h->static_skip.q_lists_dyn, S.q_lists_dyn));
-                    HIPCHK(h, h->sym_pool.upload(h->static_skip.row_keep, S.row_keep));
-                    HIPCHK(h, h->sym_pool.alloc(h->static_skip.wy, static_cast<size_t>(hc.rows) * hc.batch));
+                    HIPCHK(h, h->sym_pool.upload(h->resident.static_skip.q_prog_dyn, S.q_prog_dyn));
+                    HIPCHK(h, h->sym_pool.upload(h->resident.static_skip.q_lists_dyn, S.q_lists_dyn));
+                    HIPCHK(h, h->sym_pool.upload(h->resident.static_skip.row_keep, S.row_keep));
+                    HIPCHK(h, h->sym_pool.alloc(h->resident.static_skip.wy, static_cast<size_t>(hc.rows) * hc.batch));
                 }
             }
             h->V.asm_slot = nullptr;  // identity (pe_front.hpp front_factor); the solve_csr_real seam keeps CSR order + the map
@@ -635,9 +635,8 @@ namespace pe_eng PE_ENG_HIDDEN
             for(size_t e = 0; e < nnz; ++e) slot_e[S.asm_slot[e]] = static_cast<int>(e);
             HIPCHK(h, h->sym_pool.upload(h->V.slot_e, slot_e));
         }
-        h->sym_class = cls;
-        h->fact_valid = false;
-        h->a_static.clear();
+        h->resident.sym_class = cls;
+        invalidate_factors(h);
         h->analyze_ms = ms_since(t0);
         ++h->n_symbolic;
         return PE_HIP_OK;

@@ -1392,7 +1392,7 @@ namespace pe
     // hipGraphLaunch; what changes from iteration to iteration -- t, last_step, the companion's dt (arguments of k_m2_eval) and the sequence number
     // of k_m2_publish -- is patched into those two nodes (hipGraphExecKernelNodeSetParams).  The instances that still iterate are device data
     // (V.active, the quad list): the captured grids are those of the full sweep, finished instances return at once.
-    struct M2GraphEntry
+    struct M2GraphEntry  // (owns graph and exec: move-only, so that every early return of the capture block releases what it holds)
     {
         hipGraph_t graph{};
         hipGraphExec_t exec{};
@@ -1403,20 +1403,19 @@ namespace pe
         int* pub_flags{};
         double* pub_eta{};
         unsigned long long* pub_seq{};
+        M2GraphEntry() = default;
+        M2GraphEntry(M2GraphEntry&& o) noexcept { std::memcpy(static_cast<void*>(this), &o, sizeof o), o.graph = nullptr, o.exec = nullptr; }  // (bytes: V is a memcmp key)
+        M2GraphEntry& operator=(M2GraphEntry&&) = delete;
+        ~M2GraphEntry()
+        {
+            if(exec) (void)hipGraphExecDestroy(exec);
+            if(graph) (void)hipGraphDestroy(graph);
+        }
     };
     struct M2GraphCache
     {
         std::vector<M2GraphEntry> entries;
-        ~M2GraphCache() { clear(); }
-        void clear()
-        {
-            for(auto& e: entries)
-            {
-                if(e.exec) (void)hipGraphExecDestroy(e.exec);
-                if(e.graph) (void)hipGraphDestroy(e.graph);
-            }
-            entries.clear();
-        }
+        void clear() { entries.clear(); }
     };
     M2GraphCache* m2_graphs_create() { return new M2GraphCache; }
     void m2_graphs_destroy(M2GraphCache* c) { delete c; }
@@ -1478,16 +1477,12 @@ namespace pe
             rc = V.high_occupancy ? m2_sequence<4>(st, V, mode, t, last_step, do_factor, nullptr, nullptr, false, stamp_mode, companion, companion_dt, sk)
                                   : m2_sequence<2>(st, V, mode, t, last_step, do_factor, nullptr, nullptr, false, stamp_mode, companion, companion_dt, sk);
             hipError_t const rp = launch_m2_publish(st, V, pub_flags, pub_eta, pub_seq, seq);
-            hipError_t const re = hipStreamEndCapture(st, &e.graph);
+            hipError_t const re = hipStreamEndCapture(st, &e.graph);  // (always, once capture has begun; e owns the graph before any status is looked at)
             if(rc != hipSuccess) return rc;
             if(rp != hipSuccess) return rp;
             if(re != hipSuccess) return re;
             rc = hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0);
-            if(rc != hipSuccess)
-            {
-                (void)hipGraphDestroy(e.graph);
-                return rc;
-            }
+            if(rc != hipSuccess) return rc;
             size_t n = 0;
             rc = hipGraphGetNodes(e.graph, nullptr, &n);
             if(rc != hipSuccess) return rc;
@@ -1504,13 +1499,8 @@ namespace pe
                 else if(kp.func == reinterpret_cast<void*>(&k_m2_publish))
                     e.publish_node = nd;
             }
-            if(!e.eval_node || !e.publish_node)
-            {
-                (void)hipGraphExecDestroy(e.exec);
-                (void)hipGraphDestroy(e.graph);
-                return hipErrorInvalidValue;
-            }
-            cache->entries.push_back(e);
+            if(!e.eval_node || !e.publish_node) return hipErrorInvalidValue;
+            cache->entries.push_back(std::move(e));
             hit = &cache->entries.back();
         }
         // this iteration's scalars into the two nodes that take them

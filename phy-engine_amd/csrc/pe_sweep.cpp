@@ -14,12 +14,13 @@
 #include <vector>
 
 #include "../../include/pe_hip.h"
-#include "pe_circuit.hpp"  // gen_ncol: parameter columns of the generic device kinds
+#include "pe_circuit.hpp"          // gen_ncol: parameter columns of the generic device kinds
+#include "pe_engine_internal.hpp"  // EnginePtr, engine_build: nothing else of the engine object is used here
 
 struct pe_hip_sweep
 {
     std::vector<int> device;
-    std::vector<pe_hip_engine*> eng;
+    std::vector<pe_eng::EnginePtr> eng;
     std::vector<int> lo, hi;  // instances [lo, hi) of the whole sweep on engine g
     int batch{}, rows{};
     bool loaded{};
@@ -53,7 +54,7 @@ namespace
         for(size_t g = 0; g < G; ++g)
             if(rc[g] != PE_HIP_OK)
             {
-                s->err = "device " + std::to_string(s->device[g]) + ": " + pe_hip_last_error(s->eng[g]);
+                s->err = "device " + std::to_string(s->device[g]) + ": " + pe_hip_last_error(s->eng[g].get());
                 return rc[g];
             }
         return PE_HIP_OK;
@@ -79,18 +80,16 @@ int pe_hip_sweep_create(unsigned device_mask, pe_hip_sweep** out)
             if(d >= n)
             {
                 g_sweep_create_error = "device mask names device " + std::to_string(d) + ", " + std::to_string(n) + " visible";
-                for(auto* e: s->eng) pe_hip_destroy(e);
                 return PE_HIP_ERR_ARG;
             }
-            pe_hip_engine* e = nullptr;
-            if(int const rc = pe_hip_create(d, &e); rc != PE_HIP_OK)
+            pe_eng::EnginePtr e;
+            if(int const rc = pe_eng::engine_build(d, e); rc != PE_HIP_OK)
             {
                 g_sweep_create_error = pe_hip_last_error(nullptr);
-                for(auto* q: s->eng) pe_hip_destroy(q);
                 return rc;
             }
             s->device.push_back(d);
-            s->eng.push_back(e);
+            s->eng.push_back(std::move(e));
         }
     if(s->eng.empty())
     {
@@ -105,9 +104,7 @@ int pe_hip_sweep_create(unsigned device_mask, pe_hip_sweep** out)
 
 void pe_hip_sweep_destroy(pe_hip_sweep* s)
 {
-    if(!s) return;
-    for(auto* e: s->eng) pe_hip_destroy(e);
-    delete s;
+    delete s;  // (its engines go with it)
 }
 
 const char* pe_hip_sweep_last_error(pe_hip_sweep* s) { return s ? s->err.c_str() : g_sweep_create_error.c_str(); }
@@ -127,9 +124,9 @@ int pe_hip_sweep_set_options(pe_hip_sweep* s, const pe_hip_options* opt)
 {
     if(!s || !opt) return PE_HIP_ERR_ARG;
     for(size_t g = 0; g < s->eng.size(); ++g)
-        if(int const rc = pe_hip_set_options(s->eng[g], opt); rc != PE_HIP_OK)
+        if(int const rc = pe_hip_set_options(s->eng[g].get(), opt); rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     return PE_HIP_OK;
@@ -145,9 +142,9 @@ int pe_hip_sweep_set_tr_method(pe_hip_sweep* s, int method)
         return PE_HIP_ERR_ARG;
     }
     for(size_t g = 0; g < s->eng.size(); ++g)
-        if(int const rc = pe_hip_set_tr_method(s->eng[g], method); rc != PE_HIP_OK)
+        if(int const rc = pe_hip_set_tr_method(s->eng[g].get(), method); rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     return PE_HIP_OK;
@@ -175,7 +172,7 @@ int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int 
                                        std::vector<pe_hip_device_table> t(tables, tables + n_tables);
                                        for(auto& q: t)
                                            if(q.params_batched && q.params) q.params += static_cast<size_t>(s->lo[g]) * q.count * param_columns(q.kind);
-                                       return pe_hip_load_circuit(s->eng[g], n_nodes, n_branches, s->hi[g] - s->lo[g], n_tables, t.data());
+                                       return pe_hip_load_circuit(s->eng[g].get(), n_nodes, n_branches, s->hi[g] - s->lo[g], n_tables, t.data());
                                    });
     s->loaded = rc == PE_HIP_OK;
     return rc;
@@ -184,7 +181,7 @@ int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int 
 int pe_hip_sweep_reset(pe_hip_sweep* s)
 {
     if(!s || !s->loaded) return PE_HIP_ERR_ARG;
-    return for_each_engine(s, [&](int g) { return pe_hip_reset(s->eng[g]); });
+    return for_each_engine(s, [&](int g) { return pe_hip_reset(s->eng[g].get()); });
 }
 
 // `nsteps` transient steps of every instance; stats (may be NULL): sums over the devices, times = the slowest device
@@ -192,7 +189,7 @@ int pe_hip_sweep_run(pe_hip_sweep* s, double dt, int nsteps, pe_hip_run_stats* s
 {
     if(!s || !s->loaded) return PE_HIP_ERR_ARG;
     std::vector<pe_hip_run_stats> st(s->eng.size());
-    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_tr(s->eng[g], dt, nsteps, &st[g]); });
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_tr(s->eng[g].get(), dt, nsteps, &st[g]); });
     if(stats)
     {
         *stats = pe_hip_run_stats{};
@@ -215,7 +212,7 @@ int pe_hip_sweep_operating_point(pe_hip_sweep* s, int mode, pe_hip_run_stats* st
 {
     if(!s || !s->loaded) return PE_HIP_ERR_ARG;
     std::vector<pe_hip_run_stats> st(s->eng.size());
-    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_dc(s->eng[g], mode, &st[g]); });
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_dc(s->eng[g].get(), mode, &st[g]); });
     if(stats)
     {
         *stats = pe_hip_run_stats{};
@@ -237,7 +234,7 @@ int pe_hip_sweep_operating_point_stepping(pe_hip_sweep* s, int mode, const pe_hi
 {
     if(!s || !s->loaded) return PE_HIP_ERR_ARG;
     std::vector<pe_hip_op_step_stats> st(s->eng.size());
-    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_op_stepping(s->eng[g], mode, c, &st[g]); });
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_analyze_op_stepping(s->eng[g].get(), mode, c, &st[g]); });
     if(stats)
     {
         *stats = pe_hip_op_step_stats{};
@@ -268,7 +265,7 @@ int pe_hip_sweep_reduce(pe_hip_sweep* s, double* out)
     if(!s || !s->loaded || !out) return PE_HIP_ERR_ARG;
     size_t const R = static_cast<size_t>(s->rows);
     std::vector<std::vector<double>> part(s->eng.size(), std::vector<double>(4 * R));
-    if(int const rc = for_each_engine(s, [&](int g) { return pe_hip_sweep_statistics(s->eng[g], part[g].data()); }); rc != PE_HIP_OK) return rc;
+    if(int const rc = for_each_engine(s, [&](int g) { return pe_hip_sweep_statistics(s->eng[g].get(), part[g].data()); }); rc != PE_HIP_OK) return rc;
     bool first = true;
     for(size_t g = 0; g < s->eng.size(); ++g)
     {
@@ -295,9 +292,9 @@ int pe_hip_sweep_get_solution(pe_hip_sweep* s, int first_instance, int count, do
     {
         int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
         if(b <= a) continue;
-        if(int const rc = pe_hip_get_solution(s->eng[g], a - s->lo[g], b - a, x + static_cast<size_t>(a - first_instance) * s->rows); rc != PE_HIP_OK)
+        if(int const rc = pe_hip_get_solution(s->eng[g].get(), a - s->lo[g], b - a, x + static_cast<size_t>(a - first_instance) * s->rows); rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     }
@@ -312,11 +309,11 @@ int pe_hip_sweep_get_instance_state(pe_hip_sweep* s, int first_instance, int cou
         int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
         if(b <= a) continue;
         int const o = a - first_instance;
-        if(int const rc = pe_hip_get_instance_state(s->eng[g], a - s->lo[g], b - a, status ? status + o : nullptr, steps ? steps + o : nullptr, iters ? iters + o : nullptr,
+        if(int const rc = pe_hip_get_instance_state(s->eng[g].get(), a - s->lo[g], b - a, status ? status + o : nullptr, steps ? steps + o : nullptr, iters ? iters + o : nullptr,
                                                     t ? t + o : nullptr);
            rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     }
@@ -336,7 +333,7 @@ int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int 
         s->err = "set_probes: batch x capacity x (n_probes + 1) overflows";
         return PE_HIP_ERR_ARG;
     }
-    int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_probes(s->eng[g], n_probes, rows, capacity, stride, n_measures, m); });
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_probes(s->eng[g].get(), n_probes, rows, capacity, stride, n_measures, m); });
     if(rc == PE_HIP_OK) s->four_np = s->four_h = 0;  // (a probe configuration drops the Fourier one)
     if(rc != PE_HIP_OK)
     {
@@ -344,7 +341,7 @@ int pe_hip_sweep_set_probes(pe_hip_sweep* s, int n_probes, const int* rows, int 
         if(rc != PE_HIP_ERR_ARG)
         {
             for(size_t g = 0; g < s->eng.size(); ++g)
-                if(s->hi[g] > s->lo[g]) (void)pe_hip_set_probes(s->eng[g], 0, nullptr, 0, 0, 0, nullptr);
+                if(s->hi[g] > s->lo[g]) (void)pe_hip_set_probes(s->eng[g].get(), 0, nullptr, 0, 0, 0, nullptr);
             s->probes = false;
             s->four_np = s->four_h = 0;
         }
@@ -364,7 +361,7 @@ int pe_hip_sweep_arm_probes(pe_hip_sweep* s)
         if(s) s->err = "arm_probes: no probe configuration";
         return PE_HIP_ERR_ARG;
     }
-    return for_each_engine(s, [&](int g) { return pe_hip_arm_probes(s->eng[g]); });
+    return for_each_engine(s, [&](int g) { return pe_hip_arm_probes(s->eng[g].get()); });
 }
 
 int pe_hip_sweep_get_probe_samples(pe_hip_sweep* s, int first_instance, int count, double* t, double* v, int* n_recorded, long long* n_dropped)
@@ -376,11 +373,11 @@ int pe_hip_sweep_get_probe_samples(pe_hip_sweep* s, int first_instance, int coun
         int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
         if(b <= a) continue;
         size_t const o = static_cast<size_t>(a - first_instance);
-        if(int const rc = pe_hip_get_probe_samples(s->eng[g], a - s->lo[g], b - a, t ? t + o * cap : nullptr, v ? v + o * cap * np : nullptr,
+        if(int const rc = pe_hip_get_probe_samples(s->eng[g].get(), a - s->lo[g], b - a, t ? t + o * cap : nullptr, v ? v + o * cap * np : nullptr,
                                                    n_recorded ? n_recorded + o : nullptr, n_dropped ? n_dropped + o : nullptr);
            rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     }
@@ -395,9 +392,9 @@ int pe_hip_sweep_get_measures(pe_hip_sweep* s, int first_instance, int count, do
     {
         int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
         if(b <= a) continue;
-        if(int const rc = pe_hip_get_measures(s->eng[g], a - s->lo[g], b - a, out ? out + static_cast<size_t>(a - first_instance) * M * 2 : nullptr); rc != PE_HIP_OK)
+        if(int const rc = pe_hip_get_measures(s->eng[g].get(), a - s->lo[g], b - a, out ? out + static_cast<size_t>(a - first_instance) * M * 2 : nullptr); rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     }
@@ -412,14 +409,14 @@ int pe_hip_sweep_set_fourier(pe_hip_sweep* s, const pe_hip_fourier_control* c)
         if(s) s->err = "set_fourier: no probe configuration";
         return PE_HIP_ERR_ARG;
     }
-    int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_fourier(s->eng[g], c); });
+    int const rc = for_each_engine(s, [&](int g) { return pe_hip_set_fourier(s->eng[g].get(), c); });
     if(rc != PE_HIP_OK)
     {
         // an argument error is refused by every engine alike (nothing changed); anything else leaves the engines unequal: drop it on all
         if(rc != PE_HIP_ERR_ARG)
         {
             for(size_t g = 0; g < s->eng.size(); ++g)
-                if(s->hi[g] > s->lo[g]) (void)pe_hip_set_fourier(s->eng[g], nullptr);
+                if(s->hi[g] > s->lo[g]) (void)pe_hip_set_fourier(s->eng[g].get(), nullptr);
             s->four_np = s->four_h = 0;
         }
         return rc;
@@ -439,10 +436,10 @@ int pe_hip_sweep_get_fourier(pe_hip_sweep* s, int first_instance, int count, dou
         int const a = std::max(first_instance, s->lo[g]), b = std::min(first_instance + count, s->hi[g]);
         if(b <= a) continue;
         size_t const o = static_cast<size_t>(a - first_instance);
-        if(int const rc = pe_hip_get_fourier(s->eng[g], a - s->lo[g], b - a, coef ? coef + o * np * K4 : nullptr, thd ? thd + o * np : nullptr, covered ? covered + o : nullptr);
+        if(int const rc = pe_hip_get_fourier(s->eng[g].get(), a - s->lo[g], b - a, coef ? coef + o * np * K4 : nullptr, thd ? thd + o * np : nullptr, covered ? covered + o : nullptr);
            rc != PE_HIP_OK)
         {
-            s->err = pe_hip_last_error(s->eng[g]);
+            s->err = pe_hip_last_error(s->eng[g].get());
             return rc;
         }
     }

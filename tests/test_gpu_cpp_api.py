@@ -22,7 +22,7 @@ import pytest
 from parity_common import ROOT, make
 
 CPP = os.path.join(ROOT, "tests", "cpp")
-TESTS = ["known_answers", "user_model_overlay", "overlay_batch", "bridge_tr", "dll_smoke", "linear_models", "dll_elements", "transistors", "dll_mixed_signal", "ac_lowpass", "dll_digital_blocks", "hip_sparse_lu_seam"]  # adc_flash: checked against the golden below
+TESTS = ["known_answers", "user_model_overlay", "overlay_batch", "bridge_tr", "dll_smoke", "linear_models", "dll_elements", "transistors", "dll_mixed_signal", "ac_lowpass", "dll_digital_blocks", "hip_sparse_lu_seam", "engine_lifecycle"]  # adc_flash: checked against the golden below
 
 
 @pytest.fixture(scope="module")
