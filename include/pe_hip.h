@@ -166,7 +166,11 @@ void pe_hip_destroy(pe_hip_engine* h);
 const char* pe_hip_last_error(pe_hip_engine* h); /* valid until the next call on h; h may be NULL (creation errors) */
 
 /* ---- drop-in for cuda_sparse_lu::solve_csr_real (cuda_sparse_lu.h:465-473): A x = b, CSR, sorted columns.
- * copy_pattern != 0: (re)analyse the pattern; == 0: reuse the cached analysis (same n/nnz/pattern). */
+ * copy_pattern != 0: (re)analyse the pattern; == 0: reuse the cached analysis (same n/nnz/pattern).  Every solve is followed by a
+ * residual check on the device (componentwise backward error, as in the complex twin below): a healthy solution is returned as the
+ * kernels left it; one above 1e-10 is refined, and a cached pivot order that fails on the values of this call (bad pivot, or still
+ * inaccurate) is re-made on them once.  Returns PE_HIP_ERR_SINGULAR / PE_HIP_ERR_INACCURATE where the reference's solver returns false:
+ * never PE_HIP_OK with a solution that failed the check. */
 int pe_hip_solve_csr_real(pe_hip_engine* h, int n, int nnz, const int* row_ptr, const int* col_ind, const double* values,
                           const double* b, double* x, int copy_pattern, pe_hip_timings* out);
 

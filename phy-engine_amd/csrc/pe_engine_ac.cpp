@@ -34,6 +34,7 @@ namespace
         }
         // (the real-equivalent system is analysed under the same tuning knobs)
         if(int const rc = engine_build(h->device, A.eng, h, "analyze_ac", &h->opt, A.circ.hc); rc != PE_HIP_OK) return rc;
+        A.eng->greedy_match = true;  // (every analysis of this engine: pe_engine_internal.hpp)
         A.built = true;
         A.sym_omega = -1.0;
         return PE_HIP_OK;
@@ -61,6 +62,7 @@ namespace
         pe::HostCircuit c = A.circ.hc;
         c.batch = h->hc.batch * P;
         if(int const rc = engine_build(h->device, W.eng, h, name, &opt, std::move(c)); rc != PE_HIP_OK) return rc;
+        W.eng->greedy_match = true;  // (as A.eng)
         size_t const Q = static_cast<size_t>(h->hc.batch) * P, R2 = static_cast<size_t>(A.circ.hc.rows);
         double* omega{};
         int* point{};

@@ -508,6 +508,15 @@ struct pe_hip_engine
     } ops;
     long long param_epoch{};  // bumped by whatever changes hc's parameters, the options or the knobs (the DC sweep engine is rebuilt after it)
     std::vector<double> sym_values_override;  // representative |A| values for the row matching (AC engine)
+    // The engine holds the real-equivalent form of a circuit's complex AC system (the AC engine and its sweep engine; set once, where they
+    // are built): every analysis of it keeps the greedy row matching (pe_symbolic.cpp).  Rows i and n + i of such a system carry the two
+    // halves of the same complex entries, equal in magnitude; a matching that maximises magnitudes row by row is free to take the halves of
+    // a complex pivot from two different entries, and on ac_linear_mix it ends on blocks that cancel exactly (a zero pivot).  The greedy one
+    // is what the AC goldens were recorded with; these paths refine every solve and re-analyse on failure.
+    bool greedy_match{};
+    // Set around the analysis of the complex solver seam (pe_engine_seam.cpp), whose real-equivalent layout is known: the complex matrix is
+    // matched on the moduli of its entries and every pivot is a 2 x 2 block (pe_symbolic.cpp match_paired).
+    bool pair_match{};
 
     // solve_csr_real seam (separate small state)
     struct Csr
@@ -517,6 +526,8 @@ struct pe_hip_engine
         pe::DevView V{};
         int n{-1}, nnz{-1};
         bool have{};
+        bool on_these_values{};                 // the pivot order of the cached analysis was matched on the values of the current call
+        double *d_xacc{}, *d_b0{}, *d_worst{};  // residual check: the (refined) solution, the right-hand side, the backward error (owned by pool)
     } csr;
     // ... and its complex twin (pe_engine_seam.cpp): the real-equivalent 2n system, its refinement buffers
     struct Csrz
@@ -596,6 +607,10 @@ namespace pe_eng PE_ENG_HIDDEN
     int analyze_fitting(pe_hip_engine* h, int batch, int geometry_rows, int n, int const* rp, int const* ci, double const* vals, pe::Symbolic& S,
                         pe::SymbolicOptions& so, std::vector<char> const* dyn_slots = nullptr, std::vector<char> const* dyn_rows = nullptr);
     int ensure_symbolic(pe_hip_engine* h, bool tr, double dt);
+    // the solve + residual check + refinement both solver seams share (pe_engine_seam.cpp)
+    bool all_finite(double const* x, size_t n);
+    int seam_solve_refined(pe_hip_engine* h, pe::DevView const& V, double* xacc, double* b0, double* d_worst, double refine_above, pe_hip_timings& tm,
+                           float& gpu_ms, int& status, double& worst);
     // pe_engine.cpp: transient probes
     pe::ProbedView probe_view(pe_hip_engine const* h);  // the engine's view + its armed window (probe_armed set)
     void probe_disarm(pe_hip_engine* h);             // whatever moves x or t other than pe_hip_analyze_tr ends the window (samples stay)

@@ -252,6 +252,8 @@ namespace pe_eng PE_ENG_HIDDEN
     {
         int const batch = geometry_batch(h, batch_in);
         pe::SymbolicOptions so{};
+        so.match_greedy = h->greedy_match;
+        so.match_pairs = h->pair_match;
         // Workgroup geometry by batch size (measured on MI355X, profiles/ and scripts/sweep_split_*.sh).
         // Large circuits run the split schedule (one launch per phase): from ~100 instances on, 256-thread workgroups at four per
         // CU with every instance cut into 4 (8, 16) parts -- >= 1024 workgroups for the low-register kernels; fewer instances keep one

@@ -49,6 +49,55 @@ namespace
     }
 }  // namespace
 
+namespace pe_eng
+{
+    bool all_finite(double const* x, size_t n)
+    {
+        for(size_t i = 0; i < n; ++i)
+            if(!std::isfinite(x[i])) return false;
+        return true;
+    }
+
+    // Both solver seams (batch 1, V.aval in CSR order, V.csr_rp / V.csr_ci set, values and right-hand side uploaded): factor + solve, the
+    // solution into xacc, then residual rounds on the device -- `worst` = componentwise backward error of xacc; while it is above
+    // `refine_above`, at most three correction solves.  status != 0: the device status word of a bad pivot (worst is then meaningless).
+    int seam_solve_refined(pe_hip_engine* h, pe::DevView const& V, double* xacc, double* b0, double* d_worst, double refine_above, pe_hip_timings& tm,
+                           float& gpu_ms, int& status, double& worst)
+    {
+        auto const t0 = clk::now();
+        auto factor_solve = [&]() -> int
+        {
+            HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+            HIPCHK(h, pe::launch_factor_solve(h->stream, V, true));
+            HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+            HIPCHK(h, hipMemcpyAsync(&status, V.status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            gpu_ms += ms;
+            return PE_HIP_OK;
+        };
+        worst = 0.0;
+        if(int const rc = factor_solve(); rc != PE_HIP_OK) return rc;
+        if(status == 0)
+        {
+            HIPCHK(h, pe::launch_ac_accumulate(h->stream, V, xacc, b0, true));
+            for(int round = 0;; ++round)
+            {
+                HIPCHK(h, pe::launch_csr_residual(h->stream, V, xacc, b0, d_worst));
+                HIPCHK(h, hipMemcpyAsync(&worst, d_worst, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                if(!(worst > refine_above) || round == 3) break;
+                if(int const rc = factor_solve(); rc != PE_HIP_OK) return rc;
+                if(status != 0) break;
+                HIPCHK(h, pe::launch_ac_accumulate(h->stream, V, xacc, b0, false));
+            }
+        }
+        tm.solve_host_ms += ms_since(t0);
+        return PE_HIP_OK;
+    }
+}  // namespace pe_eng
+
 extern "C" {
 
 int pe_hip_solve_csr_complex(pe_hip_engine* h, int n, int nnz, const int* row_ptr, const int* col_ind, const double* values_re_im, const double* b_re_im,
@@ -94,7 +143,10 @@ int pe_hip_solve_csr_complex(pe_hip_engine* h, int n, int nnz, const int* row_pt
         C.have = false;
         C.pool.release();
         pe::SymbolicOptions so{};
-        if(int const rc = analyze_fitting(h, 1, 0, n2, C.rp2.data(), C.ci2.data(), C.vals.data(), C.sym, so); rc != PE_HIP_OK) return rc;
+        h->pair_match = true;  // (rows i and n + i are the halves of complex row i: pe_symbolic.cpp match_paired)
+        int const arc = analyze_fitting(h, 1, 0, n2, C.rp2.data(), C.ci2.data(), C.vals.data(), C.sym, so);
+        h->pair_match = false;
+        if(arc != PE_HIP_OK) return arc;
         pe::DevView V{};
         V.rows = n2;
         V.n_nodes = n2;
@@ -127,46 +179,15 @@ int pe_hip_solve_csr_complex(pe_hip_engine* h, int n, int nnz, const int* row_pt
     else
         C.on_these_values = false;
     float gpu_ms = 0.f;
-    // one factor + solve of the current V.rhs; returns the device status word (0 ok) in `status`
-    auto factor_solve = [&](int& status) -> int
-    {
-        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-        HIPCHK(h, pe::launch_factor_solve(h->stream, C.V, true));
-        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&status, C.V.status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        gpu_ms += ms;
-        return PE_HIP_OK;
-    };
     // solve + refine on the device: x in C.d_xacc, `worst` = componentwise backward error reached; status != 0: bad pivot
     auto solve_refined = [&](int& status, double& worst) -> int
     {
-        auto t0 = clk::now();
+        auto const t0 = clk::now();
         HIPCHK(h, hipMemcpyAsync(C.V.aval, C.vals.data(), static_cast<size_t>(nnz2) * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(C.V.rhs, C.rhs.data(), static_cast<size_t>(n2) * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         tm.h2d_ms += ms_since(t0);
-        t0 = clk::now();
-        worst = 0.0;
-        if(int const rc = factor_solve(status); rc != PE_HIP_OK) return rc;
-        if(status == 0)
-        {
-            HIPCHK(h, pe::launch_ac_accumulate(h->stream, C.V, C.d_xacc, C.d_b0, true));
-            for(int round = 0;; ++round)
-            {
-                HIPCHK(h, pe::launch_csr_residual(h->stream, C.V, C.d_xacc, C.d_b0, C.d_worst));
-                HIPCHK(h, hipMemcpyAsync(&worst, C.d_worst, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                if(!(worst > 4.0e-16) || round == 3) break;  // (NaN: falls through to the rounds, ends above tolerance)
-                if(int const rc = factor_solve(status); rc != PE_HIP_OK) return rc;
-                if(status != 0) break;
-                HIPCHK(h, pe::launch_ac_accumulate(h->stream, C.V, C.d_xacc, C.d_b0, false));
-            }
-        }
-        tm.solve_host_ms += ms_since(t0);
-        return PE_HIP_OK;
+        return seam_solve_refined(h, C.V, C.d_xacc, C.d_b0, C.d_worst, 4.0e-16, tm, gpu_ms, status, worst);
     };
     constexpr double accept = 1.0e-10;  // componentwise backward error a returned solution may carry (healthy solves end at ~1e-16)
     int status = 0;
@@ -184,6 +205,8 @@ int pe_hip_solve_csr_complex(pe_hip_engine* h, int n, int nnz, const int* row_pt
     auto const t0 = clk::now();
     C.x.resize(static_cast<size_t>(n2));
     HIPCHK(h, hipMemcpy(C.x.data(), C.d_xacc, static_cast<size_t>(n2) * sizeof(double), hipMemcpyDeviceToHost));
+    // (the residual kernel takes its maximum with fmax, which drops a NaN: a row that touches a non-finite x says nothing there)
+    if(!all_finite(C.x.data(), C.x.size())) return fail(h, PE_HIP_ERR_INACCURATE, "solve_csr_complex: the solution is not finite");
     for(int i = 0; i < n; ++i)
     {
         x_re_im[2 * static_cast<size_t>(i)] = C.x[i];

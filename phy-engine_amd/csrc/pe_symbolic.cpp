@@ -10,7 +10,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
+#include <limits>
 #include <numeric>
+#include <queue>
+#include <utility>
 
 namespace pe
 {
@@ -19,40 +23,162 @@ namespace pe
         using ivec = std::vector<int>;
 
         // ------------------------------------------------------------------------------------
-        // 1. row matching: unknown j <- equation rmatch[j], maximising (greedily) the scaled pivot size
+        // 1. row matching: unknown j <- equation rmatch[j]
+        //
+        // The numeric factorisation never searches for a pivot, so the matching IS the pivot choice, and a matching that is merely
+        // zero-free is not enough: on a circuit with many branch rows (inductors, controlled sources, transformers) a greedy choice
+        // strings pivots of 1e-3 beside entries of 1 into chains whose multipliers multiply up -- errors of 1e9 tolerance units on
+        // matrices of condition 6e7 that partial pivoting solves to 1e-8.
+        //
+        // (a) weighted_matching: the matching of maximum PRODUCT of the magnitudes (equivalently minimum sum of cost = log(max|row|) -
+        //     log|a|), by shortest augmenting paths on reduced costs (Dijkstra with row / column potentials u, v: the sparse assignment
+        //     algorithm of Duff & Koster's MC64).  On return cost - u - v >= 0 for every entry and = 0 for the matched ones: with the
+        //     rows scaled by exp(u) / max|row| and the columns by exp(v) every entry of A is <= 1 in magnitude and every matched one is
+        //     1.  A factorisation without pivot search is invariant under such a scaling, so the scaling is never applied: it is the
+        //     yardstick in which a pivot's size is judged.
+        // (b) match_plain: the own diagonal is kept wherever it is >= tau_diag in that scaling -- a symmetric pattern fills less, a
+        //     node-voltage matrix keeps the identity, and the diagonal of an MNA matrix is a sound pivot well below the entries beside it:
+        //     a conductance of 1e-3 beside susceptances of 1e3 whose own block [[1, -1], [-1, 1]] is singular (two nodes joined by a
+        //     capacitor in the real-equivalent AC system) is the pivot that works, the larger entries are the ones that cancel.  The other
+        //     equations are matched by augmenting paths over entries >= tau only, largest scaled magnitude first: an off-diagonal pivot has
+        //     nothing structural to recommend it, so it has to be large -- threshold pivoting with threshold tau, decided once.  A path
+        //     always exists: the matching of (a) is a perfect matching among those entries.
         // ------------------------------------------------------------------------------------
-        bool match_rows(int n, int const* rp, int const* ci, double const* vals, double diag_rel, ivec& rmatch, int& swaps)
+        // red[e]: reduced cost of entry e (-log of its scaled magnitude; +inf for an explicit zero).  False: structurally singular.
+        bool weighted_matching(int n, int const* rp, int const* ci, double const* vals, std::vector<double>& red, ivec& rmatch)
         {
-            rmatch.assign(n, -1);
-            ivec colof(n, -1);  // equation i -> unknown it pivots
-            std::vector<double> rowmax(n, 0.0);
-            for(int i = 0; i < n; ++i)
-                for(int e = rp[i]; e < rp[i + 1]; ++e) rowmax[i] = std::max(rowmax[i], vals ? std::fabs(vals[e]) : 1.0);
-            // pass 1: keep the diagonal wherever it is usable
-            for(int i = 0; i < n; ++i)
+            double const inf = std::numeric_limits<double>::infinity();
+            int const nnz = rp[n];
+            red.assign(nnz, 0.0);
+            std::vector<double> u(n, 0.0), v(n, 0.0);
+            if(vals)
             {
-                for(int e = rp[i]; e < rp[i + 1]; ++e)
+                for(int i = 0; i < n; ++i)
                 {
-                    if(ci[e] != i) continue;
-                    double const w = vals ? std::fabs(vals[e]) : 1.0;
-                    if(w > 0.0 && w >= diag_rel * rowmax[i])
+                    double mx = 0.0;
+                    // (an infinite entry is a usable pivot, the largest there is; a NaN is none)
+                    double const big = std::numeric_limits<double>::max();
+                    for(int e = rp[i]; e < rp[i + 1]; ++e)
+                        if(double const w = std::min(std::fabs(vals[e]), big); w > mx) mx = w;
+                    for(int e = rp[i]; e < rp[i + 1]; ++e)
                     {
-                        rmatch[i] = i;
-                        colof[i] = i;
+                        double const w = std::min(std::fabs(vals[e]), big);
+                        red[e] = w > 0.0 ? std::log(mx) - std::log(w) : inf;
                     }
                 }
+                // starting potentials: v = column minimum, u = row minimum of what is left
+                v.assign(n, inf);
+                for(int e = 0; e < nnz; ++e) v[ci[e]] = std::min(v[ci[e]], red[e]);
+                for(int j = 0; j < n; ++j)
+                    if(v[j] == inf) return false;
+                for(int i = 0; i < n; ++i)
+                {
+                    u[i] = inf;
+                    for(int e = rp[i]; e < rp[i + 1]; ++e)
+                        if(red[e] < inf) u[i] = std::min(u[i], red[e] - v[ci[e]]);
+                    if(u[i] == inf) return false;
+                }
             }
-            // pass 2: augmenting paths for the remaining equations, heaviest (row-scaled) candidates first
+            rmatch.assign(n, -1);
+            ivec colof(n, -1);
+            // tight entries first (the diagonal before the others)
+            for(int pass = 0; pass < 2; ++pass)
+                for(int i = 0; i < n; ++i)
+                    for(int e = rp[i]; e < rp[i + 1] && colof[i] < 0; ++e)
+                    {
+                        int const c = ci[e];
+                        if((pass == 0 && c != i) || rmatch[c] >= 0 || !(red[e] - u[i] - v[c] <= 0.0)) continue;
+                        rmatch[c] = i;
+                        colof[i] = c;
+                    }
+            // shortest augmenting path from every equation still free
+            std::vector<double> d(n, inf), lrow(n, 0.0);
+            ivec pred(n, -1), seen(n, -1), done(n, -1), tree_rows, done_cols;
+            using item = std::pair<double, int>;
+            std::priority_queue<item, std::vector<item>, std::greater<item>> heap;
+            for(int r0 = 0; r0 < n; ++r0)
+            {
+                if(colof[r0] >= 0) continue;
+                heap = {};
+                tree_rows.assign(1, r0);
+                done_cols.clear();
+                lrow[r0] = 0.0;
+                int i = r0, jend = -1;
+                double lsp = 0.0;
+                for(;;)
+                {
+                    for(int e = rp[i]; e < rp[i + 1]; ++e)
+                    {
+                        int const c = ci[e];
+                        if(red[e] == inf || done[c] == r0) continue;
+                        double const nd = lrow[i] + std::max(0.0, red[e] - u[i] - v[c]);
+                        if(seen[c] != r0 || nd < d[c])
+                        {
+                            seen[c] = r0;
+                            d[c] = nd;
+                            pred[c] = i;
+                            heap.push({nd, c});
+                        }
+                    }
+                    int c = -1;
+                    while(!heap.empty())
+                    {
+                        auto const [dd, cc] = heap.top();
+                        heap.pop();
+                        if(done[cc] == r0 || dd > d[cc]) continue;
+                        c = cc;
+                        break;
+                    }
+                    if(c < 0) return false;  // no zero-free diagonal exists
+                    done[c] = r0;
+                    if(rmatch[c] < 0)
+                    {
+                        jend = c;
+                        lsp = d[c];
+                        break;
+                    }
+                    done_cols.push_back(c);
+                    i = rmatch[c];
+                    lrow[i] = d[c];
+                    tree_rows.push_back(i);
+                }
+                for(int c: done_cols) v[c] += d[c] - lsp;
+                for(int r: tree_rows) u[r] += lsp - lrow[r];
+                for(int c = jend;;)
+                {
+                    int const r = pred[c], prev = colof[r];
+                    rmatch[c] = r;
+                    colof[r] = c;
+                    if(r == r0) break;
+                    c = prev;
+                }
+            }
+            for(int i = 0; i < n; ++i)
+                for(int e = rp[i]; e < rp[i + 1]; ++e)
+                    if(red[e] < inf) red[e] = std::max(0.0, red[e] - u[i] - v[ci[e]]);
+            return true;
+        }
+
+        // Keep the diagonal of the equations with diag_ok, then augmenting paths by depth-first search for the others: the candidates of an
+        // equation are its entries with key < inf, smallest key first (ties: lowest column).  False: no perfect matching among them.
+        bool dfs_matching(int n, int const* rp, int const* ci, std::vector<double> const& key, std::vector<char> const& diag_ok, ivec& rmatch)
+        {
+            double const inf = std::numeric_limits<double>::infinity();
+            rmatch.assign(n, -1);
+            ivec colof(n, -1);  // equation i -> unknown it pivots
+            for(int i = 0; i < n; ++i)
+                if(diag_ok[i])
+                {
+                    rmatch[i] = i;
+                    colof[i] = i;
+                }
             std::vector<ivec> cand(n);
             auto build_cand = [&](int i)
             {
                 if(!cand[i].empty()) return;
                 std::vector<std::pair<double, int>> t;
                 for(int e = rp[i]; e < rp[i + 1]; ++e)
-                {
-                    double const w = vals ? std::fabs(vals[e]) : 1.0;
-                    if(w > 0.0) t.push_back({-w, ci[e]});
-                }
+                    if(key[e] < inf) t.push_back({key[e], ci[e]});
                 std::sort(t.begin(), t.end());
                 for(auto const& [w, c]: t) cand[i].push_back(c);
             };
@@ -89,7 +215,7 @@ namespace pe
                     it[nxt] = 0;
                     stack_row.push_back(nxt);
                 }
-                if(!found) return false;  // structurally singular
+                if(!found) return false;
                 // flip along the path: stack_row[t] takes stack_col[t]
                 for(size_t t = 0; t < stack_row.size(); ++t)
                 {
@@ -97,6 +223,121 @@ namespace pe
                     colof[stack_row[t]] = stack_col[t];
                 }
             }
+            return true;
+        }
+
+        // The greedy matching: the diagonal wherever it is >= diag_rel of its row, every non-zero entry a candidate of the others, heaviest
+        // first.  Cheap, and on node-voltage matrices the choice the goldens were recorded with -- but it looks at no pivot's size beyond the
+        // order of the search: match_plain judges the result.
+        bool greedy_matching(int n, int const* rp, int const* ci, double const* vals, double diag_rel, ivec& rmatch)
+        {
+            std::vector<double> key(rp[n]);
+            std::vector<char> diag_ok(n, 0);
+            for(int i = 0; i < n; ++i)
+            {
+                double rowmax = 0.0;
+                for(int e = rp[i]; e < rp[i + 1]; ++e) rowmax = std::max(rowmax, vals ? std::fabs(vals[e]) : 1.0);
+                for(int e = rp[i]; e < rp[i + 1]; ++e)
+                {
+                    double const w = vals ? std::fabs(vals[e]) : 1.0;
+                    key[e] = w > 0.0 ? -w : std::numeric_limits<double>::infinity();
+                    if(ci[e] == i && w > 0.0 && w >= diag_rel * rowmax) diag_ok[i] = 1;
+                }
+            }
+            return dfs_matching(n, rp, ci, key, diag_ok, rmatch);
+        }
+
+        bool match_plain(int n, int const* rp, int const* ci, double const* vals, double tau, double tau_diag, bool greedy_only, ivec& rmatch)
+        {
+            if(greedy_only) return greedy_matching(n, rp, ci, vals, tau_diag, rmatch);
+            std::vector<double> red;
+            ivec best;
+            if(!weighted_matching(n, rp, ci, vals, red, best)) return false;
+            // an entry qualifies as a pivot when its scaled magnitude is >= tau (the slack: the matched entries of (a) are 1 up to rounding)
+            double const limit = -std::log(std::min(1.0, std::max(tau, 1e-300))) + 1e-9;
+            double const limit_diag = std::max(limit, -std::log(std::min(1.0, std::max(tau_diag, 1e-300))));
+            // the greedy matching first: taken when it meets the same two thresholds
+            if(greedy_matching(n, rp, ci, vals, tau_diag, rmatch))
+            {
+                bool ok = true;
+                for(int i = 0; i < n && ok; ++i)
+                    for(int e = rp[i]; e < rp[i + 1]; ++e)
+                        if(rmatch[ci[e]] == i) ok = ok && red[e] <= (ci[e] == i ? limit_diag : limit);
+                if(ok) return true;
+            }
+            std::vector<double> key(rp[n]);
+            std::vector<char> diag_ok(n, 0);
+            for(int i = 0; i < n; ++i)
+                for(int e = rp[i]; e < rp[i + 1]; ++e)
+                {
+                    key[e] = red[e] <= limit ? red[e] : std::numeric_limits<double>::infinity();
+                    if(ci[e] == i && red[e] <= limit_diag) diag_ok[i] = 1;
+                }
+            // (a failure is unreachable but for rounding at the limit: the matching of (a) lies among the qualifying entries)
+            if(!dfs_matching(n, rp, ci, key, diag_ok, rmatch)) rmatch = best;
+            return true;
+        }
+
+        // (c) The real-equivalent form [[Ar, -Ai], [Ai, Ar]] of a complex system of order h = n / 2, rows laid out as pe_engine_seam.cpp
+        //     real_equivalent_pattern lays them out (row i = [columns of complex row i | the same + h], row h + i likewise).  Rows i and
+        //     h + i carry the two halves of the same complex entries, equal in magnitude, and a matching on magnitudes is free to take the
+        //     halves of a complex pivot from two different entries: on AC stamps of circuits it then ends on blocks that cancel exactly
+        //     (a zero pivot).  So the COMPLEX matrix is matched, on the moduli |a + j b| of its entries, by (a) and (b) above, and a matched
+        //     entry (i, j) becomes the pivot block of rows i, h + i and columns j, h + j, entered through its larger half: a on the
+        //     diagonal of the block when |a| >= |b|, otherwise b (equation i takes unknown h + j and equation h + i unknown j).
+        //     False when the pattern is not of that layout.
+        bool paired_layout(int n, int const* rp, int const* ci)
+        {
+            int const h = n / 2;
+            if(n % 2) return false;
+            for(int i = 0; i < h; ++i)
+            {
+                int const len = rp[i + 1] - rp[i], half = len / 2;
+                if(len % 2 || rp[h + i + 1] - rp[h + i] != len) return false;
+                for(int k = 0; k < half; ++k)
+                {
+                    int const c = ci[rp[i] + k];
+                    if(c >= h || ci[rp[i] + half + k] != c + h || ci[rp[h + i] + k] != c || ci[rp[h + i] + half + k] != c + h) return false;
+                }
+            }
+            return true;
+        }
+        bool match_paired(int n, int const* rp, int const* ci, double const* vals, double tau, double tau_diag, bool greedy_only, ivec& rmatch)
+        {
+            int const h = n / 2;
+            ivec rp1(h + 1, 0), ci1, rm1;
+            std::vector<double> mod;
+            for(int i = 0; i < h; ++i)
+            {
+                int const half = (rp[i + 1] - rp[i]) / 2;
+                for(int k = 0; k < half; ++k)
+                {
+                    ci1.push_back(ci[rp[i] + k]);
+                    mod.push_back(std::hypot(vals[rp[i] + k], vals[rp[i] + half + k]));
+                }
+                rp1[i + 1] = static_cast<int>(ci1.size());
+            }
+            if(!match_plain(h, rp1.data(), ci1.data(), mod.data(), tau, tau_diag, greedy_only, rm1)) return false;
+            rmatch.assign(n, -1);
+            for(int i = 0; i < h; ++i)
+            {
+                int const half = (rp[i + 1] - rp[i]) / 2;
+                for(int k = 0; k < half; ++k)
+                {
+                    int const j = ci[rp[i] + k];
+                    if(rm1[j] != i) continue;
+                    bool const real_half = std::fabs(vals[rp[i] + k]) >= std::fabs(vals[rp[i] + half + k]);
+                    rmatch[j] = real_half ? i : h + i;
+                    rmatch[h + j] = real_half ? h + i : i;
+                }
+            }
+            return true;
+        }
+
+        bool match_rows(int n, int const* rp, int const* ci, double const* vals, SymbolicOptions const& opt, ivec& rmatch, int& swaps)
+        {
+            bool const paired = opt.match_pairs && vals && paired_layout(n, rp, ci);
+            if(!(paired ? match_paired : match_plain)(n, rp, ci, vals, opt.match_tau, opt.match_diag_tau, opt.match_greedy, rmatch)) return false;
             swaps = 0;
             for(int j = 0; j < n; ++j) swaps += rmatch[j] != j;
             return true;
@@ -373,7 +614,7 @@ namespace pe
         if(n == 0) return true;
 
         ivec rmatch;
-        if(!match_rows(n, rp, ci, vals, opt.match_diag_rel, rmatch, S.n_row_swaps))
+        if(!match_rows(n, rp, ci, vals, opt, rmatch, S.n_row_swaps))
         {
             S.structurally_singular = true;
             S.error = "structurally singular matrix (no zero-free diagonal exists)";

@@ -33,7 +33,12 @@ namespace pe
         int relax_small{8};       // always merge a last child into its parent while the merged front has <= this many pivots
         double relax_zero_frac{0.30};  // otherwise merge only if the explicit zeros added stay below this fraction of the merged panel
         int max_pivots{48};       // never grow a front beyond this many pivots (chains are split)
-        double match_diag_rel{1e-8};   // keep a_jj as pivot when |a_jj| >= rel * max|row|
+        // row matching (pe_symbolic.cpp match_rows), both in the scaling of the maximum-product matching (every entry <= 1, the matched ones 1):
+        double match_diag_tau{1e-8};   // keep a_jj as pivot when it is >= this
+        double match_tau{0.1};         // any other entry may be a pivot when it is >= this
+        bool match_greedy{};           // take the greedy matching as it is (the AC engines: pe_engine_internal.hpp greedy_match)
+        bool match_pairs{};            // the matrix is the real-equivalent form of a complex one in the layout of pe_engine_seam.cpp: match the
+                                       // complex matrix on the moduli of its entries, every pivot a 2 x 2 block (pe_symbolic.cpp match_paired)
         // GPU mapping limits (see pe_front.hpp): a WAVE front (m <= wave_m, p <= wave_p) is factorised by one
         // wavefront in its own LDS slot; larger fronts are COOPERATIVE: the whole workgroup, pivot panels in LDS
         int wave_m{48};
