@@ -766,6 +766,93 @@ int pe_hip_get_net_status(pe_hip_engine* h, int first_point, int n_points, int f
 int pe_hip_convert_net(pe_hip_engine* h, int n_ports, int n_mats, const double* z_re, const double* z_im, const double* z0, double* y_re, double* y_im,
                        double* s_re, double* s_im, int* y_status, int* s_status);
 
+/* ---- Pole-zero analysis (.PZ): the natural frequencies of the circuit at its operating point nearest to a shift the caller names, and
+ * the zeros of one transfer function, by shift-invert Arnoldi on ONE factorisation.
+ *   The pencil.  The small-signal matrix of pe_hip_analyze_ac is affine in omega: A(s) = G + s B with real G = Re A(j 1), B = Im A(j 1).
+ *   The poles are the finite s with det A(s) = 0.  Independent sources do not matter: only the matrix is used.  The shift is
+ *   s0 = j omega0, omega0 > 0 finite, chosen near the band of interest: a purely imaginary shift is what the real-equivalent engine
+ *   factors anyway, A0 = A(s0).
+ *   Poles.  s = s0 - omega0 / theta' over the eigenvalues theta' of M' = A0^-1 (omega0 B); omega0 B is the lower-left block of the matrix
+ *   the engine has assembled at omega0, nothing is divided by omega0.  Eigenvalues with |theta'| <= theta_floor max |theta'| are the
+ *   pencil's infinite eigenvalues (nodes without reactive elements) and are dropped: a definition, not a tolerance.
+ *   Zeros of H(s) = c^T A(s)^-1 b, b a unit current into in_pos and out of in_neg, c reading x[out_pos] - x[out_neg] (rows as in
+ *   pe_hip_analyze_net: -1 is ground, a branch row makes it a voltage excitation): the finite eigenvalues of the bordered pencil
+ *   [[A(s), b], [c^T, 0]], whose shift-inverted operator is M'_z v = w - z (c^T w) / (c^T z) with w = M' v, z = A0^-1 b -- one more
+ *   solve on the kept factors per call.  c^T z = H(s0) is returned (pe_hip_get_pz_gain).  H(s0) zero or not finite: that instance's
+ *   zeros carry PE_HIP_ERR_SINGULAR, its poles are unaffected.  A mode that is uncontrollable or unobservable from the chosen ports
+ *   appears as a coinciding pole and zero, as in SPICE.
+ *   What the floor cannot remove.  Where the infinite eigenvalue is DEFECTIVE -- a Jordan block of size p at theta' = 0, which the bordered
+ *   pencil of a transfer function with several zeros at infinity can have -- rounding spreads it over a ring of p values at
+ *   |theta'| ~ (2^-52)^(1/p) max |theta'|, far above any relative floor (p = 7: 6e-3).  The call returns them: up to p more values, the
+ *   farthest of the list, |s - s0| ~ omega0 / |theta'|, ill-determined in every digit.  err_est measures the Krylov residual only, not the
+ *   conditioning of a value: on a complete instance they carry err_est 0 and count as converged like every other value.  A caller tells
+ *   them by their distance (beyond the band the shift was chosen for) or by moving omega0: a zero stays where it is, the ring moves.
+ *   Iteration, per instance, all instances in lock-step.  The start vector is M' r, r a fixed function of the row index (no random
+ *   numbers: the same for every instance and run).  Arnoldi without restart, up to max_krylov steps, classical Gram-Schmidt applied twice
+ *   against all previous vectors.  An instance is COMPLETE when h(k+1,k) <= breakdown_tol |w|, |w| taken before orthogonalisation: its
+ *   Krylov space is invariant, its Ritz values are the whole finite spectrum reachable from the start vector; it is parked -- its
+ *   right-hand sides are zero from then on, nothing of it is overwritten.  Ritz values are the eigenvalues of the k x k Hessenberg
+ *   matrix (complex single-shift QR with Wilkinson shifts on the device, at most 30 k sweeps: beyond that the instance carries
+ *   PE_HIP_ERR_NO_CONVERGENCE).  err_est = |h(k+1,k)| |e_k^T y_i| / |theta'_i|, 0 for a complete instance; a value is CONVERGED when
+ *   err_est <= tol.  Results per instance are sorted by |s - s0| ascending, ties by larger imaginary part first.  Fewer than n_wanted
+ *   converged leading entries is no failure of the call: the counts say so.  No restarts.
+ *   Operating point.  The rule of pe_hip_analyze_net: run pe_hip_analyze_dc(PE_HIP_MODE_OP) first; an instance whose last analysis failed
+ *   has no operating point: the call returns that status, every instance carries it and reads NaN.
+ *   Statuses.  A singular or non-finite A0 (the shift on a pole of a lossless LC, a NaN parameter) gives that instance the engine's
+ *   status: it reads NaN, the others stay readable.  Returns PE_HIP_OK or the first failing instance's status.
+ *   One factorisation.  The call is one pass of one point of the sweep body: poles and zeros together are 1 + 2 (max_krylov + 1)
+ *   right-hand sides on one factorisation; n_factorisations is 1 plus whatever the residual safety net forced, n_solves the batched
+ *   kept-factor solves, refinement corrections included.
+ *   Determinism.  The kernels of this call sum through a fixed tree per instance (no atomics) and nothing of an instance is read from
+ *   another or from an earlier call: two calls return the same bits.  Across batches the same holds where the solves do -- the static pivot
+ *   order of the factorisation is matched on instance 0's values, as for every analysis of these engines: an instance reads the same bits
+ *   at another batch size or position when that order is the same (always, when it is instance 0 in both).
+ *   State.  The call has state of its own; the main engine is read and never written: a stored AC sweep, noise, sensitivity, network
+ *   and DC-sweep result read the same bits before and after.  The basis takes batch x (max_krylov + 1) x 2 rows doubles on the device,
+ *   checked against the memory budget of the sweep's automatic pass size.
+ *   PE_HIP_ERR_ARG, engine unchanged: no circuit, c NULL, `what` outside 1 .. 3, omega0 not finite or <= 0, n_wanted or max_krylov outside
+ *   1 .. PE_HIP_PZ_MAX_KRYLOV, n_wanted > max_krylov, a non-finite or negative tol, theta_floor or breakdown_tol, when zeros are asked
+ *   for a row out of range or pos == neg for a port (both -1 included), a basis that does not fit the memory budget, a circuit with a
+ *   host-stamp overlay.  There is no twin on the multi-device pe_hip_sweep_* handle. */
+#define PE_HIP_PZ_MAX_KRYLOV 64
+enum { PE_HIP_PZ_POLES = 1, PE_HIP_PZ_ZEROS = 2 };
+typedef struct pe_hip_pz_control {
+    int what;                 /* PE_HIP_PZ_POLES, PE_HIP_PZ_ZEROS, or 3: both */
+    double omega0;            /* the shift s0 = j omega0, rad/s, finite, > 0 */
+    int n_wanted;             /* 1 .. max_krylov: how many nearest values the caller is after.  Validated only: the call always runs max_krylov
+                                 steps, and the caller compares n_converged with it */
+    int max_krylov;           /* Arnoldi steps, 1 .. PE_HIP_PZ_MAX_KRYLOV; 0: 32 */
+    double tol;               /* err_est of a converged value; 0: 1e-10 */
+    double theta_floor;       /* 0: 1e-12 */
+    double breakdown_tol;     /* 0: 2^-40 */
+    int in_pos, in_neg;       /* rows of b (zeros only) */
+    int out_pos, out_neg;     /* rows of c (zeros only) */
+} pe_hip_pz_control;
+typedef struct pe_hip_pz_stats {
+    int n_steps;              /* Arnoldi steps run per kind (poles, zeros): max_krylov, or 0 when no pass ran */
+    int n_factorisations;     /* batched numeric factorisations launched: 1 + what the safety net forced */
+    int n_solves;             /* batched kept-factor solves, refinement corrections included */
+    int n_refine_rounds;      /* correction solves */
+    int n_complete;           /* instances whose pole iteration is complete */
+    double gpu_ms;            /* HIP-event time of the pass and of the Ritz kernel */
+} pe_hip_pz_stats;
+/* instance_status: NULL or [batch], the worst of what the instance's poles and zeros carry */
+int pe_hip_analyze_pz(pe_hip_engine* h, const pe_hip_pz_control* c, int* instance_status, pe_hip_pz_stats* stats);
+/* results of the last call, which = PE_HIP_PZ_POLES or PE_HIP_PZ_ZEROS (it must have been asked for): re, im, err_est [count][capacity]
+ * padded with NaN (values past capacity are not returned); n_found, n_converged (the length of the leading converged run), complete
+ * [count]; any output pointer may be NULL */
+int pe_hip_get_pz(pe_hip_engine* h, int which, int first_instance, int count, int capacity, double* re, double* im, double* err_est, int* n_found,
+                  int* n_converged, int* complete);
+/* H(s0) = c^T A0^-1 b of the last call (it must have asked for zeros): re, im [count] */
+int pe_hip_get_pz_gain(pe_hip_engine* h, int first_instance, int count, double* re, double* im);
+/* The dense eigenvalue kernel alone, on caller-supplied upper Hessenberg matrices h_re / h_im [n_mats][m][m] (what lies below the
+ * subdiagonal is not read), 1 <= m <= PE_HIP_PZ_MAX_KRYLOV.  Needs a created engine, no circuit.  theta_re / theta_im [n_mats][m]: the
+ * eigenvalues; last_re / last_im [n_mats][m]: for each the last component of its unit eigenvector; status [n_mats]: PE_HIP_OK,
+ * PE_HIP_ERR_SINGULAR (an entry is not finite: that matrix reads NaN) or PE_HIP_ERR_NO_CONVERGENCE.  PE_HIP_ERR_ARG: m out of range,
+ * n_mats < 1, a NULL pointer. */
+int pe_hip_eig_hessenberg(pe_hip_engine* h, int m, int n_mats, const double* h_re, const double* h_im, double* theta_re, double* theta_im, double* last_re,
+                          double* last_im, int* status);
+
 /* x = [node voltages ; branch currents], instance-major [count][rows] */
 int pe_hip_get_solution(pe_hip_engine* h, int first_instance, int count, double* x);
 int pe_hip_set_solution(pe_hip_engine* h, int first_instance, int count, const double* x);

@@ -3,7 +3,8 @@
 // sweep as batches of that system on a third engine, pe_ac_sweep.hpp), and pe_hip_analyze_noise / pe_hip_get_noise* (the same sweep body
 // on the adjoint system, pe_noise.hpp), and pe_hip_analyze_sens / pe_hip_get_sens* (the same body on the adjoint system at omega = 0, one
 // point per output, pe_sens.hpp), and pe_hip_analyze_net / pe_hip_get_net* / pe_hip_convert_net (the same body on a forward system of its
-// own with one right-hand side per port on one factorisation per pass, pe_net.hpp).
+// own with one right-hand side per port on one factorisation per pass, pe_net.hpp), and pe_hip_analyze_pz / pe_hip_get_pz* /
+// pe_hip_eig_hessenberg (the same body once more: one pass of one point, every Arnoldi step a right-hand side on the kept factors, pe_pz.hpp).
 #include "pe_engine_internal.hpp"
 
 #include <functional>
@@ -106,6 +107,8 @@ namespace pe_eng
         h->sens = pe_hip_engine::Sens{};
         h->net.sys.drop();
         h->net = pe_hip_engine::Net{};
+        h->pz.sys.drop();
+        h->pz = pe_hip_engine::Pz{};
     }
 
     int KeptRows::set(pe_hip_engine* h, char const* name, int n_rows, int const* rows_in)
@@ -357,6 +360,8 @@ namespace
         std::function<int(pe_hip_engine* E, int j)> next_rhs;
         int* n_factorisations = nullptr;                        // (counted from the engine's n_factor_launches)
         int* n_solves = nullptr;                                // kept-factor solves
+        // pole-zero analysis only: the statuses the engine's instances carried in the last pass (it reports per instance, not per point)
+        std::vector<int>* inst_status = nullptr;
     };
 
     // point i of the host result: every checked value finite / every block NaN
@@ -614,6 +619,7 @@ namespace
             HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
             S.gpu_ms += ms;
             if(int const rc = check_above(); rc != PE_HIP_OK) return rc;
+            if(K.inst_status) *K.inst_status = inst_status;
             for(int p = 0; p < n; ++p)
                 for(int b = 0; b < B; ++b)
                     if(inst_status[static_cast<size_t>(b) * P + p] != 0) failed[point_h[p]] = 1;
@@ -1675,6 +1681,327 @@ int pe_hip_convert_net(pe_hip_engine* h, int n_ports, int n_mats, const double* 
 
 }  // extern "C"
 
+static_assert(pe::PZ_MAX_KRYLOV == PE_HIP_PZ_MAX_KRYLOV && pe::PZ_ERR_SINGULAR == PE_HIP_ERR_SINGULAR && pe::PZ_ERR_NO_CONVERGENCE == PE_HIP_ERR_NO_CONVERGENCE,
+              "pe_pz.hpp names these without including the C header");
+
+extern "C" {
+
+/* Poles and zeros nearest to s0 = j omega0: the sweep body of pe_hip_analyze_ac_sweep on a forward system with state of its own (h->pz),
+ * ONE pass of ONE point whose engine keeps its factors -- the first right-hand side is b (z = A0^-1 b, H(s0)), then every Arnoldi step is
+ * one more: (omega0 B) v written by k_pz_bmul, the refined kept-factor solve, k_pz_orth in the epilogue; k_pz_ritz after the last step of
+ * a kind.  Definitions: include/pe_hip.h. */
+int pe_hip_analyze_pz(pe_hip_engine* h, const pe_hip_pz_control* ctl, int* instance_status, pe_hip_pz_stats* stats)
+{
+    if(!h || !h->loaded) return PE_HIP_ERR_ARG;
+    if(stats) std::memset(stats, 0, sizeof(*stats));
+    if(!ctl) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: no control");
+    auto& hc = h->hc;
+    int const B = hc.batch, N = hc.rows;
+    int const what = ctl->what, m = ctl->max_krylov == 0 ? 32 : ctl->max_krylov;
+    if(what < 1 || what > 3) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: what must be 1 (poles), 2 (zeros) or 3 (both)");
+    if(!std::isfinite(ctl->omega0) || !(ctl->omega0 > 0.0)) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: omega0 must be finite and positive");
+    if(m < 1 || m > PE_HIP_PZ_MAX_KRYLOV) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: max_krylov out of range");
+    if(ctl->n_wanted < 1 || ctl->n_wanted > PE_HIP_PZ_MAX_KRYLOV) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: n_wanted out of range");
+    if(ctl->n_wanted > m) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: n_wanted > max_krylov");
+    for(double const v: {ctl->tol, ctl->theta_floor, ctl->breakdown_tol})
+        if(!std::isfinite(v) || v < 0.0) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: tol, theta_floor and breakdown_tol must be finite and not negative");
+    bool const zeros = (what & PE_HIP_PZ_ZEROS) != 0, poles = (what & PE_HIP_PZ_POLES) != 0;
+    if(zeros)
+    {
+        for(int const r: {ctl->in_pos, ctl->in_neg, ctl->out_pos, ctl->out_neg})
+            if(r < -1 || r >= N) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: port row out of range");
+        if(ctl->in_pos == ctl->in_neg || ctl->out_pos == ctl->out_neg) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: a port needs two different rows (-1: ground)");
+    }
+    if(has_overlay(h)) return fail(h, PE_HIP_ERR_ARG, "analyze_pz: host-stamped overlay models are not supported");
+    size_t const R2 = 2 * static_cast<size_t>(N);
+    if(static_cast<long long>(static_cast<size_t>(B) * (m + 1) * R2 * sizeof(double)) > sweep_memory_budget())
+        return fail(h, PE_HIP_ERR_ARG, "analyze_pz: the Krylov basis (batch x (max_krylov + 1) x 2 rows doubles) does not fit the memory budget");
+    HIPCHK(h, hipSetDevice(h->device));
+    auto& Z = h->pz;
+    auto& A = Z.sys;
+    auto& W = A.sweep;
+    Z.valid = false;
+    double const tol = ctl->tol == 0.0 ? 1.0e-10 : ctl->tol, theta_floor = ctl->theta_floor == 0.0 ? 1.0e-12 : ctl->theta_floor;
+    double const breakdown_tol = ctl->breakdown_tol == 0.0 ? 0x1p-40 : ctl->breakdown_tol;
+    int const kinds[2] = {poles ? PE_HIP_PZ_POLES : PE_HIP_PZ_ZEROS, PE_HIP_PZ_ZEROS}, n_kinds = (poles && zeros) ? 2 : 1;
+    size_t const plane = static_cast<size_t>(B) * m;
+    for(int t = 0; t < 2; ++t)
+    {
+        Z.res[t].assign(3 * plane, std::nan(""));
+        Z.n_found[t].assign(static_cast<size_t>(B), 0);
+        Z.n_conv[t].assign(static_cast<size_t>(B), 0);
+        Z.complete[t].assign(static_cast<size_t>(B), 0);
+        Z.status[t].assign(static_cast<size_t>(B), PE_HIP_OK);
+    }
+    Z.gain.assign(2 * static_cast<size_t>(B), std::nan(""));
+    std::vector<int> worst(static_cast<size_t>(B), PE_HIP_OK);
+    pe_hip_ac_sweep_stats S{};
+    int n_fact = 0, n_solves = 0, steps_run = 0;
+    auto publish = [&]() -> int
+    {
+        Z.batch = B;
+        Z.capacity = m;
+        Z.what = what;
+        Z.valid = true;
+        for(int t = 0; t < n_kinds; ++t)
+            for(int b = 0; b < B; ++b)
+                if(worst[b] == PE_HIP_OK) worst[b] = Z.status[kinds[t] - 1][b];
+        if(instance_status) std::copy(worst.begin(), worst.end(), instance_status);
+        if(stats)
+        {
+            stats->n_steps = steps_run;
+            stats->n_factorisations = n_fact;
+            stats->n_solves = n_solves;
+            stats->n_refine_rounds = S.n_refine_rounds;
+            auto const& done = Z.complete[kinds[0] - 1];
+            stats->n_complete = static_cast<int>(std::count(done.begin(), done.end(), 1));
+            stats->gpu_ms = S.gpu_ms;
+        }
+        for(int b = 0; b < B; ++b)
+            if(worst[b] != PE_HIP_OK) return fail(h, worst[b], "analyze_pz: instance " + std::to_string(b) + " failed");
+        return PE_HIP_OK;
+    };
+    if(N == 0) return publish();
+
+    // an instance whose last analysis failed has no operating point to linearise at: the call carries that status instead of numbers
+    int bad = -1, bad_status = PE_HIP_OK;
+    if(int const rc = operating_point_status(h, bad, bad_status); rc != PE_HIP_OK) return rc;
+    if(bad >= 0)
+    {
+        for(int t = 0; t < n_kinds; ++t) std::fill(Z.status[kinds[t] - 1].begin(), Z.status[kinds[t] - 1].end(), bad_status);
+        (void)publish();
+        return fail(h, bad_status, "analyze_pz: instance " + std::to_string(bad) + " has no operating point (its last analysis failed)");
+    }
+
+    // ---- the forward system; its right-hand-side lists select the input port (poles alone: row 0 -- the first solve is the one that factors)
+    int const pos0 = zeros ? ctl->in_pos : 0, neg0 = zeros ? ctl->in_neg : -1;
+    if(!A.built)
+    {
+        if(int const rc = ensure_ac_built(h, A); rc != PE_HIP_OK) return rc;
+        Z.have_port = false;
+    }
+    if(!Z.have_port || Z.pos0 != pos0 || Z.neg0 != neg0) select_rhs(A, pos0, neg0);
+    Z.have_port = true;
+    Z.pos0 = pos0;
+    Z.neg0 = neg0;
+
+    std::vector<int> pst(1, PE_HIP_OK), inst;
+    bool unanalysable = false;
+    int kind_at = 0, step_at = -1;  // the right-hand side the pass is solving: -1: b; else step `step_at` of kind `kind_at`
+    size_t const cnt = 5 * static_cast<size_t>(B);  // per kind: n_found | n_converged | Ritz status | parked | steps
+    SweepHooks hooks;
+    hooks.name = "analyze_pz";
+    hooks.pass_knob = "PZ_POINTS";
+    hooks.n_rhs = 1 + n_kinds * (m + 1);
+    hooks.keep_factors = true;
+    hooks.n_factorisations = &n_fact;
+    hooks.n_solves = &n_solves;
+    hooks.inst_status = &inst;
+    hooks.single = [&](int) -> int
+    {
+        unanalysable = inst.empty();  // (no pass ran: the band's values could not be analysed)
+        return PE_HIP_OK;
+    };
+    hooks.prepare = [&](int P) -> int
+    {
+        if(P != 1) return fail(h, PE_HIP_ERR_INTERNAL, "analyze_pz: more than one point per pass");
+        if(Z.buf_batch != static_cast<size_t>(B) || Z.buf_rows != R2 || Z.buf_m != m)
+        {
+            Z.buf_pool.release();
+            Z.V = pe::PzView{};
+            Z.buf_batch = Z.buf_rows = 0;
+            Z.buf_m = 0;
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.basis, static_cast<size_t>(B) * (m + 1) * R2));
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.h_re, static_cast<size_t>(B) * (m + 1) * m));
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.h_im, static_cast<size_t>(B) * (m + 1) * m));
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.zvec, static_cast<size_t>(B) * R2));
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.gain, 2 * static_cast<size_t>(B)));
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.steps, static_cast<size_t>(B)));
+            HIPCHK(h, Z.buf_pool.alloc(Z.V.parked, static_cast<size_t>(B)));
+            Z.buf_batch = static_cast<size_t>(B);
+            Z.buf_rows = R2;
+            Z.buf_m = m;
+        }
+        HIPCHK(h, Z.d_res.ensure(2 * 3 * plane, false));
+        HIPCHK(h, Z.d_cnt.ensure(2 * cnt, false));
+        HIPCHK(h, Z.d_res.fill_nan());
+        HIPCHK(h, hipMemset(Z.d_cnt.p, 0, Z.d_cnt.len * sizeof(int)));
+        Z.V.n_half = N;
+        Z.V.rhs0 = A.rhs0;
+        Z.V.m_max = m;
+        Z.V.in_pos = zeros ? ctl->in_pos : -1;
+        Z.V.in_neg = zeros ? ctl->in_neg : -1;
+        Z.V.out_pos = zeros ? ctl->out_pos : -1;
+        Z.V.out_neg = zeros ? ctl->out_neg : -1;
+        Z.V.breakdown_tol = breakdown_tol;
+        Z.V.xacc = W.V.xacc;
+        Z.V.b0 = W.V.b0;
+        return PE_HIP_OK;
+    };
+    hooks.after_fill = [&](pe_hip_engine*) -> int
+    {
+        kind_at = 0;
+        step_at = -1;
+        return PE_HIP_OK;
+    };
+    hooks.next_rhs = [&](pe_hip_engine* E, int j) -> int
+    {
+        kind_at = (j - 1) / (m + 1);
+        step_at = (j - 1) % (m + 1);
+        if(step_at == 0)  // a kind starts: every instance runs again, the Hessenberg matrices are this kind's
+        {
+            HIPCHK(h, hipMemsetAsync(Z.V.steps, 0, static_cast<size_t>(B) * sizeof(int), E->stream));
+            HIPCHK(h, hipMemsetAsync(Z.V.parked, 0, static_cast<size_t>(B) * sizeof(int), E->stream));
+            HIPCHK(h, hipMemsetAsync(Z.V.h_re, 0, static_cast<size_t>(B) * (m + 1) * m * sizeof(double), E->stream));
+            HIPCHK(h, hipMemsetAsync(Z.V.h_im, 0, static_cast<size_t>(B) * (m + 1) * m * sizeof(double), E->stream));
+        }
+        HIPCHK(h, pe::launch_pz_bmul(E->stream, E->V, Z.V, step_at - 1));
+        return PE_HIP_OK;
+    };
+    hooks.epilogue = [&](pe_hip_engine* E) -> int
+    {
+        if(step_at < 0)
+        {
+            HIPCHK(h, pe::launch_pz_store_z(E->stream, E->V, Z.V));
+            return PE_HIP_OK;
+        }
+        bool const kz = kinds[kind_at] == PE_HIP_PZ_ZEROS;
+        HIPCHK(h, pe::launch_pz_orth(E->stream, E->V, Z.V, step_at, kz));
+        if(step_at < m) return PE_HIP_OK;
+        // the last step of a kind: its Ritz values, and what the next kind overwrites
+        double* const d = Z.d_res.p + static_cast<size_t>(kind_at) * 3 * plane;
+        int* const c = Z.d_cnt.p + static_cast<size_t>(kind_at) * cnt;
+        pe::PzRitzView R{};
+        R.n_mats = B;
+        R.m = m;
+        R.steps = Z.V.steps;
+        R.parked = Z.V.parked;
+        R.h_re = Z.V.h_re;
+        R.h_im = Z.V.h_im;
+        R.mat_stride = static_cast<long long>(m + 1) * m;
+        R.ld = m;
+        R.omega0 = ctl->omega0;
+        R.theta_floor = theta_floor;
+        R.tol = tol;
+        R.s_re = d;
+        R.s_im = d + plane;
+        R.s_err = d + 2 * plane;
+        R.n_found = c;
+        R.n_conv = c + B;
+        R.status = c + 2 * B;
+        HIPCHK(h, pe::launch_pz_ritz(E->stream, R));
+        HIPCHK(h, hipMemcpyAsync(c + 3 * B, Z.V.parked, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToDevice, E->stream));
+        HIPCHK(h, hipMemcpyAsync(c + 4 * B, Z.V.steps, static_cast<size_t>(B) * sizeof(int), hipMemcpyDeviceToDevice, E->stream));
+        return PE_HIP_OK;
+    };
+    if(int const rc = sweep_body(h, A, 1, &ctl->omega0, pst, S, hooks); rc != PE_HIP_OK) return rc;
+    steps_run = inst.empty() ? 0 : m;  // (no pass ran where the band's values could not be analysed)
+
+    // ---- results and statuses per instance
+    std::vector<double> res(2 * 3 * plane);
+    std::vector<int> c(2 * cnt);
+    HIPCHK(h, hipMemcpy(res.data(), Z.d_res.p, res.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(c.data(), Z.d_cnt.p, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if(zeros) HIPCHK(h, hipMemcpy(Z.gain.data(), Z.V.gain, Z.gain.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for(int t = 0; t < n_kinds; ++t)
+    {
+        int const k = kinds[t] - 1;
+        int const* ct = c.data() + static_cast<size_t>(t) * cnt;
+        for(int b = 0; b < B; ++b)
+        {
+            int st = unanalysable ? PE_HIP_ERR_SINGULAR : (b < static_cast<int>(inst.size()) ? inst[b] : PE_HIP_OK);
+            if(st == PE_HIP_OK && ct[3 * B + b] == pe::PZ_PARKED_FAILED) st = PE_HIP_ERR_SINGULAR;  // zeros: H(s0) is 0 or not finite; else a vector was not finite
+            if(st == PE_HIP_OK) st = ct[2 * B + b];
+            Z.status[k][b] = st;
+            if(st != PE_HIP_OK) continue;
+            for(int pl = 0; pl < 3; ++pl)
+                std::copy_n(res.data() + (static_cast<size_t>(t) * 3 + pl) * plane + static_cast<size_t>(b) * m, m, Z.res[k].data() + pl * plane + static_cast<size_t>(b) * m);
+            Z.n_found[k][b] = ct[b];
+            Z.n_conv[k][b] = ct[B + b];
+            Z.complete[k][b] = ct[3 * B + b] == pe::PZ_PARKED_COMPLETE ? 1 : 0;
+        }
+    }
+    for(int b = 0; b < B; ++b)  // (an instance the engine failed has no gain either)
+        if(unanalysable || (b < static_cast<int>(inst.size()) && inst[b] != PE_HIP_OK)) Z.gain[2 * b] = Z.gain[2 * b + 1] = std::nan("");
+    return publish();
+}
+
+int pe_hip_get_pz(pe_hip_engine* h, int which, int first_instance, int count, int capacity, double* re, double* im, double* err_est, int* n_found,
+                  int* n_converged, int* complete)
+{
+    if(!h || !h->loaded || (which != PE_HIP_PZ_POLES && which != PE_HIP_PZ_ZEROS) || capacity < 0) return PE_HIP_ERR_ARG;
+    auto const& Z = h->pz;
+    if(int const rc = stored_window(h, "get_pz", "pole-zero analysis", nullptr, Z.valid, Z.batch, 0, 0, 0, first_instance, count); rc != PE_HIP_OK) return rc;
+    if(!(Z.what & which)) return fail(h, PE_HIP_ERR_ARG, "get_pz: the last call did not ask for this kind");
+    int const k = which - 1;
+    size_t const plane = static_cast<size_t>(Z.batch) * Z.capacity;
+    double* const out[3] = {re, im, err_est};
+    for(int pl = 0; pl < 3; ++pl)
+        for(int b = 0; out[pl] && b < count; ++b)
+            for(int i = 0; i < capacity; ++i)
+                out[pl][static_cast<size_t>(b) * capacity + i] = i < Z.capacity ? Z.res[k][pl * plane + static_cast<size_t>(first_instance + b) * Z.capacity + i] : std::nan("");
+    for(int b = 0; b < count; ++b)
+    {
+        if(n_found) n_found[b] = Z.n_found[k][first_instance + b];
+        if(n_converged) n_converged[b] = Z.n_conv[k][first_instance + b];
+        if(complete) complete[b] = Z.complete[k][first_instance + b];
+    }
+    return PE_HIP_OK;
+}
+
+int pe_hip_get_pz_gain(pe_hip_engine* h, int first_instance, int count, double* re, double* im)
+{
+    if(!h || !h->loaded || !re || !im) return PE_HIP_ERR_ARG;
+    auto const& Z = h->pz;
+    if(int const rc = stored_window(h, "get_pz_gain", "pole-zero analysis", nullptr, Z.valid, Z.batch, 0, 0, 0, first_instance, count); rc != PE_HIP_OK) return rc;
+    if(!(Z.what & PE_HIP_PZ_ZEROS)) return fail(h, PE_HIP_ERR_ARG, "get_pz_gain: the last call did not ask for zeros");
+    for(int b = 0; b < count; ++b)
+    {
+        re[b] = Z.gain[2 * static_cast<size_t>(first_instance + b)];
+        im[b] = Z.gain[2 * static_cast<size_t>(first_instance + b) + 1];
+    }
+    return PE_HIP_OK;
+}
+
+/* the Ritz kernel of pe_hip_analyze_pz on the caller's matrices */
+int pe_hip_eig_hessenberg(pe_hip_engine* h, int m, int n_mats, const double* h_re, const double* h_im, double* theta_re, double* theta_im, double* last_re,
+                          double* last_im, int* status)
+{
+    if(!h) return PE_HIP_ERR_ARG;
+    if(m < 1 || m > PE_HIP_PZ_MAX_KRYLOV || n_mats < 1 || !h_re || !h_im || !theta_re || !theta_im || !last_re || !last_im || !status)
+        return fail(h, PE_HIP_ERR_ARG, "eig_hessenberg: m out of range, n_mats < 1 or a null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    size_t const mm = static_cast<size_t>(n_mats) * m * m, nm = static_cast<size_t>(n_mats) * m;
+    Pool pool;
+    double *d_h{}, *d_o{};
+    int* d_status{};
+    HIPCHK(h, pool.alloc(d_h, 2 * mm, false));
+    HIPCHK(h, pool.alloc(d_o, 4 * nm, false));
+    HIPCHK(h, pool.alloc(d_status, static_cast<size_t>(n_mats)));
+    HIPCHK(h, hipMemcpy(d_h, h_re, mm * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_h + mm, h_im, mm * sizeof(double), hipMemcpyHostToDevice));
+    pe::PzRitzView R{};
+    R.n_mats = n_mats;
+    R.m = m;
+    R.h_re = d_h;
+    R.h_im = d_h + mm;
+    R.mat_stride = static_cast<long long>(m) * m;
+    R.ld = m;
+    R.theta_re = d_o;
+    R.theta_im = d_o + nm;
+    R.last_re = d_o + 2 * nm;
+    R.last_im = d_o + 3 * nm;
+    R.status = d_status;
+    HIPCHK(h, pe::launch_pz_ritz(h->stream, R));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double* const out[4] = {theta_re, theta_im, last_re, last_im};
+    for(int k = 0; k < 4; ++k) HIPCHK(h, hipMemcpy(out[k], d_o + k * nm, nm * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(status, d_status, static_cast<size_t>(n_mats) * sizeof(int), hipMemcpyDeviceToHost));
+    return PE_HIP_OK;
+}
+
+}  // extern "C"
+
 #if !defined(__HIPCC__)
 // Builds without HIP (the emulation library of tests/emu): the sweep's launchers as serial loops over the instances, with a one-thread
 // team running the text of pe_ac_sweep.hpp
@@ -1777,6 +2104,43 @@ namespace pe
             net_convert(NetSerialWave{}, n, z_re + o, z_im + o, z0, y_re ? y_re + o : nullptr, y_im ? y_im + o : nullptr, s_re ? s_re + o : nullptr,
                         s_im ? s_im + o : nullptr, y_status ? y_status + m : nullptr, s_status ? s_status + m : nullptr);
         }
+        return hipSuccess;
+    }
+    // ... and the pole-zero launchers with the text of pe_pz.hpp (one thread sums in ascending order; the Ritz kernel's LDS is a heap buffer
+    // of exactly its size)
+    namespace
+    {
+        struct PzHostTeam
+        {
+            mutable double cr[PZ_MAX_KRYLOV], ci[PZ_MAX_KRYLOV];
+            int tid() const { return 0; }
+            int size() const { return 1; }
+            void sync() const {}
+            void sum2(double&, double&) const {}
+            void keep(int j, double re, double im) const { cr[j] = re, ci[j] = im; }
+            void kept(int j, double& re, double& im) const { re = cr[j], im = ci[j]; }
+        };
+    }  // namespace
+    hipError_t launch_pz_bmul(hipStream_t, DevView const& V, PzView const& Z, int src)
+    {
+        for(int q = 0; q < V.batch; ++q) pz_bmul(SweepHostTeam{}, V, Z, q, src);
+        return hipSuccess;
+    }
+    hipError_t launch_pz_store_z(hipStream_t, DevView const& V, PzView const& Z)
+    {
+        for(int q = 0; q < V.batch; ++q) pz_store_z(SweepHostTeam{}, V, Z, q);
+        return hipSuccess;
+    }
+    hipError_t launch_pz_orth(hipStream_t, DevView const& V, PzView const& Z, int k, bool zeros)
+    {
+        PzHostTeam const tm{};  // (the caller has checked k)
+        for(int q = 0; q < V.batch; ++q) pz_orth(tm, V, Z, q, k, zeros);
+        return hipSuccess;
+    }
+    hipError_t launch_pz_ritz(hipStream_t, PzRitzView const& R)
+    {
+        std::vector<double> lds(static_cast<size_t>(pz_ritz_doubles(R.m)));
+        for(int i = 0; i < R.n_mats; ++i) pz_ritz(PzSerialWave{}, R, i, lds.data());  // (both callers have checked R.m)
         return hipSuccess;
     }
 }  // namespace pe

@@ -8,7 +8,7 @@
 //   pe_engine_newton.cpp      host-driven Newton / transient loops of the split schedule, residual safety net, pe_hip_analyze_tr / _dc
 //   pe_engine_checkpoint.cpp  pe_hip_checkpoint_*
 //   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep, pe_hip_analyze_noise / pe_hip_get_noise*,
-//                             pe_hip_analyze_sens / pe_hip_get_sens*, pe_hip_analyze_net / pe_hip_get_net*; the helpers of every stored result (KeptRows, stored_window)
+//                             pe_hip_analyze_sens / pe_hip_get_sens*, pe_hip_analyze_net / pe_hip_get_net*, pe_hip_analyze_pz / pe_hip_get_pz*; the helpers of every stored result (KeptRows, stored_window)
 //   pe_engine_seam.cpp        pe_hip_solve_csr_complex (the complex twin of the solver seam)
 //   pe_sweep.cpp              pe_hip_sweep_*: the multi-device handle (uses EnginePtr and engine_build only; everything else through the C ABI)
 #pragma once
@@ -38,6 +38,7 @@
 #include "pe_net.hpp"
 #include "pe_noise.hpp"
 #include "pe_op_step.hpp"
+#include "pe_pz.hpp"
 #include "pe_sens.hpp"
 #include "pe_symbolic.hpp"
 
@@ -249,10 +250,10 @@ using pe_eng::Pool;
 // ORDER of destruction is the reverse of the declaration order below, and it matters:
 //   - stream and events are declared first: they go last, after everything that was enqueued on them;
 //   - the pools are declared before the captured-graph cache: the graphs go before the memory their nodes point into and before the stream;
-//   - the sub-engines (ac, noise, sens, net, dcs) are declared after the pools and buffers their kernels read: each goes first, and
+//   - the sub-engines (ac, noise, sens, net, pz, dcs) are declared after the pools and buffers their kernels read: each goes first, and
 //     synchronises its own stream in its pe_hip_destroy.
 // A state struct that holds a sub-engine beside buffers of its own (Ac, Ac::Sweep, DcSweep) does not leave that to its member order: its
-// destructor and its drop() reset the engine explicitly before anything else goes.  Noise, Sens and Net declare their Ac last.
+// destructor and its drop() reset the engine explicitly before anything else goes.  Noise, Sens, Net and Pz declare their Ac last.
 struct pe_hip_engine
 {
     int device{};
@@ -475,6 +476,26 @@ struct pe_hip_engine
         std::vector<int> status;          // [2][n_points][batch]
         Ac sys;                           // (declared last: its engines go before the tables and buffers above)
     } net;
+    // pole-zero analysis (pe_hip_analyze_pz, pe_pz.hpp): a FORWARD real-equivalent system with sweep state of its own, like the network
+    // analysis -- its right-hand-side lists hold the input port's selector, its engine keeps the factors --, the Arnoldi buffers (sized by
+    // batch x max_krylov x 2N: released when a call of another shape comes) and the result of the last call
+    struct Pz
+    {
+        bool have_port{};
+        int pos0{-1}, neg0{-1};           // the port the right-hand-side lists of `sys` select
+        Pool buf_pool;                    // basis, Hessenberg matrices, z, gain, steps, parked
+        size_t buf_batch{}, buf_rows{};
+        int buf_m{};
+        pe_eng::DevBuf<double> d_res;     // Ritz output [2 kinds][3][batch][max_krylov]: s re | s im | err_est (kind 0: the first kind the call ran)
+        pe_eng::DevBuf<int> d_cnt;        // [2 kinds][5][batch]: n_found | n_converged | status of the Ritz kernel | parked | steps at the kind's end
+        pe::PzView V{};
+        bool valid{};                     // the results below belong to the current circuit at its current operating point
+        int batch{}, capacity{}, what{};
+        std::vector<double> res[2];       // poles, zeros: [3][batch][capacity]
+        std::vector<int> n_found[2], n_conv[2], complete[2], status[2];  // [batch] each
+        std::vector<double> gain;         // [batch][2] H(s0)
+        Ac sys;                           // (declared last: its engines go before the buffers above)
+    } pz;
     long long n_factor_launches{};  // batched numeric factorisations launched by dc_solve / dc_solve_kept on this engine (its first attempt and every retry group)
     // DC sweep (pe_hip_analyze_dc_sweep, pe_dc_sweep.hpp): an engine of its own holding this circuit with batch (circuit batch) x P -- the
     // points of one pass are extra instances --, the buffers of its kernels and the stored result.  The main engine is only read.
@@ -647,6 +668,7 @@ namespace pe_eng PE_ENG_HIDDEN
         h->noise.valid = false;
         h->sens.valid = false;
         h->net.valid = false;
+        h->pz.valid = false;
     }
     // The check every getter of a stored result makes: there is one (`valid`, made at the batch the engine has now) -- else "<name>: no
     // <what> yet" --, and items [first, first + n) of its n_items and instances [first_instance, first_instance + count) lie inside it --

@@ -28,6 +28,7 @@
 #include "pe_op_step.hpp"
 #include "pe_noise.hpp"
 #include "pe_net.hpp"
+#include "pe_pz.hpp"
 #include "pe_sens.hpp"
 #include "pe_lte.hpp"
 #include "pe_kernels.hpp"
@@ -2067,6 +2068,117 @@ namespace pe
         if(n < 1 || n > NET_MAX_PORTS) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_net_convert, dim3((n_mats + NET_MATS_PER_GROUP - 1) / NET_MATS_PER_GROUP), dim3(64 * NET_MATS_PER_GROUP), 0, st, n, n_mats, z_re, z_im,
                            z0, y_re, y_im, s_re, s_im, y_status, s_status);
+        return hipGetLastError();
+    }
+
+    // ---- pole-zero analysis (pe_pz.hpp, pe_engine_ac.cpp pe_hip_analyze_pz / pe_hip_eig_hessenberg)
+    // (omega0 B) x basis vector `src` as the right-hand side of instance blockIdx.y (before the kept-factor solve of an Arnoldi step)
+    __global__ void __launch_bounds__(256) k_pz_bmul(DevView V, PzView Z, int src)
+    {
+        pz_bmul(GridTeam{}, V, Z, static_cast<int>(blockIdx.y), src);
+    }
+    // One workgroup per instance.  A sum: every thread its strided subsequence in ascending order, the 64 lanes by a fixed __shfl_down
+    // tree, the four wavefronts through LDS in wavefront order.  No atomics: an instance's numbers depend on that instance alone.
+    struct PzBlockTeam
+    {
+        double* red;   // [2][4]
+        double* coef;  // [2][PZ_MAX_KRYLOV]
+        __device__ __forceinline__ int tid() const { return static_cast<int>(threadIdx.x); }
+        __device__ __forceinline__ int size() const { return PZ_ORTH_THREADS; }
+        __device__ __forceinline__ void sync() const { __syncthreads(); }
+        __device__ __forceinline__ void sum2(double& a, double& b) const
+        {
+#pragma unroll
+            for(int o = 32; o > 0; o >>= 1)
+            {
+                a += __shfl_down(a, o);
+                b += __shfl_down(b, o);
+            }
+            int const wv = static_cast<int>(threadIdx.x) >> 6;
+            if((threadIdx.x & 63) == 0)
+            {
+                red[wv] = a;
+                red[4 + wv] = b;
+            }
+            __syncthreads();
+            a = ((red[0] + red[1]) + red[2]) + red[3];
+            b = ((red[4] + red[5]) + red[6]) + red[7];
+            __syncthreads();
+        }
+        __device__ __forceinline__ void keep(int j, double re, double im) const
+        {
+            if(threadIdx.x == 0)
+            {
+                coef[j] = re;
+                coef[PZ_MAX_KRYLOV + j] = im;
+            }
+        }
+        __device__ __forceinline__ void kept(int j, double& re, double& im) const
+        {
+            re = coef[j];
+            im = coef[PZ_MAX_KRYLOV + j];
+        }
+    };
+    // k < 0: z and H(s0) of the instance from the first solve; else Arnoldi step k
+    __global__ void __launch_bounds__(PZ_ORTH_THREADS) k_pz_orth(DevView V, PzView Z, int k, int zeros)
+    {
+        __shared__ double red[8];
+        __shared__ double coef[2 * PZ_MAX_KRYLOV];
+        PzBlockTeam const tm{red, coef};
+        int const q = static_cast<int>(blockIdx.x);
+        if(k < 0) pz_store_z(tm, V, Z, q);
+        else
+            pz_orth(tm, V, Z, q, k, zeros != 0);
+    }
+    // One wavefront per matrix, one matrix per workgroup: the matrix, the last row of the unitary factor and five vectors in dynamic LDS
+    // (pz_ritz_doubles).  The workgroup IS the wavefront, so its barrier orders the lanes' LDS traffic.  No scratch, no atomics.
+    struct PzWave
+    {
+        __device__ __forceinline__ int lane() const { return static_cast<int>(threadIdx.x); }
+        __device__ __forceinline__ int lanes() const { return 64; }
+        __device__ __forceinline__ void sync() const { __syncthreads(); }
+        __device__ __forceinline__ double nanmax(double v, double*) const
+        {
+#pragma unroll
+            for(int o = 32; o > 0; o >>= 1) v = ac_nanmax(v, __shfl_xor(v, o));
+            return v;
+        }
+    };
+    __global__ void __launch_bounds__(64) k_pz_ritz(PzRitzView R)
+    {
+        pz_ritz(PzWave{}, R, static_cast<int>(blockIdx.x), pe_lds);
+    }
+    hipError_t launch_pz_bmul(hipStream_t st, DevView const& V, PzView const& Z, int src)
+    {
+        if(V.batch <= 0 || V.rows <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_pz_bmul, dim3(sweep_grid(V.rows / 2), V.batch), dim3(256), 0, st, V, Z, src);
+        return hipGetLastError();
+    }
+    hipError_t launch_pz_store_z(hipStream_t st, DevView const& V, PzView const& Z)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        hipLaunchKernelGGL(k_pz_orth, dim3(V.batch), dim3(PZ_ORTH_THREADS), 0, st, V, Z, -1, 0);
+        return hipGetLastError();
+    }
+    hipError_t launch_pz_orth(hipStream_t st, DevView const& V, PzView const& Z, int k, bool zeros)
+    {
+        if(V.batch <= 0) return hipSuccess;
+        if(k < 0 || k > PZ_MAX_KRYLOV) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_pz_orth, dim3(V.batch), dim3(PZ_ORTH_THREADS), 0, st, V, Z, k, zeros ? 1 : 0);
+        return hipGetLastError();
+    }
+    hipError_t launch_pz_ritz(hipStream_t st, PzRitzView const& R)
+    {
+        if(R.n_mats <= 0) return hipSuccess;
+        if(R.m < 1 || R.m > PZ_MAX_KRYLOV) return hipErrorInvalidValue;
+        // refused, not truncated, where a workgroup cannot have that much LDS
+        size_t const bytes = static_cast<size_t>(pz_ritz_doubles(R.m)) * sizeof(double);
+        int dev = 0, limit = 0;
+        if(hipError_t const e = hipGetDevice(&dev); e != hipSuccess) return e;
+        if(hipError_t const e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev); e != hipSuccess) return e;
+        if(bytes > static_cast<size_t>(limit)) return hipErrorInvalidValue;
+        if(hipError_t const e = set_lds(reinterpret_cast<void const*>(&k_pz_ritz), bytes); e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_pz_ritz, dim3(R.n_mats), dim3(64), bytes, st, R);
         return hipGetLastError();
     }
 

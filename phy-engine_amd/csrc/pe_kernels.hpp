@@ -96,6 +96,17 @@ namespace pe
     hipError_t launch_net_gather(hipStream_t st, DevView const& V, NetView const& Z, int j);
     hipError_t launch_net_convert(hipStream_t st, int n, int n_mats, double const* z_re, double const* z_im, double const* z0, double* y_re, double* y_im,
                                   double* s_re, double* s_im, int* y_status, int* s_status);
+    // pole-zero analysis (pe_pz.hpp): V is the view of the call's engine (one point per pass).  bmul: (omega0 B) x basis vector `src` (-1:
+    // the start vector's pre-image) into the right-hand-side slots of every instance and into Z.b0, zeros for a parked instance.  store_z:
+    // Z.zvec and Z.gain from Z.xacc.  orth: Arnoldi step k of every running instance from Z.xacc (zeros: with the rank-one correction),
+    // one workgroup per instance.  ritz: the matrices of R, one wavefront per matrix with the matrix in LDS; hipErrorInvalidValue when
+    // R.m is out of range or the matrix does not fit the LDS of a workgroup.  Builds without HIP: serial host definitions in pe_engine_ac.cpp.
+    struct PzView;
+    struct PzRitzView;
+    hipError_t launch_pz_bmul(hipStream_t st, DevView const& V, PzView const& Z, int src);
+    hipError_t launch_pz_store_z(hipStream_t st, DevView const& V, PzView const& Z);
+    hipError_t launch_pz_orth(hipStream_t st, DevView const& V, PzView const& Z, int k, bool zeros);
+    hipError_t launch_pz_ritz(hipStream_t st, PzRitzView const& R);
     // variable-step transient (pe_lte.hpp): lte: q of the candidate V.x against the history ring + failed / non-finite instances into
     // L.result (cleared first); history_push: V.x of every instance into ring slot `slot`; state_copy: every (dst, src, bytes) of the table
     // (snapshot and roll-back of a step).  Builds without HIP: serial host definitions in pe_engine_newton.cpp.

@@ -37,6 +37,7 @@ EXPORTS = [
     "pe_hip_analyze_noise", "pe_hip_get_noise", "pe_hip_get_noise_sources", "pe_hip_get_noise_source_density", "pe_hip_get_noise_integrated",
     "pe_hip_get_sens_params", "pe_hip_analyze_sens", "pe_hip_get_sens",
     "pe_hip_analyze_net", "pe_hip_get_net", "pe_hip_get_net_status", "pe_hip_convert_net",
+    "pe_hip_analyze_pz", "pe_hip_get_pz", "pe_hip_get_pz_gain", "pe_hip_eig_hessenberg",
     "pe_hip_set_dc_sweep_rows", "pe_hip_analyze_dc_sweep", "pe_hip_get_dc_sweep", "pe_hip_get_dc_sweep_status",
     "pe_hip_analyze_op_stepping", "pe_hip_get_op_step_state", "pe_hip_get_op_step_log", "pe_hip_sweep_operating_point_stepping",
     "pe_hip_get_static_fronts", "pe_hip_get_static_skip_stats", "pe_hip_get_static_skip_refinement_stats",
@@ -45,6 +46,8 @@ EXPORTS = [
 DC_SWEEP_PARALLEL, DC_SWEEP_TRACE = 0, 1
 NET_MAX_PORTS = 8
 NET_Z, NET_Y, NET_S = 0, 1, 2
+PZ_MAX_KRYLOV = 64
+PZ_POLES, PZ_ZEROS, PZ_BOTH = 1, 2, 3
 # pe_hip_tr_method
 TR_TRAP, TR_BE, TR_GEAR2 = 0, 1, 2
 _TR_NAMES = {"trap": TR_TRAP, "be": TR_BE, "gear2": TR_GEAR2, "gear": TR_GEAR2}
@@ -285,6 +288,20 @@ class NetStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PzControl(C.Structure):
+    _fields_ = [("what", C.c_int), ("omega0", C.c_double), ("n_wanted", C.c_int), ("max_krylov", C.c_int), ("tol", C.c_double),
+                ("theta_floor", C.c_double), ("breakdown_tol", C.c_double), ("in_pos", C.c_int), ("in_neg", C.c_int), ("out_pos", C.c_int),
+                ("out_neg", C.c_int)]
+
+
+class PzStats(C.Structure):
+    _fields_ = [("n_steps", C.c_int), ("n_factorisations", C.c_int), ("n_solves", C.c_int), ("n_refine_rounds", C.c_int), ("n_complete", C.c_int),
+                ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -348,6 +365,10 @@ def lib():
         l.pe_hip_get_net.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.pe_hip_get_net_status.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         l.pe_hip_convert_net.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 7 + [C.POINTER(C.c_int)] * 2
+        l.pe_hip_analyze_pz.argtypes = [C.c_void_p, C.POINTER(PzControl), C.POINTER(C.c_int), C.POINTER(PzStats)]
+        l.pe_hip_get_pz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int)] * 3
+        l.pe_hip_get_pz_gain.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.pe_hip_eig_hessenberg.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 6 + [C.POINTER(C.c_int)]
         l.pe_hip_set_dc_sweep_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.pe_hip_analyze_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(DcSweepControl), C.POINTER(C.c_int), C.POINTER(DcSweepStats)]
         l.pe_hip_get_dc_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -965,6 +986,53 @@ class Engine(_Probes):
         ys, ss = np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1), dtype=np.int32)
         self._chk(lib().pe_hip_convert_net(self._h, n, m, _dp(zr), _dp(zi), _dp(ref) if ref is not None else None, *[_dp(o) for o in out], _ip(ys), _ip(ss)))
         return ((out[0] + 1j * out[1]).reshape(Zc.shape), (out[2] + 1j * out[3]).reshape(Zc.shape), ys[:m].reshape(lead), ss[:m].reshape(lead))
+
+    def analyze_pz(self, omega0, what=PZ_POLES, n_wanted=1, max_krylov=32, ports=None, tol=0.0, theta_floor=0.0, breakdown_tol=0.0, check=True):
+        """Poles and / or zeros nearest to the shift j omega0 by shift-invert Arnoldi on one factorisation (pe_hip_analyze_pz).  ports:
+        ((in_pos, in_neg), (out_pos, out_neg)) rows of x, -1: ground -- needed for zeros.  Returns (instance_status [batch], stats dict with
+        the return code under 'rc'); the values come from pz() / pz_gain()."""
+        (ip, ineg), (op, on) = ports if ports is not None else ((-1, -1), (-1, -1))
+        ctl = PzControl(int(what), float(omega0), int(n_wanted), int(max_krylov), float(tol), float(theta_floor), float(breakdown_tol), int(ip), int(ineg),
+                        int(op), int(on))
+        status = np.zeros(max(self.batch, 1), dtype=np.int32)
+        st = PzStats()
+        rc = lib().pe_hip_analyze_pz(self._h, C.byref(ctl), _ip(status), C.byref(st))
+        if check:
+            self._chk(rc)
+        d = st.asdict()
+        d["rc"] = rc
+        return status[:self.batch], d
+
+    def pz(self, which=PZ_POLES, capacity=PZ_MAX_KRYLOV):
+        """The poles (PZ_POLES) or zeros (PZ_ZEROS) of the last analyze_pz: (s complex [batch][capacity] sorted by |s - s0|, padded with NaN,
+        err_est [batch][capacity], n_found, n_converged, complete [batch])."""
+        B = self.batch
+        re, im, err = np.empty((B, capacity)), np.empty((B, capacity)), np.empty((B, capacity))
+        nf, nc, cp = (np.zeros(max(B, 1), dtype=np.int32) for _ in range(3))
+        self._chk(lib().pe_hip_get_pz(self._h, int(which), 0, B, int(capacity), _dp(re), _dp(im), _dp(err), _ip(nf), _ip(nc), _ip(cp)))
+        return re + 1j * im, err, nf[:B], nc[:B], cp[:B]
+
+    def pz_gain(self):
+        """H(s0) = c^T A0^-1 b of the last analyze_pz that asked for zeros, complex [batch]"""
+        re, im = np.empty(max(self.batch, 1)), np.empty(max(self.batch, 1))
+        self._chk(lib().pe_hip_get_pz_gain(self._h, 0, self.batch, _dp(re), _dp(im)))
+        return (re + 1j * im)[:self.batch]
+
+    def eig_hessenberg(self, H):
+        """Eigenvalues of upper Hessenberg matrices H complex [..., m, m] (1 <= m <= PZ_MAX_KRYLOV) and, for each, the last component of its
+        unit eigenvector, by the Ritz kernel of analyze_pz (pe_hip_eig_hessenberg; needs no circuit).  Returns (theta, last complex
+        [..., m], status [...])."""
+        Hc = np.asarray(H, dtype=np.complex128)
+        m = Hc.shape[-1]
+        if Hc.ndim < 2 or Hc.shape[-2] != m:
+            raise ValueError("H must be [..., m, m]")
+        lead = Hc.shape[:-2]
+        n = int(np.prod(lead, dtype=np.int64))
+        hr, hi = np.ascontiguousarray(Hc.real).reshape(n, m, m), np.ascontiguousarray(Hc.imag).reshape(n, m, m)
+        out = [np.empty((n, m)) for _ in range(4)]
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(lib().pe_hip_eig_hessenberg(self._h, m, n, _dp(hr), _dp(hi), *[_dp(o) for o in out], _ip(status)))
+        return (out[0] + 1j * out[1]).reshape(lead + (m,)), (out[2] + 1j * out[3]).reshape(lead + (m,)), status[:n].reshape(lead)
 
     def phase_clocks_coop(self, instance=0):
         """Per-layout breakdown of the cooperative fronts (see pe_hip_get_phase_clocks_ex), microseconds / counts."""

@@ -1493,6 +1493,67 @@ namespace phy_engine
             return rc == PE_HIP_OK || gpu_fail();
         }
 
+        // Pole-zero analysis (pe_hip_analyze_pz, include/pe_hip.h): the poles of the circuit nearest to the shift j omega0 and, with ports,
+        // the zeros of V(out) / I(in) -- node pairs (positive, negative; null: ground) --, at the circuit's operating point, which is
+        // prepared and solved first (OP).  pz_poles / pz_zeros are sorted by |s - j omega0|; pz_*_err carry err_est, pz_*_converged the
+        // length of the leading converged run, pz_*_complete whether the iteration found the whole reachable spectrum; pz_gain is H(j omega0).
+        ::std::vector<::std::complex<double>> pz_poles{}, pz_zeros{};
+        ::std::vector<double> pz_poles_err{}, pz_zeros_err{};
+        int pz_poles_converged{}, pz_zeros_converged{};
+        bool pz_poles_complete{}, pz_zeros_complete{};
+        ::std::complex<double> pz_gain{};
+        pe_hip_pz_stats last_pz_stats{};
+        [[nodiscard]] bool analyze_pz(double omega0, int n_wanted = 1, int max_krylov = 32, net_port const* in = nullptr, net_port const* out = nullptr) noexcept
+        {
+            pz_poles.clear(), pz_zeros.clear(), pz_poles_err.clear(), pz_zeros_err.clear();
+            pz_poles_converged = pz_zeros_converged = 0;
+            pz_poles_complete = pz_zeros_complete = false;
+            pz_gain = {};
+            last_pz_stats = pe_hip_pz_stats{};
+            auto const saved = at;
+            at = analyze_type::OP;
+            bool ok = prepare();
+            if(ok) ok = solve();
+            at = saved;
+            if(!ok || !gpu_ || !loaded_) return false;
+            auto row = [&](::phy_engine::model::node_t const* n) { return (!n || n == &nl.ground_node) ? -1 : static_cast<int>(n->node_index); };
+            bool const zeros = in && out;
+            pe_hip_pz_control ctl{};
+            ctl.what = zeros ? (PE_HIP_PZ_POLES | PE_HIP_PZ_ZEROS) : PE_HIP_PZ_POLES;
+            ctl.omega0 = omega0;
+            ctl.n_wanted = n_wanted;
+            ctl.max_krylov = max_krylov;
+            ctl.in_pos = zeros ? row(in->pos) : -1;
+            ctl.in_neg = zeros ? row(in->neg) : -1;
+            ctl.out_pos = zeros ? row(out->pos) : -1;
+            ctl.out_neg = zeros ? row(out->neg) : -1;
+            int const rc = pe_hip_analyze_pz(gpu_, &ctl, nullptr, &last_pz_stats);
+            if(rc == PE_HIP_ERR_ARG || rc == PE_HIP_ERR_NO_DEVICE || rc == PE_HIP_ERR_INTERNAL) return gpu_fail();
+            int const cap = max_krylov == 0 ? 32 : max_krylov;
+            ::std::vector<double> re(static_cast<::std::size_t>(cap)), im(re.size()), err(re.size());
+            for(int which = PE_HIP_PZ_POLES; which <= (zeros ? PE_HIP_PZ_ZEROS : PE_HIP_PZ_POLES); ++which)
+            {
+                int found = 0, conv = 0, complete = 0;
+                if(pe_hip_get_pz(gpu_, which, 0, 1, cap, re.data(), im.data(), err.data(), &found, &conv, &complete) != PE_HIP_OK) return gpu_fail();
+                auto& s = which == PE_HIP_PZ_POLES ? pz_poles : pz_zeros;
+                auto& e = which == PE_HIP_PZ_POLES ? pz_poles_err : pz_zeros_err;
+                for(int k = 0; k < found; ++k)
+                {
+                    s.push_back({re[static_cast<::std::size_t>(k)], im[static_cast<::std::size_t>(k)]});
+                    e.push_back(err[static_cast<::std::size_t>(k)]);
+                }
+                (which == PE_HIP_PZ_POLES ? pz_poles_converged : pz_zeros_converged) = conv;
+                (which == PE_HIP_PZ_POLES ? pz_poles_complete : pz_zeros_complete) = complete != 0;
+            }
+            if(zeros)
+            {
+                double gr = 0.0, gi = 0.0;
+                if(pe_hip_get_pz_gain(gpu_, 0, 1, &gr, &gi) != PE_HIP_OK) return gpu_fail();
+                pz_gain = {gr, gi};
+            }
+            return rc == PE_HIP_OK || gpu_fail();
+        }
+
         // Operating point with gmin / source stepping (pe_hip_analyze_op_stepping, include/pe_hip.h): what analyze() does for OP, DC or the
         // operating point of TROP, with the continuation of the header where the direct Newton iteration fails.  method: PE_HIP_STEP_GMIN,
         // PE_HIP_STEP_SOURCE or PE_HIP_STEP_AUTO.  The solution is scattered into the nodes and branches as after analyze();
