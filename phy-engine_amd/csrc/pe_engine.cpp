@@ -248,6 +248,19 @@ int engine_build(int device, EnginePtr& out, pe_hip_engine* h, std::string const
     return fail(h, rc, name + ": " + msg);
 }
 
+int set_symbolic_reference(pe_hip_engine* h, int n_nodes, int n_branches, int n_tables, pe_hip_device_table const* tables)
+{
+    if(!h || !h->loaded || (n_tables > 0 && !tables)) return PE_HIP_ERR_ARG;
+    auto ref = std::make_unique<pe::HostCircuit>();
+    if(!pe::build_circuit(n_nodes, n_branches, 1, n_tables, tables, static_cast<int>(h->drv_node.size()), h->drv_node.data(), h->drv_volt.data(), *ref,
+                          h->overlay.empty() ? nullptr : &h->overlay))
+        return fail(h, PE_HIP_ERR_ARG, "set_symbolic_reference: " + ref->error);
+    if(ref->rp != h->hc.rp || ref->ci != h->hc.ci) return fail(h, PE_HIP_ERR_INTERNAL, "set_symbolic_reference: the pattern differs from the resident circuit's");
+    h->sym_ref = std::move(ref);
+    h->resident.sym_class = -1;  // (no analysis has run since the load; said here so that the order cannot be an older one)
+    return PE_HIP_OK;
+}
+
 // ---------------- transient probes (pe_probe.hpp)
 pe::ProbedView probe_view(pe_hip_engine const* h)
 {
@@ -516,6 +529,7 @@ int pe_hip_load_circuit(pe_hip_engine* h, int n_nodes, int n_branches, int batch
     ac_sweep_drop(h);
     dc_sweep_drop(h);
     h->ac.drop();
+    h->sym_ref.reset();
     if(!pe::build_circuit(n_nodes, n_branches, batch, n_tables, tables, static_cast<int>(h->drv_node.size()), h->drv_node.data(),
                           h->drv_volt.data(), h->hc, h->overlay.empty() ? nullptr : &h->overlay))
         return fail(h, PE_HIP_ERR_ARG, "load_circuit: " + h->hc.error);

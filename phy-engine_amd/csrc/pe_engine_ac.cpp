@@ -176,6 +176,34 @@ namespace pe_eng
         if(!op.rl_engaged.empty()) HIPCHK(h, hipMemcpy(op.rl_engaged.data(), h->V.rl_engaged, op.rl_engaged.size() * sizeof(int), hipMemcpyDeviceToHost));
         return PE_HIP_OK;
     }
+
+    // The static pivot order of a batch is matched on instance 0's values and holds for every instance.  A contact cell -- (k, k) of a
+    // switch or a relay -- is -r_open where the contact is open and exactly 0 where it is closed: with instance 0 open, the matching
+    // takes that cell for a pivot and every instance with the contact closed meets a zero pivot.  `rep`: the representative values per
+    // CSR slot of the AC system, from instance 0; vals [B][stride]: the value vectors of the instances.  A slot fed by a contact value
+    // that is 0 in some instance gets the representative value 0: the order then pivots on the incidence entries, as it does when
+    // instance 0's contact is closed.  Batches whose instances agree on their contact states keep the order they had.
+    void ac_mask_contacts_closed_elsewhere(pe::HostCircuit const& hc, pe::AcCircuit const& circ, double const* vals, size_t stride, std::vector<double>& rep)
+    {
+        int const B = hc.batch;
+        if(B < 2) return;
+        std::vector<char> closed_elsewhere(static_cast<size_t>(pe::DV_FIXED) + circ.slots.size(), 0);
+        bool any = false;
+        for(size_t i = 0; i < circ.slots.size(); ++i)
+        {
+            auto const& sl = circ.slots[i];
+            if(!(sl.kind == pe::AcSlot::RELAY_R || (sl.kind == pe::AcSlot::GEN_STATIC && hc.gen[static_cast<size_t>(sl.idx)].kind == PE_HIP_SWITCH))) continue;
+            size_t const v = pe::DV_FIXED + i;
+            if(vals[v] == 0.0) continue;
+            for(int b = 1; b < B && !closed_elsewhere[v]; ++b) closed_elsewhere[v] = vals[static_cast<size_t>(b) * stride + v] == 0.0;
+            any = any || closed_elsewhere[v];
+        }
+        if(!any) return;
+        auto const& ah = circ.hc;
+        for(size_t s = 0; s < ah.ci.size(); ++s)
+            for(int e = ah.a_ptr[s]; e < ah.a_ptr[s + 1]; ++e)
+                if(ah.a_src[e] >= 0 && closed_elsewhere[static_cast<size_t>(ah.a_src[e] >> 1)]) rep[s] = 0.0;
+    }
 }  // namespace pe_eng
 
 extern "C" {
@@ -237,6 +265,7 @@ int pe_hip_analyze_ac(pe_hip_engine* h, double omega, pe_hip_run_stats* st)
             }
             A.eng->sym_values_override[s] = acc;
         }
+        ac_mask_contacts_closed_elsewhere(hc, A.circ, dv.data(), static_cast<size_t>(ah.dv_len), A.eng->sym_values_override);
         A.eng->resident.sym_class = -1;
         A.sym_omega = omega;
     };
@@ -476,6 +505,7 @@ namespace
                 }
                 out[s] = acc;
             }
+            ac_mask_contacts_closed_elsewhere(hc, A.circ, base.data(), static_cast<size_t>(rhs0), out);
         };
 
         // ---- points per pass: the knob, else what fits the memory budget; never more than the largest band needs

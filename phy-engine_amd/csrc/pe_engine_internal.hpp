@@ -10,7 +10,7 @@
 //   pe_engine_ac.cpp          pe_hip_analyze_ac / pe_hip_get_solution_ac, pe_hip_analyze_ac_sweep / pe_hip_get_ac_sweep, pe_hip_analyze_noise / pe_hip_get_noise*,
 //                             pe_hip_analyze_sens / pe_hip_get_sens*, pe_hip_analyze_net / pe_hip_get_net*, pe_hip_analyze_pz / pe_hip_get_pz*; the helpers of every stored result (KeptRows, stored_window)
 //   pe_engine_seam.cpp        pe_hip_solve_csr_complex (the complex twin of the solver seam)
-//   pe_sweep.cpp              pe_hip_sweep_*: the multi-device handle (uses EnginePtr and engine_build only; everything else through the C ABI)
+//   pe_sweep.cpp              pe_hip_sweep_*: the multi-device handle (uses EnginePtr, engine_build and set_symbolic_reference only; everything else through the C ABI)
 #pragma once
 // (the helpers below are shared between the engine's translation units only: not exported from libpe_hip.so)
 #define PE_ENG_HIDDEN __attribute__((visibility("hidden")))
@@ -529,6 +529,10 @@ struct pe_hip_engine
     } ops;
     long long param_epoch{};  // bumped by whatever changes hc's parameters, the options or the knobs (the DC sweep engine is rebuilt after it)
     std::vector<double> sym_values_override;  // representative |A| values for the row matching (AC engine)
+    // A shard of a multi-device sweep (pe_sweep.cpp): the circuit of the SWEEP's first instance, batch 1.  The static pivot order is
+    // matched on its values instead of this engine's own instance 0, so that an instance's result does not depend on which device held
+    // it (with per-instance switch states the two orders differ, and next to r_open = 1e12 the rounding differs visibly).  Empty: hc.
+    std::unique_ptr<pe::HostCircuit> sym_ref;
     // The engine holds the real-equivalent form of a circuit's complex AC system (the AC engine and its sweep engine; set once, where they
     // are built): every analysis of it keeps the greedy row matching (pe_symbolic.cpp).  Rows i and n + i of such a system carry the two
     // halves of the same complex entries, equal in magnitude; a matching that maximises magnitudes row by row is free to take the halves of
@@ -628,6 +632,8 @@ namespace pe_eng PE_ENG_HIDDEN
     int analyze_fitting(pe_hip_engine* h, int batch, int geometry_rows, int n, int const* rp, int const* ci, double const* vals, pe::Symbolic& S,
                         pe::SymbolicOptions& so, std::vector<char> const* dyn_slots = nullptr, std::vector<char> const* dyn_rows = nullptr);
     int ensure_symbolic(pe_hip_engine* h, bool tr, double dt);
+    // after pe_hip_load_circuit of a shard: `tables` as the whole sweep gave them (batched blocks starting at the sweep's instance 0)
+    int set_symbolic_reference(pe_hip_engine* h, int n_nodes, int n_branches, int n_tables, pe_hip_device_table const* tables);
     // the solve + residual check + refinement both solver seams share (pe_engine_seam.cpp)
     bool all_finite(double const* x, size_t n);
     int seam_solve_refined(pe_hip_engine* h, pe::DevView const& V, double* xacc, double* b0, double* d_worst, double refine_above, pe_hip_timings& tm,

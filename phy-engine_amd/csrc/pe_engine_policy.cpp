@@ -458,7 +458,7 @@ namespace pe_eng PE_ENG_HIDDEN
         if(!h->sym_values_override.empty()) av = h->sym_values_override;
         else
         {
-            pe::estimate_values(h->hc, tr, dt, h->opt.g_min, r_open_of(h), av);
+            pe::estimate_values(h->sym_ref ? *h->sym_ref : h->hc, tr, dt, h->opt.g_min, r_open_of(h), av);
             // test knob: a pivot matching that cannot see magnitudes (every structural entry weighs 1) -- the deliberately bad
             // static order the residual safety net is tested against; a re-match on an instance's own values is not affected
             if(char const* k = std::getenv("PHY_ENGINE_HIP_TEST_BLIND_MATCH"); k && *k == '1') std::fill(av.begin(), av.end(), 1.0);

@@ -15,7 +15,7 @@
 
 #include "../../include/pe_hip.h"
 #include "pe_circuit.hpp"          // gen_ncol: parameter columns of the generic device kinds
-#include "pe_engine_internal.hpp"  // EnginePtr, engine_build: nothing else of the engine object is used here
+#include "pe_engine_internal.hpp"  // EnginePtr, engine_build, set_symbolic_reference: nothing else of the engine object is used here
 
 struct pe_hip_sweep
 {
@@ -172,7 +172,10 @@ int pe_hip_sweep_load_circuit(pe_hip_sweep* s, int n_nodes, int n_branches, int 
                                        std::vector<pe_hip_device_table> t(tables, tables + n_tables);
                                        for(auto& q: t)
                                            if(q.params_batched && q.params) q.params += static_cast<size_t>(s->lo[g]) * q.count * param_columns(q.kind);
-                                       return pe_hip_load_circuit(s->eng[g].get(), n_nodes, n_branches, s->hi[g] - s->lo[g], n_tables, t.data());
+                                       int const rc = pe_hip_load_circuit(s->eng[g].get(), n_nodes, n_branches, s->hi[g] - s->lo[g], n_tables, t.data());
+                                       // every shard matches its static pivot order on the sweep's first instance, as one engine would
+                                       if(rc != PE_HIP_OK || s->lo[g] == 0) return rc;
+                                       return pe_eng::set_symbolic_reference(s->eng[g].get(), n_nodes, n_branches, n_tables, tables);
                                    });
     s->loaded = rc == PE_HIP_OK;
     return rc;

@@ -18,6 +18,14 @@ R, CAP, L, VDC, VAC, IDC, DIODE = 1, 2, 3, 4, 5, 6, 7
 IAC, VCCS, VCVS, CCCS, CCVS, OPAMP, XFMR, SWITCH, VGEN, COUPLED_L = 8, 9, 10, 11, 12, 13, 14, 15, 16, 17
 NMOS, PMOS, BJT_NPN, BJT_PNP, RELAY, XFMR_CT = 18, 19, 20, 21, 22, 23
 DIODE_NPARAM = 11
+VGEN_NPARAM = 8
+# parameter columns of a device table, by the kind names of deck_tables.  The library holds the same counts in the loader and gen_ncol
+# (csrc/pe_circuit.cpp) and in param_columns (csrc/pe_sweep.cpp); tests/param_common.py pins this table to them.
+NCOL = {"R": 1, "C": 1, "L": 1, "VDC": 1, "VAC": 3, "IDC": 1, "D": DIODE_NPARAM, "IAC": 3, "VCCS": 1, "VCVS": 1, "CCCS": 1, "CCVS": 1, "OPAMP": 1,
+        "XFMR": 1, "SW": 1, "VGEN": VGEN_NPARAM, "KL": 3, "NMOS": 3, "PMOS": 3, "NPN": 5, "PNP": 5, "RELAY": 2, "XCT": 1}
+KIND_CODE = {"R": R, "C": CAP, "L": L, "VDC": VDC, "VAC": VAC, "IDC": IDC, "D": DIODE, "IAC": IAC, "VCCS": VCCS, "VCVS": VCVS, "CCCS": CCCS,
+             "CCVS": CCVS, "OPAMP": OPAMP, "XFMR": XFMR, "SW": SWITCH, "VGEN": VGEN, "KL": COUPLED_L, "NMOS": NMOS, "PMOS": PMOS,
+             "NPN": BJT_NPN, "PNP": BJT_PNP, "RELAY": RELAY, "XCT": XFMR_CT}
 MODE_OP, MODE_DC, MODE_TR, MODE_TROP = 0, 1, 4, 5
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_SINGULAR, ERR_NO_CONVERGENCE, ERR_INTERNAL, ERR_INACCURATE = 0, -1, -2, -3, -4, -5, -6
 
@@ -423,8 +431,10 @@ def deck_tables(deck, batch=1, overrides=None, n_drives=0):
     """
     overrides = overrides or {}
     from .deck import NBRANCH, VGEN_LAYOUT
-    names = ("R", "C", "L", "VDC", "VAC", "IDC", "D", "IAC", "VCCS", "VCVS", "CCCS", "CCVS", "OPAMP", "XFMR", "SW", "VGEN", "KL", "NMOS", "PMOS",
-             "NPN", "PNP", "RELAY", "XCT")
+    names = tuple(NCOL)
+    unknown = sorted(set(overrides) - set(names))
+    if unknown:
+        raise ValueError(f"overrides for unknown kinds {unknown}: the tables are {names}")
     groups = {k: {"nodes": [], "branch": [], "par": []} for k in names}
     k = n_drives
     for kind, nodes, par in deck.devices:
@@ -447,9 +457,7 @@ def deck_tables(deck, batch=1, overrides=None, n_drives=0):
         for _ in range(nb):
             g["branch"].append(k)
             k += 1
-    code = {"R": R, "C": CAP, "L": L, "VDC": VDC, "VAC": VAC, "IDC": IDC, "D": DIODE, "IAC": IAC, "VCCS": VCCS, "VCVS": VCVS, "CCCS": CCCS,
-            "CCVS": CCVS, "OPAMP": OPAMP, "XFMR": XFMR, "SW": SWITCH, "VGEN": VGEN, "KL": COUPLED_L, "NMOS": NMOS, "PMOS": PMOS,
-            "NPN": BJT_NPN, "PNP": BJT_PNP, "RELAY": RELAY, "XCT": XFMR_CT}
+    code = KIND_CODE
     tables = []
     for name, g in groups.items():
         if not g["nodes"]:
@@ -458,7 +466,9 @@ def deck_tables(deck, batch=1, overrides=None, n_drives=0):
         branch = np.ascontiguousarray(np.array(g["branch"], dtype=np.int32)) if g["branch"] else None
         if name in overrides:
             par = np.ascontiguousarray(overrides[name], dtype=np.float64)
-            assert par.shape[0] == batch and par.shape[1] == len(nodes)
+            if par.shape != (batch, len(nodes), NCOL[name]):
+                raise ValueError(f"overrides[{name!r}] has shape {par.shape}: the {name} table of this deck and batch is "
+                                 f"[{batch}][{len(nodes)}][{NCOL[name]}]")
             batched = 1
         else:
             par = np.ascontiguousarray(np.array(g["par"], dtype=np.float64))
@@ -1051,7 +1061,10 @@ class Engine(_Probes):
         return out
 
     def update_param(self, kind, index, column, values):
-        v = np.atleast_1d(np.asarray(values, dtype=np.float64))
+        """one value for every instance, or [batch] values (pe_hip_update_param's batched form)"""
+        v = np.ascontiguousarray(np.atleast_1d(values), dtype=np.float64)      # (a column sliced out of a table is strided: the library reads a dense array)
+        if v.shape not in ((1,), (self.batch,)):
+            raise ValueError(f"update_param takes one value or [{self.batch}] values, not an array of shape {v.shape}")
         self._chk(lib().pe_hip_update_param(self._h, kind, index, column, _dp(v), 1 if len(v) > 1 else 0))
 
     def solve_csr(self, n, row_ptr, col_ind, values, b, copy_pattern=True):
@@ -1153,6 +1166,12 @@ class Sweep(_Probes):
     def run(self, dt, nsteps):
         st = RunStats()
         self._chk(lib().pe_hip_sweep_run(self._h, float(dt), int(nsteps), C.byref(st)))
+        return st.asdict()
+
+    def operating_point(self, mode=MODE_OP):
+        """pe_hip_sweep_operating_point: Engine.analyze_dc on every device's engine, statistics summed"""
+        st = RunStats()
+        self._chk(lib().pe_hip_sweep_operating_point(self._h, int(mode), C.byref(st)))
         return st.asdict()
 
     def operating_point_stepping(self, mode=MODE_OP, method=STEP_AUTO, check=True, **control):

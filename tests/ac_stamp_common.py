@@ -35,7 +35,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from device_eval_common import E, U, OracleEngine, Worst, f_sqrt
-from parity_common import pe
+from parity_common import instance_devices, pe      # (instance_devices: the deck's devices with instance b's overridden parameters)
 
 F = pe.ffi
 Deck = pe.deck.Deck
@@ -322,19 +322,6 @@ def ref_stamp(devices, n_nodes, drives, omega, g_min, r_open, nl, arms):
 
 
 # ---- engines ------------------------------------------------------------------------------------------------------------------------------------
-def instance_devices(deck, overrides, b):
-    """the deck's devices with instance b's overridden parameters"""
-    out, seen = [], {}
-    for kind, nodes, par in deck.devices:
-        j = seen.get(kind, 0)
-        seen[kind] = j + 1
-        if overrides and kind in overrides:
-            row = np.asarray(overrides[kind], dtype=float)[b, j]
-            par = tuple(float(v) for v in row[:len(par)]) + tuple(par[len(row):])
-        out.append((kind, nodes, tuple(par)))
-    return out
-
-
 class OracleAc(OracleEngine):
     """oracle/pe_oracle.py behind the Engine methods this module uses: stamp_ac as the float64 second implementation"""
 

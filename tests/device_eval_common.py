@@ -41,7 +41,7 @@ import mpmath as mp
 import numpy as np
 import scipy.sparse as sp
 
-from parity_common import ROOT, pe
+from parity_common import ROOT, instance_deck, pe
 
 mp.mp.prec = 256
 F = pe.ffi
@@ -383,24 +383,7 @@ class OracleEngine:
         self.o, self.last, self.trace = [], [None] * batch, []
         self.status = np.zeros(batch, dtype=np.int32)
         for b in range(batch):
-            d = pe.deck.Deck()
-            d.n_nodes = deck.n_nodes
-            seen = {}
-            for kind, nodes, par in deck.devices:
-                key = "VGEN" if kind in pe.deck.VGEN_LAYOUT else kind
-                j = seen.get(key, 0)
-                seen[key] = j + 1
-                if overrides and key in overrides:
-                    row = np.asarray(overrides[key], dtype=float)[b, j]
-                    par = list(par)
-                    if key == "VGEN":
-                        for col, q in enumerate(pe.deck.VGEN_LAYOUT[kind][1]):
-                            if q >= 0:
-                                par[q] = float(row[1 + col])
-                    else:
-                        par[:len(row)] = [float(v) for v in row]
-                d.devices.append((kind, nodes, tuple(par)))
-            o = mod.Oracle(d)
+            o = mod.Oracle(instance_deck(deck, overrides, b))
             o.prepare()      # at reset x is zero: Ud_last = 0
             self.o.append(o)
 

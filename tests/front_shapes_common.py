@@ -23,6 +23,7 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
+import parity_common
 from parity_common import pe
 
 LIN = (1e-9, 1e-7)          # the project's linear tolerance (tests/test_gpu_parity.py)
@@ -108,12 +109,7 @@ def resistor_table(deck, seed, batch, repeat=None):
 
 def instance_deck(deck, r_values):
     """the deck of one instance: `deck` with its resistors at r_values (in deck order)"""
-    out = pe.deck.Deck()
-    out.n_nodes = deck.n_nodes
-    it = iter(np.asarray(r_values, dtype=float).reshape(-1))
-    for kind, nodes, par in deck.devices:
-        out.add(kind, nodes, *((next(it),) + tuple(par[1:]) if kind == "R" else par))
-    return out
+    return parity_common.instance_deck(deck, {"R": np.asarray(r_values, dtype=float).reshape(1, -1, 1)}, 0)
 
 
 # ---- reference ------------------------------------------------------------------------------------------------------------------------

@@ -117,6 +117,37 @@ def adversarial_pivot_sweep():
     return d0, d1, {"R": rr, "SW": sw}
 
 
+def instance_devices(deck, overrides, b):
+    """the deck's devices with instance b's parameters of the per-instance tables `overrides` ({table name of ffi.deck_tables:
+    [B][count][ncol]}; count runs over the kind's devices in deck order, those with an unconnected pin included).  A generator's row is the
+    VGEN table's (type, Vh, Vl, freq, duty, phase, tr, tf): the columns its deck line has are taken, the type stays.  A row longer than the
+    deck's parameter tuple (the diode's tt_in_tr) gives its leading columns; a shorter one leaves the rest."""
+    out, seen = [], {}
+    for kind, nodes, par in deck.devices:
+        key = "VGEN" if kind in pe.deck.VGEN_LAYOUT else kind
+        j = seen.get(key, 0)
+        seen[key] = j + 1
+        if overrides and key in overrides:
+            row = np.asarray(overrides[key], dtype=float)[b, j]
+            if key == "VGEN":
+                par = list(par)
+                for col, q in enumerate(pe.deck.VGEN_LAYOUT[kind][1]):
+                    if q >= 0:
+                        par[q] = float(row[1 + col])
+            else:
+                par = tuple(float(v) for v in row[:len(par)]) + tuple(par[len(row):])
+        out.append((kind, nodes, tuple(par)))
+    return out
+
+
+def instance_deck(deck, overrides, b):
+    """a plain deck that carries instance b's parameters (instance_devices); topology, order and unconnected pins as in `deck`"""
+    out = pe.deck.Deck()
+    out.n_nodes = deck.n_nodes
+    out.devices = instance_devices(deck, overrides, b)
+    return out
+
+
 def make(*args):
     """`make <args>` under an exclusive lock: the test modules build shared artefacts (tests/emu libraries, tests/cpp programs) from
     their fixtures, and under pytest-xdist several workers reach those fixtures at once -- two makes rebuilding the same library is how
