@@ -602,55 +602,92 @@ namespace pe
                 std::sort(s.begin(), s.end());
             }
         }
-    }  // namespace
 
-    void build_quad_plan(Symbolic& S, int lds_doubles);
-
-    bool analyze(int n, int const* rp, int const* ci, double const* vals, SymbolicOptions const& opt, Symbolic& S)
-    {
-        S = Symbolic{};
-        S.n = n;
-        S.nnzA = rp[n];
-        if(n == 0) return true;
-
-        ivec rmatch;
-        if(!match_rows(n, rp, ci, vals, opt, rmatch, S.n_row_swaps))
+        // postorder of a forest (children before parents): the roots in the given order, the children of a node in the order of kids[]
+        ivec postorder(std::vector<ivec> const& kids, ivec const& roots)
         {
-            S.structurally_singular = true;
-            S.error = "structurally singular matrix (no zero-free diagonal exists)";
-            return false;
+            ivec post, stack, next(kids.size(), 0);
+            post.reserve(kids.size());
+            for(int r: roots)
+            {
+                stack.push_back(r);
+                while(!stack.empty())
+                {
+                    int const v = stack.back();
+                    if(next[v] < static_cast<int>(kids[v].size())) stack.push_back(kids[v][next[v]++]);
+                    else
+                    {
+                        post.push_back(v);
+                        stack.pop_back();
+                    }
+                }
+            }
+            return post;
         }
 
-        ivec gp, gi;
-        sym_graph(n, rp, ci, rmatch, gp, gi);
+        // ====================================================================================
+        // The phases of analyze(), in the order they run (numbered as in pe_symbolic.hpp).  A phase takes what it reads by const reference
+        // and returns what it makes; the tables of the plan go straight into the Symbolic.  One that can fail leaves its message in
+        // `error`, or in S.error where it fills the Symbolic.
+        // ====================================================================================
 
-        ivec q;
+        // cost model of a front, for the cuts and balances of the schedule: fixed work + the dense elimination
+        double front_cost(int p, int u)
         {
-            Dissector D(n, gp, gi, std::max(2, opt.nd_leaf));
+            double const m = p + u;
+            return 400.0 + m * m * (2.0 + p);
+        }
+        // arena doubles of a front's slot: the u x u update matrix followed by the u-vector of the forward substitution
+        long long slot_doubles(int u) { return static_cast<long long>(u) * (u + 1); }
+
+        // ---------------- phase 1: row matching, graph, nested dissection.  (The seam of the ordering: another fill-reducing ordering, or a
+        // choice between several, changes this function only.)
+        struct Ordering
+        {
+            ivec rmatch;  // unknown j <- equation rmatch[j]
+            ivec gp, gi;  // adjacency of pattern(A' + A'^T)
+            ivec q;       // fill-reducing symmetric ordering: position k holds unknown q[k]
+            int swaps{};
+            bool singular{};
+        };
+        Ordering fill_reducing_order(int n, int const* rp, int const* ci, double const* vals, SymbolicOptions const& opt, std::string& error)
+        {
+            Ordering o;
+            if(!match_rows(n, rp, ci, vals, opt, o.rmatch, o.swaps))
+            {
+                o.singular = true;
+                error = "structurally singular matrix (no zero-free diagonal exists)";
+                return o;
+            }
+            sym_graph(n, rp, ci, o.rmatch, o.gp, o.gi);
+            Dissector D(n, o.gp, o.gi, std::max(2, opt.nd_leaf));
             ivec all(n);
             std::iota(all.begin(), all.end(), 0);
             D.run(std::move(all));
-            q = std::move(D.order);
-        }
-        if(static_cast<int>(q.size()) != n)
-        {
-            S.error = "internal: ordering lost vertices";
-            return false;
+            o.q = std::move(D.order);
+            if(static_cast<int>(o.q.size()) != n) error = "internal: ordering lost vertices";
+            return o;
         }
 
-        // ---------------- elimination tree + column structures of an ordering (optionally re-postordered)
-        std::vector<ivec> st;
-        ivec parent;
-        auto compute_tree = [&](ivec& ord, bool repostorder)
+        // ---------------- phase 2: elimination tree + column structures of an ordering.  `repostorder`: q is then replaced by a postorder
+        // of its tree, children sorted by structure size ascending (largest last => mergeable with the parent), and the tree is that of the new q
+        struct Tree
         {
+            ivec parent;           // elimination tree, -1 for roots
+            std::vector<ivec> st;  // per column: its rows below the diagonal, ascending
+        };
+        Tree column_tree(ivec const& gp, ivec const& gi, ivec& q, bool repostorder)
+        {
+            int const n = static_cast<int>(q.size());
+            Tree t;
             for(int pass = 0; pass < 2; ++pass)
             {
                 ivec qinv(n);
-                for(int k = 0; k < n; ++k) qinv[ord[k]] = k;
+                for(int k = 0; k < n; ++k) qinv[q[k]] = k;
                 std::vector<ivec> lower(n), upper(n);
                 for(int k = 0; k < n; ++k)
                 {
-                    int const v = ord[k];
+                    int const v = q[k];
                     for(int e = gp[v]; e < gp[v + 1]; ++e)
                     {
                         int const l = qinv[gi[e]];
@@ -659,76 +696,70 @@ namespace pe
                     }
                     std::sort(upper[k].begin(), upper[k].end());
                 }
-                etree_of(n, lower, parent);
-                col_structs(n, upper, parent, st);
+                etree_of(n, lower, t.parent);
+                col_structs(n, upper, t.parent, t.st);
                 if(pass == 1 || !repostorder) break;
-                // postorder, children sorted by structure size ascending (largest last => mergeable with the parent)
                 std::vector<ivec> kids(n);
                 ivec roots;
-                for(int j = 0; j < n; ++j) (parent[j] >= 0 ? kids[parent[j]] : roots).push_back(j);
-                auto by_size = [&](int a, int b) { return st[a].size() != st[b].size() ? st[a].size() < st[b].size() : a < b; };
+                for(int j = 0; j < n; ++j) (t.parent[j] >= 0 ? kids[t.parent[j]] : roots).push_back(j);
+                auto by_size = [&t](int a, int b) { return t.st[a].size() != t.st[b].size() ? t.st[a].size() < t.st[b].size() : a < b; };
                 for(auto& kv: kids) std::sort(kv.begin(), kv.end(), by_size);
-                ivec post;
-                post.reserve(n);
-                ivec stack, itx(n, 0);
-                for(int r: roots)
-                {
-                    stack.push_back(r);
-                    while(!stack.empty())
-                    {
-                        int const v = stack.back();
-                        if(itx[v] < static_cast<int>(kids[v].size())) stack.push_back(kids[v][itx[v]++]);
-                        else
-                        {
-                            post.push_back(v);
-                            stack.pop_back();
-                        }
-                    }
-                }
+                ivec const post = postorder(kids, roots);
                 ivec q2(n);
-                for(int k = 0; k < n; ++k) q2[k] = ord[post[k]];
-                ord.swap(q2);
+                for(int k = 0; k < n; ++k) q2[k] = q[post[k]];
+                q.swap(q2);
             }
-        };
-        compute_tree(q, true);
-        for(int j = 0; j < n; ++j) S.nnz_LU += 2LL * static_cast<long long>(st[j].size()) + 1;
+            return t;
+        }
 
-        // ---------------- supernodes: fundamental runs, then relaxed merging of last children
+        // The top class of a run of columns (second pass: SymbolicOptions::big_unknowns; q maps a column to its unknown): a run made of
+        // marked unknowns only forms fronts that own a CU's LDS -- more pivots, a larger panel budget, never a wave front
+        struct TopClass
+        {
+            SymbolicOptions const& opt;
+            ivec const& q;
+            bool has_big;
+            TopClass(SymbolicOptions const& opt_, ivec const& q_)
+                : opt(opt_), q(q_), has_big(opt_.big_unknowns && opt_.big_unknowns->size() == q_.size() && opt_.panel_doubles_top > 0)
+            {
+            }
+            int of(int c0, int c1) const  // 0: ordinary, 1: a CU's whole LDS, 2: half of it (the smallest share among its unknowns)
+            {
+                if(!has_big) return 0;
+                int cls = 1;
+                for(int c = c0; c < c1; ++c)
+                {
+                    int const k = (*opt.big_unknowns)[q[c]];
+                    if(k == 0) return 0;
+                    cls = std::max(cls, k);
+                }
+                return cls;
+            }
+            bool big(int c0, int c1) const { return of(c0, c1) != 0; }
+            int pivots_max(int cls) const { return cls != 0 ? std::max(opt.max_pivots, opt.max_pivots_top) : opt.max_pivots; }
+            long long panel_budget(int cls) const { return std::max(opt.panel_doubles, cls == 1 ? opt.panel_doubles_top : (cls == 2 ? opt.panel_doubles_mid : 0)); }
+        };
+
+        // ---------------- phase 3: supernodes: fundamental runs, then relaxed merging of last children
         struct SN
         {
-            int c0, c1;         // columns [c0, c1)
-            long long zeros;    // explicit zeros in the L panel (same count in U)
+            int c0, c1;       // columns [c0, c1)
+            long long zeros;  // explicit zeros in the L panel (same count in U)
         };
-        std::vector<SN> sn;
-        auto u_of = [&](SN const& s) { return static_cast<int>(st[s.c1 - 1].size()); };
-        // (second pass: columns whose fronts own a CU's LDS -- SymbolicOptions::big_unknowns; q maps a column to its unknown)
-        bool const has_big = opt.big_unknowns && static_cast<int>(opt.big_unknowns->size()) == n && opt.panel_doubles_top > 0;
-        auto big_class = [&](int c0, int c1)  // 0: ordinary, 1: a CU's whole LDS, 2: half of it
+        // P swallows the supernodes at the end of sn while they are its last children and the explicit zeros stay within the relaxation
+        void merge_last_children(std::vector<SN>& sn, SN& P, Tree const& t, TopClass const& top, SymbolicOptions const& opt)
         {
-            if(!has_big) return 0;
-            int cls = 1;
-            for(int c = c0; c < c1; ++c)
-            {
-                int const k = (*opt.big_unknowns)[q[c]];
-                if(k == 0) return 0;
-                cls = std::max(cls, k);
-            }
-            return cls;
-        };
-        auto big_run = [&](int c0, int c1) { return big_class(c0, c1) != 0; };
-        auto pivots_max = [&](int c0, int c1) { return big_run(c0, c1) ? std::max(opt.max_pivots, opt.max_pivots_top) : opt.max_pivots; };
-        auto try_merge = [&](SN& P)
-        {
+            auto u_of = [&t](SN const& s) { return static_cast<int>(t.st[s.c1 - 1].size()); };
             while(!sn.empty())
             {
                 SN const& C = sn.back();
                 if(C.c1 != P.c0) break;
-                int const pc = parent[C.c1 - 1];
+                int const pc = t.parent[C.c1 - 1];
                 if(pc < P.c0 || pc >= P.c1) break;  // not a child of P
                 int const pC = C.c1 - C.c0, uC = u_of(C);
                 int const pP = P.c1 - P.c0, mP = pP + u_of(P);
                 int const np = pC + pP;
-                if(np > pivots_max(C.c0, P.c1)) break;
+                if(np > top.pivots_max(top.of(C.c0, P.c1))) break;
                 long long const z = C.zeros + P.zeros + static_cast<long long>(pC) * (mP - uC);
                 double const panel = static_cast<double>(np) * (np + u_of(P)) - 0.5 * np * (np - 1);
                 if(np > opt.relax_small && static_cast<double>(z) > opt.relax_zero_frac * panel) break;
@@ -736,26 +767,33 @@ namespace pe
                 P.zeros = z;
                 sn.pop_back();
             }
-        };
+        }
+        std::vector<SN> supernodes(Tree const& t, ivec const& q, SymbolicOptions const& opt)
         {
-            int j = 0;
-            while(j < n)
+            int const n = static_cast<int>(q.size());
+            TopClass const top(opt, q);
+            std::vector<SN> sn;
+            for(int j = 0; j < n;)
             {
                 SN P{j, j + 1, 0};
-                while(P.c1 < n && parent[P.c1 - 1] == P.c1 && st[P.c1 - 1].size() == st[P.c1].size() + 1 && (big_run(P.c0, P.c1 + 1) || (P.c1 - P.c0) < opt.max_pivots)) ++P.c1;  // (second pass: a fundamental run of the top stays ONE group, cut into equal links below)
+                // (second pass: a fundamental run of the top stays ONE group, cut into equal links by split_into_fronts)
+                while(P.c1 < n && t.parent[P.c1 - 1] == P.c1 && t.st[P.c1 - 1].size() == t.st[P.c1].size() + 1 && (top.big(P.c0, P.c1 + 1) || (P.c1 - P.c0) < opt.max_pivots)) ++P.c1;
                 j = P.c1;
-                try_merge(P);
+                merge_last_children(sn, P, t, top, opt);
                 sn.push_back(P);
             }
+            return sn;
         }
 
-        // ---------------- generalised absorption: a parent swallows ANY of its children while the merged front stays
+        // ---------------- phase 4: generalised absorption: a parent swallows ANY of its children while the merged front stays
         // small enough for one wavefront (m <= absorb_m).  The absorbed columns are treated as dense (explicit zeros),
-        // which removes the tiny fronts whose cost on a GPU is pure latency.  Needs a re-permutation so that the
+        // which removes the tiny fronts whose cost on a GPU is pure latency.  Needs a re-permutation of q so that the
         // merged columns are contiguous; fill is unchanged (same elimination tree order within every subtree).
-        std::vector<std::pair<int, int>> groups;  // forced partition [c0, c1) in the NEW order
+        // Returns the forced partition [c0, c1) of the columns in the NEW order.
+        using Groups = std::vector<std::pair<int, int>>;
+        Groups absorb_children(Tree const& t, std::vector<SN> const& sn, ivec& q, SymbolicOptions const& opt, std::string& error)
         {
-            int const ns = static_cast<int>(sn.size());
+            int const n = static_cast<int>(q.size()), ns = static_cast<int>(sn.size());
             ivec col2sn(n);
             for(int i = 0; i < ns; ++i)
                 for(int c = sn[i].c0; c < sn[i].c1; ++c) col2sn[c] = i;
@@ -763,7 +801,7 @@ namespace pe
             std::vector<ivec> kids(ns), members(ns);
             for(int i = 0; i < ns; ++i)
             {
-                auto const& r = st[sn[i].c1 - 1];
+                auto const& r = t.st[sn[i].c1 - 1];
                 if(!r.empty()) par[i] = col2sn[r[0]];
                 gp_[i] = sn[i].c1 - sn[i].c0;
                 gu[i] = static_cast<int>(r.size());
@@ -779,7 +817,7 @@ namespace pe
                 {
                     again = false;
                     ivec cand = kids[P];
-                    std::sort(cand.begin(), cand.end(), [&](int a, int b) { return gp_[a] != gp_[b] ? gp_[a] < gp_[b] : a < b; });
+                    std::sort(cand.begin(), cand.end(), [&gp_](int a, int b) { return gp_[a] != gp_[b] ? gp_[a] < gp_[b] : a < b; });
                     for(int C: cand)
                     {
                         if(gp_[P] + gp_[C] + gu[P] > opt.absorb_m || gp_[P] + gp_[C] > opt.wave_p) continue;
@@ -799,128 +837,82 @@ namespace pe
                     }
                 }
             }
-            // new column order: postorder DFS of the merged tree; a node emits its member supernodes in ascending order
+            // new column order: postorder of the merged tree, children ascending; a node emits its member supernodes in ascending order
+            ivec roots;
+            for(int r = 0; r < ns; ++r)
+                if(par[r] < 0 && !absorbed[r]) roots.push_back(r);
+            for(auto& k: kids) std::sort(k.begin(), k.end());
+            Groups groups;
             ivec q2;
             q2.reserve(n);
-            ivec stack, itx(ns, 0);
-            for(int r = 0; r < ns; ++r)
+            for(int v: postorder(kids, roots))
             {
-                if(par[r] >= 0 || absorbed[r]) continue;
-                stack.push_back(r);
-                while(!stack.empty())
-                {
-                    int const v = stack.back();
-                    if(itx[v] == 0) std::sort(kids[v].begin(), kids[v].end());
-                    if(itx[v] < static_cast<int>(kids[v].size())) stack.push_back(kids[v][itx[v]++]);
-                    else
-                    {
-                        std::sort(members[v].begin(), members[v].end());
-                        int const c0 = static_cast<int>(q2.size());
-                        for(int mbr: members[v])
-                            for(int c = sn[mbr].c0; c < sn[mbr].c1; ++c) q2.push_back(q[c]);
-                        groups.push_back({c0, static_cast<int>(q2.size())});
-                        stack.pop_back();
-                    }
-                }
+                std::sort(members[v].begin(), members[v].end());
+                int const c0 = static_cast<int>(q2.size());
+                for(int mbr: members[v])
+                    for(int c = sn[mbr].c0; c < sn[mbr].c1; ++c) q2.push_back(q[c]);
+                groups.push_back({c0, static_cast<int>(q2.size())});
             }
-            if(static_cast<int>(q2.size()) != n)
-            {
-                S.error = "internal: absorption lost columns";
-                return false;
-            }
-            q.swap(q2);
+            if(static_cast<int>(q2.size()) != n) error = "internal: absorption lost columns";
+            else
+                q.swap(q2);
+            return groups;
         }
-        compute_tree(q, false);
 
-        // ---------------- fronts = forced groups, split to respect the wave / LDS-panel limits
+        // ---------------- phase 5: fronts = forced groups, split to respect the wave / LDS-panel limits
         struct FR
         {
             int c0, c1, g1;  // pivots [c0, c1); the group ends at g1 (rows = [c1, g1) + structure of column g1-1)
         };
-        std::vector<FR> fr;
-        for(auto const& [c0, c1]: groups)
+        std::vector<FR> split_into_fronts(Tree const& t, Groups const& groups, ivec const& q, SymbolicOptions const& opt, std::string& error)
         {
-            int const ug = static_cast<int>(st[c1 - 1].size());
-            int a = c0;
-            while(a < c1)
+            TopClass const top(opt, q);
+            std::vector<FR> fr;
+            for(auto const& [c0, c1]: groups)
             {
-                int const rest = c1 - a;
-                int const mfull = rest + ug;
-                int b;
-                if(mfull <= opt.wave_m && !big_run(c0, c1)) b = a + std::min(rest, opt.wave_p);  // (a front of the top is never a wave front)
-                else if(opt.quad_mid && mfull <= 64)
-                    b = a + std::min(rest, 16);  // a candidate MID front of the lane-group kernels: <= 16 pivots (one row set)
-                else
+                int const ug = static_cast<int>(t.st[c1 - 1].size());
+                int const cls = top.of(c0, c1);  // (second pass: a front of the top that owns a CU's LDS, or half of it)
+                bool const big = cls != 0;
+                for(int a = c0; a < c1;)
                 {
-                    int const cls = big_class(c0, c1);  // (second pass: a front of the top that owns a CU's LDS, or half of it)
-                    bool const big = cls != 0;
-                    long long const budget = std::max(opt.panel_doubles, cls == 1 ? opt.panel_doubles_top : (cls == 2 ? opt.panel_doubles_mid : 0));
-                    int pbest = 0;
-                    for(int pp = std::min(rest, big ? std::max(opt.max_pivots, opt.max_pivots_top) : opt.max_pivots); pp >= 1; --pp)
+                    int const rest = c1 - a;
+                    int const mfull = rest + ug;
+                    int b;
+                    if(mfull <= opt.wave_m && !big) b = a + std::min(rest, opt.wave_p);  // (a front of the top is never a wave front)
+                    else if(opt.quad_mid && mfull <= 64)
+                        b = a + std::min(rest, 16);  // a candidate MID front of the lane-group kernels: <= 16 pivots (one row set)
+                    else
                     {
-                        long long const uch = (rest - pp) + ug, mch = pp + uch;
-                        if(static_cast<long long>(pe_ld(static_cast<int>(mch))) * pp + static_cast<long long>(pe_ld(pp)) * uch <= budget)
+                        long long const budget = top.panel_budget(cls);
+                        int pbest = 0;
+                        for(int pp = std::min(rest, top.pivots_max(cls)); pp >= 1; --pp)
                         {
-                            pbest = pp;
-                            break;
+                            long long const uch = (rest - pp) + ug, mch = pp + uch;
+                            if(static_cast<long long>(pe_ld(static_cast<int>(mch))) * pp + static_cast<long long>(pe_ld(pp)) * uch <= budget)
+                            {
+                                pbest = pp;
+                                break;
+                            }
                         }
+                        if(pbest == 0)
+                        {
+                            error = "front too large for the LDS panels";
+                            return fr;
+                        }
+                        // (links of equal length instead of full ones + a remnant of two or three pivots: the panel need grows with the
+                        //  pivots of a link, so the shorter link fits where the longest did)
+                        if(big) pbest = (rest + (rest + pbest - 1) / pbest - 1) / ((rest + pbest - 1) / pbest);
+                        b = a + pbest;
                     }
-                    if(pbest == 0)
-                    {
-                        S.error = "front too large for the LDS panels";
-                        return false;
-                    }
-                    // (links of equal length instead of full ones + a remnant of two or three pivots: the panel need grows with the
-                    //  pivots of a link, so the shorter link fits where the longest did)
-                    if(big) pbest = (rest + (rest + pbest - 1) / pbest - 1) / ((rest + pbest - 1) / pbest);
-                    b = a + pbest;
+                    fr.push_back({a, b, c1});
+                    a = b;
                 }
-                fr.push_back({a, b, c1});
-                a = b;
             }
+            return fr;
         }
 
-        int const nf = static_cast<int>(fr.size());
-        S.nfronts = nf;
-        S.f_col0.resize(nf);
-        S.f_p.resize(nf);
-        S.f_u.resize(nf);
-        S.f_parent.assign(nf, -1);
-        S.f_rows_ptr.assign(nf + 1, 0);
-        ivec col2front(n);
-        for(int s = 0; s < nf; ++s)
-        {
-            S.f_col0[s] = fr[s].c0;
-            S.f_p[s] = fr[s].c1 - fr[s].c0;
-            S.f_u[s] = (fr[s].g1 - fr[s].c1) + static_cast<int>(st[fr[s].g1 - 1].size());
-            S.f_rows_ptr[s + 1] = S.f_rows_ptr[s] + S.f_u[s];
-            for(int c = fr[s].c0; c < fr[s].c1; ++c) col2front[c] = s;
-            S.nnz_LU_stored += 2LL * S.f_p[s] * S.f_u[s] + static_cast<long long>(S.f_p[s]) * S.f_p[s];
-        }
-        S.f_rows.resize(S.f_rows_ptr[nf]);
-        for(int s = 0; s < nf; ++s)
-        {
-            int* dst = S.f_rows.data() + S.f_rows_ptr[s];
-            for(int c = fr[s].c1; c < fr[s].g1; ++c) *dst++ = c;
-            auto const& r = st[fr[s].g1 - 1];
-            std::copy(r.begin(), r.end(), dst);
-            if(S.f_u[s] > 0) S.f_parent[s] = col2front[S.f_rows[S.f_rows_ptr[s]]];
-            int const m = S.f_p[s] + S.f_u[s];
-            S.max_m = std::max(S.max_m, m);
-            S.max_u = std::max(S.max_u, S.f_u[s]);
-            for(int k = 0; k < S.f_p[s]; ++k)
-            {
-                double const r1 = m - k - 1;
-                S.flops += 2.0 * r1 * r1 + r1;
-            }
-        }
-        if(S.max_m >= 65536)
-        {
-            S.error = "front order exceeds 65535";
-            return false;
-        }
-
-        auto local_of = [&](int s, int t) -> int
+        // local index of permuted row / column t in front s (pivots first, then the update rows), -1 if it is not there
+        int local_of(Symbolic const& S, int s, int t)
         {
             int const c0 = S.f_col0[s], p = S.f_p[s];
             if(t < c0 + p) return t - c0;
@@ -928,61 +920,101 @@ namespace pe
             auto it = std::lower_bound(b, e, t);
             if(it == e || *it != t) return -1;
             return p + static_cast<int>(it - b);
-        };
+        }
 
-        // children, relative indices, depth
-        S.f_child_ptr.assign(nf + 1, 0);
-        for(int s = 0; s < nf; ++s)
-            if(S.f_parent[s] >= 0) ++S.f_child_ptr[S.f_parent[s] + 1];
-        for(int s = 0; s < nf; ++s) S.f_child_ptr[s + 1] += S.f_child_ptr[s];
-        S.f_child.resize(S.f_child_ptr[nf]);
+        // ---------------- phase 6: the front tables: pivots, update rows, parents, children, relative maps, depth, statistics
+        struct FrontMaps
         {
+            ivec col2front;  // permuted column -> the front it is a pivot of
+            ivec depth;      // of a front in the assembly tree, roots 1
+        };
+        FrontMaps fill_front_tables(Symbolic& S, Tree const& t, std::vector<FR> const& fr)
+        {
+            int const nf = static_cast<int>(fr.size());
+            FrontMaps fm{ivec(t.st.size()), ivec(nf, 1)};
+            S.nfronts = nf;
+            S.f_col0.resize(nf);
+            S.f_p.resize(nf);
+            S.f_u.resize(nf);
+            S.f_parent.assign(nf, -1);
+            S.f_rows_ptr.assign(nf + 1, 0);
+            for(int s = 0; s < nf; ++s)
+            {
+                S.f_col0[s] = fr[s].c0;
+                S.f_p[s] = fr[s].c1 - fr[s].c0;
+                S.f_u[s] = (fr[s].g1 - fr[s].c1) + static_cast<int>(t.st[fr[s].g1 - 1].size());
+                S.f_rows_ptr[s + 1] = S.f_rows_ptr[s] + S.f_u[s];
+                for(int c = fr[s].c0; c < fr[s].c1; ++c) fm.col2front[c] = s;
+                S.nnz_LU_stored += 2LL * S.f_p[s] * S.f_u[s] + static_cast<long long>(S.f_p[s]) * S.f_p[s];
+            }
+            S.f_rows.resize(S.f_rows_ptr[nf]);
+            for(int s = 0; s < nf; ++s)
+            {
+                int* dst = S.f_rows.data() + S.f_rows_ptr[s];
+                for(int c = fr[s].c1; c < fr[s].g1; ++c) *dst++ = c;
+                auto const& r = t.st[fr[s].g1 - 1];
+                std::copy(r.begin(), r.end(), dst);
+                if(S.f_u[s] > 0) S.f_parent[s] = fm.col2front[S.f_rows[S.f_rows_ptr[s]]];
+                int const m = S.f_p[s] + S.f_u[s];
+                S.max_m = std::max(S.max_m, m);
+                S.max_u = std::max(S.max_u, S.f_u[s]);
+                for(int k = 0; k < S.f_p[s]; ++k)
+                {
+                    double const r1 = m - k - 1;
+                    S.flops += 2.0 * r1 * r1 + r1;
+                }
+            }
+            if(S.max_m >= 65536)
+            {
+                S.error = "front order exceeds 65535";
+                return fm;
+            }
+            // children, relative indices, depth
+            S.f_child_ptr.assign(nf + 1, 0);
+            for(int s = 0; s < nf; ++s)
+                if(S.f_parent[s] >= 0) ++S.f_child_ptr[S.f_parent[s] + 1];
+            for(int s = 0; s < nf; ++s) S.f_child_ptr[s + 1] += S.f_child_ptr[s];
+            S.f_child.resize(S.f_child_ptr[nf]);
             ivec fill(S.f_child_ptr.begin(), S.f_child_ptr.end() - 1);
             for(int s = 0; s < nf; ++s)
                 if(S.f_parent[s] >= 0) S.f_child[fill[S.f_parent[s]]++] = s;
-        }
-        S.f_rel_ptr = S.f_rows_ptr;
-        S.f_rel.assign(S.f_rows.size(), -1);
-        ivec depth(nf, 1);
-        {
+            S.f_rel_ptr = S.f_rows_ptr;
+            S.f_rel.assign(S.f_rows.size(), -1);
             for(int s = nf - 1; s >= 0; --s)
             {
                 int const P = S.f_parent[s];
                 if(P >= 0)
                 {
-                    depth[s] = depth[P] + 1;
+                    fm.depth[s] = fm.depth[P] + 1;
                     if(P <= s)
                     {
                         S.error = "internal: front tree is not in postorder";
-                        return false;
+                        return fm;
                     }
                     for(int a = S.f_rows_ptr[s]; a < S.f_rows_ptr[s + 1]; ++a)
                     {
-                        int const l = local_of(P, S.f_rows[a]);
+                        int const l = local_of(S, P, S.f_rows[a]);
                         if(l < 0)
                         {
                             S.error = "internal: child update row missing from parent front";
-                            return false;
+                            return fm;
                         }
                         S.f_rel[a] = l;
                     }
                 }
-                S.tree_depth = std::max(S.tree_depth, depth[s]);
+                S.tree_depth = std::max(S.tree_depth, fm.depth[s]);
             }
+            return fm;
         }
 
-        // permutations
-        S.col_src = q;
-        S.row_src.resize(n);
-        for(int k = 0; k < n; ++k) S.row_src[k] = rmatch[q[k]];
-
-        // assembly lists: A slot e=(i_old, j_old) -> permuted (k, l) -> owner front = front of min(k, l)
+        // ---------------- phase 7: the own entries of every front: A slot e = (i_old, j_old) -> permuted (k, l) -> owner front = front of min(k, l)
+        void own_entries(Symbolic& S, int const* rp, int const* ci, ivec const& col2front)
         {
+            int const n = S.n, nf = S.nfronts, nnz = rp[n];
             ivec qinv(n), eq2k(n);
-            for(int k = 0; k < n; ++k) qinv[q[k]] = k;
+            for(int k = 0; k < n; ++k) qinv[S.col_src[k]] = k;
             for(int k = 0; k < n; ++k) eq2k[S.row_src[k]] = k;
             S.f_asm_ptr.assign(nf + 1, 0);
-            int const nnz = rp[n];
             ivec owner(nnz), pos(nnz);
             for(int i = 0; i < n; ++i)
             {
@@ -991,11 +1023,11 @@ namespace pe
                 {
                     int const l = qinv[ci[e]];
                     int const s = col2front[std::min(k, l)];
-                    int const r = local_of(s, k), c = local_of(s, l);
+                    int const r = local_of(S, s, k), c = local_of(S, s, l);
                     if(r < 0 || c < 0)
                     {
                         S.error = "internal: matrix entry outside its front";
-                        return false;
+                        return;
                     }
                     owner[e] = s;
                     pos[e] = (r << 16) | c;
@@ -1014,10 +1046,12 @@ namespace pe
             }
         }
 
-        // static fronts (pe_symbolic.hpp): own x-dependent entry / pivot row, or a dynamic child (postorder: children come first)
-        S.f_static.assign(nf, 0);
-        if(opt.dyn_slots && opt.dyn_rows && static_cast<int>(opt.dyn_slots->size()) == rp[n] && static_cast<int>(opt.dyn_rows->size()) == n)
+        // ---------------- phase 8: static fronts (pe_symbolic.hpp): own x-dependent entry / pivot row, or a dynamic child (postorder: children come first)
+        void classify_static(Symbolic& S, SymbolicOptions const& opt, int nnz)
         {
+            int const nf = S.nfronts;
+            S.f_static.assign(nf, 0);
+            if(!(opt.dyn_slots && opt.dyn_rows && static_cast<int>(opt.dyn_slots->size()) == nnz && static_cast<int>(opt.dyn_rows->size()) == S.n)) return;
             std::vector<char> dynamic(nf, 0);
             for(int s = 0; s < nf; ++s)
             {
@@ -1028,7 +1062,7 @@ namespace pe
             }
         }
 
-        // ---------------- schedule
+        // ---------------- phase 9: the schedule.
         // Two nested proportional cuts of the assembly tree (from the roots downwards):
         //   level 1 (only when n_parts > 1, the multi-workgroup mode for one or few instances): subtrees costing at most
         //           total / (n_parts * part_cut) become PART subtrees, spread over n_parts workgroups; what stays above is
@@ -1037,58 +1071,64 @@ namespace pe
         //           part_total / (W * cut_factor) become WAVE subtrees, spread over the W wavefronts of the workgroup;
         //           the rest of the part is COOPERATIVE (whole workgroup).
         // Near a root there is no tree parallelism left, so the upper fronts are always handled by the wider executor.
-        int const W = std::max(1, opt.n_waves);
-        int const K = std::max(1, opt.n_parts);
-        S.n_parts = K;
-        S.f_kind.assign(nf, 1);
-        ivec part_of(nf, K > 1 ? -1 : 0);
-        std::vector<double> cost(nf, 0.0), sub(nf, 0.0);
-        std::vector<char> fits(nf, 1), fits_mid(nf, opt.quad_mid ? 1 : 0), fits_quad(nf, opt.quad ? 1 : 0);
-        double total = 0.0;
-        for(int s = 0; s < nf; ++s)
+        struct SubtreeCosts
         {
-            double const m = S.f_p[s] + S.f_u[s];
-            cost[s] = 400.0 + m * m * (2.0 + S.f_p[s]);
-            total += cost[s];
-            fits[s] = fits[s] && m <= opt.wave_m && S.f_p[s] <= opt.wave_p;
-            // lane-group kernel (pe_quad.hpp): two row sets of 16, pivots in the first, one-byte entry indices
-            // lane-group kernel (pe_quad.hpp): two row sets of 16, pivots in the first, one-byte entry indices -- a wave front is a QUAD front
-            // when its whole subtree satisfies this; the other wave fronts stay with the per-instance wave phase of factor_part
-            fits_quad[s] = fits_quad[s] && m <= 32 && S.f_p[s] <= 16 && S.f_asm_ptr[s + 1] - S.f_asm_ptr[s] <= 255 && S.f_child_ptr[s + 1] - S.f_child_ptr[s] <= 16;
-            if(fits[s] && opt.wave_slot > 0)
-            {
-                // (the slot also holds the right-hand-side column: m doubles behind the image / the panels)
-                long long const mm = S.f_p[s] + S.f_u[s], whole = (pe_ld(static_cast<int>(mm)) + 1LL) * mm,
-                                panel = static_cast<long long>(pe_ld(static_cast<int>(mm))) * S.f_p[s] + static_cast<long long>(pe_ld(S.f_p[s])) * S.f_u[s] + mm;
-                if(whole > opt.wave_slot && panel > opt.wave_slot) fits[s] = 0;
-            }
-            // MID class of the lane-group kernels: order <= 64 (four row sets), otherwise the wave fronts' limits, whole subtree
-            fits_mid[s] = fits_mid[s] && m <= 64 && S.f_p[s] <= 16 && S.f_asm_ptr[s + 1] - S.f_asm_ptr[s] <= 255 && S.f_child_ptr[s + 1] - S.f_child_ptr[s] <= 16;
-            sub[s] += cost[s];
-            int const P = S.f_parent[s];
-            if(P >= 0)
-            {
-                sub[P] += sub[s];
-                if(!fits[s]) fits[P] = 0;
-                if(!fits_mid[s]) fits_mid[P] = 0;
-                if(!fits_quad[s]) fits_quad[P] = 0;
-            }
-        }
-        auto mark_subtree = [&](int root, auto&& fn)
-        {
-            ivec st2{root};
-            while(!st2.empty())
-            {
-                int const t = st2.back();
-                st2.pop_back();
-                fn(t);
-                for(int a = S.f_child_ptr[t]; a < S.f_child_ptr[t + 1]; ++a) st2.push_back(S.f_child[a]);
-            }
+            std::vector<double> cost, sub;           // of a front (front_cost) / of its whole subtree
+            std::vector<char> fits, fits_mid, fits_quad;  // the whole subtree of a front satisfies the limits of the wave / MID / quad class
+            double total{};
         };
-        std::vector<double> part_total(K, 0.0);
-        if(K > 1)
+        SubtreeCosts subtree_costs(Symbolic const& S, SymbolicOptions const& opt)
         {
-            double const limit1 = total / (static_cast<double>(K) * opt.part_cut);
+            int const nf = S.nfronts;
+            SubtreeCosts c{std::vector<double>(nf, 0.0), std::vector<double>(nf, 0.0), std::vector<char>(nf, 1), std::vector<char>(nf, opt.quad_mid ? 1 : 0),
+                           std::vector<char>(nf, opt.quad ? 1 : 0), 0.0};
+            for(int s = 0; s < nf; ++s)
+            {
+                int const p = S.f_p[s], u = S.f_u[s], m = p + u;
+                c.cost[s] = front_cost(p, u);
+                c.total += c.cost[s];
+                c.fits[s] = c.fits[s] && m <= opt.wave_m && p <= opt.wave_p;
+                // lane-group kernel (pe_quad.hpp): two row sets of 16, pivots in the first, one-byte entry indices -- a wave front is a QUAD front
+                // when its whole subtree satisfies this; the other wave fronts stay with the per-instance wave phase of factor_part
+                bool const lane_group = p <= 16 && S.f_asm_ptr[s + 1] - S.f_asm_ptr[s] <= 255 && S.f_child_ptr[s + 1] - S.f_child_ptr[s] <= 16;
+                c.fits_quad[s] = c.fits_quad[s] && m <= 32 && lane_group;
+                if(c.fits[s] && opt.wave_slot > 0)
+                {
+                    // (the slot also holds the right-hand-side column: m doubles behind the image / the panels)
+                    long long const whole = (pe_ld(m) + 1LL) * m, panel = static_cast<long long>(pe_ld(m)) * p + static_cast<long long>(pe_ld(p)) * u + m;
+                    if(whole > opt.wave_slot && panel > opt.wave_slot) c.fits[s] = 0;
+                }
+                // MID class of the lane-group kernels: order <= 64 (four row sets), otherwise the wave fronts' limits, whole subtree
+                c.fits_mid[s] = c.fits_mid[s] && m <= 64 && lane_group;
+                c.sub[s] += c.cost[s];
+                int const P = S.f_parent[s];
+                if(P >= 0)
+                {
+                    c.sub[P] += c.sub[s];
+                    if(!c.fits[s]) c.fits[P] = 0;
+                    if(!c.fits_mid[s]) c.fits_mid[P] = 0;
+                    if(!c.fits_quad[s]) c.fits_quad[P] = 0;
+                }
+            }
+            return c;
+        }
+
+        // level 1: part_of[s] = part of front s (-1: top), parts numbered in descending cost; part_total[q] = cost of part q
+        struct Parts
+        {
+            ivec part_of;
+            std::vector<double> part_total;
+        };
+        Parts cut_parts(Symbolic const& S, SymbolicOptions const& opt, SubtreeCosts const& c, int K)
+        {
+            int const nf = S.nfronts;
+            Parts P{ivec(nf, K > 1 ? -1 : 0), std::vector<double>(K, 0.0)};
+            if(K == 1)
+            {
+                P.part_total[0] = c.total;
+                return P;
+            }
+            double const limit1 = c.total / (static_cast<double>(K) * opt.part_cut);
             ivec stack, sroots;
             for(int s = 0; s < nf; ++s)
                 if(S.f_parent[s] < 0) stack.push_back(s);
@@ -1096,58 +1136,48 @@ namespace pe
             {
                 int const s = stack.back();
                 stack.pop_back();
-                if(sub[s] <= limit1) sroots.push_back(s);
+                if(c.sub[s] <= limit1) sroots.push_back(s);
                 else
                     for(int a = S.f_child_ptr[s]; a < S.f_child_ptr[s + 1]; ++a) stack.push_back(S.f_child[a]);
             }
-            std::sort(sroots.begin(), sroots.end(), [&](int a, int b) { return sub[a] != sub[b] ? sub[a] > sub[b] : a < b; });
+            std::sort(sroots.begin(), sroots.end(), [&c](int a, int b) { return c.sub[a] != c.sub[b] ? c.sub[a] > c.sub[b] : a < b; });
             for(int r: sroots)
             {
-                int const pidx = static_cast<int>(std::min_element(part_total.begin(), part_total.end()) - part_total.begin());
-                part_total[pidx] += sub[r];
-                mark_subtree(r, [&](int t) { part_of[t] = pidx; });
+                int const pidx = static_cast<int>(std::min_element(P.part_total.begin(), P.part_total.end()) - P.part_total.begin());
+                P.part_total[pidx] += c.sub[r];
+                for(ivec todo{r}; !todo.empty();)  // the whole subtree of r
+                {
+                    int const t = todo.back();
+                    todo.pop_back();
+                    P.part_of[t] = pidx;
+                    for(int a = S.f_child_ptr[t]; a < S.f_child_ptr[t + 1]; ++a) todo.push_back(S.f_child[a]);
+                }
             }
             // parts in descending cost: the launch dispatches workgroups part by part, the cheapest last (shortest tail)
             ivec order(K), rank(K);
             for(int q = 0; q < K; ++q) order[q] = q;
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return part_total[a] > part_total[b]; });
+            std::stable_sort(order.begin(), order.end(), [&P](int a, int b) { return P.part_total[a] > P.part_total[b]; });
             std::vector<double> sorted_total(K);
             for(int q = 0; q < K; ++q)
             {
                 rank[order[q]] = q;
-                sorted_total[q] = part_total[order[q]];
+                sorted_total[q] = P.part_total[order[q]];
             }
-            part_total = sorted_total;
+            P.part_total = sorted_total;
             for(int t = 0; t < nf; ++t)
-                if(part_of[t] >= 0) part_of[t] = rank[part_of[t]];
+                if(P.part_of[t] >= 0) P.part_of[t] = rank[P.part_of[t]];
+            return P;
         }
-        else
-            part_total[0] = total;
-        // level 2
-        for(int s = nf - 1; s >= 0; --s)
+
+        // executors: wave w of part q -> q * (W + 1) + w ; cooperative phase of part q -> q * (W + 1) + W ; top fronts: none (-1).
+        // Also lays out the wavefronts' backward stacks (f_wstack, f_wpar, wave_stack).
+        ivec assign_executors(Symbolic& S, ivec const& part_of, SubtreeCosts const& c, int K, int W)
         {
-            if(part_of[s] < 0)
-            {
-                S.f_kind[s] = 2;
-                continue;
-            }
-            int const P = S.f_parent[s];
-            bool const parent_is_wave = P >= 0 && part_of[P] == part_of[s] && S.f_kind[P] == 0;
-            if(parent_is_wave) S.f_kind[s] = 0;  // inside a wave subtree
-            else
-            {
-                double const limit2 = part_total[part_of[s]] / (opt.cut_factor * W);
-                S.f_kind[s] = (fits[s] && sub[s] <= limit2) ? 0 : (fits_mid[s] ? 3 : 1);
-            }
-        }
-        S.f_quad.assign(nf, 0);
-        for(int s = 0; s < nf; ++s) S.f_quad[s] = (opt.quad && S.f_kind[s] == 0 && fits_quad[s]) ? 1 : 0;
-        // executors: wave w of part q -> q * (W + 1) + w ; cooperative phase of part q -> q * (W + 1) + W ; top fronts: none
-        ivec exec_of(nf, -1), wroot_of(nf, -1);
-        S.f_wstack.assign(nf, 0);
-        S.f_wpar.assign(nf, -1);
-        S.wave_stack = 1;
-        {
+            int const nf = S.nfronts;
+            ivec exec_of(nf, -1), wroot_of(nf, -1);
+            S.f_wstack.assign(nf, 0);
+            S.f_wpar.assign(nf, -1);
+            S.wave_stack = 1;
             // wave subtree roots per part, LPT over the W wavefronts
             std::vector<ivec> wroots(K);
             for(int s = nf - 1; s >= 0; --s)
@@ -1169,7 +1199,7 @@ namespace pe
             for(int s = 0; s < nf; ++s)
             {
                 if(S.f_kind[s] != 0) continue;
-                if(!S.f_quad[s]) sub_nq[s] += cost[s];
+                if(!S.f_quad[s]) sub_nq[s] += c.cost[s];
                 int const P = S.f_parent[s];
                 if(P >= 0 && S.f_kind[P] == 0 && part_of[P] == part_of[s]) sub_nq[P] += sub_nq[s];
             }
@@ -1180,7 +1210,7 @@ namespace pe
                           [&](int a, int b)
                           {
                               if(sub_nq[a] != sub_nq[b]) return sub_nq[a] > sub_nq[b];
-                              return sub[a] != sub[b] ? sub[a] > sub[b] : a < b;
+                              return c.sub[a] != c.sub[b] ? c.sub[a] > c.sub[b] : a < b;
                           });
                 std::vector<double> load(W, 0.0), load_q(W, 0.0);
                 for(int root: r)
@@ -1192,7 +1222,7 @@ namespace pe
                         if(better) w = k;
                     }
                     load[w] += sub_nq[root];
-                    load_q[w] += sub[root] - sub_nq[root];
+                    load_q[w] += c.sub[root] - sub_nq[root];
                     exec_of[root] = q * (W + 1) + w;
                 }
             }
@@ -1202,9 +1232,14 @@ namespace pe
                 else if(S.f_kind[s] == 1 || S.f_kind[s] == 3)
                     exec_of[s] = part_of[s] * (W + 1) + W;
             }
+            return exec_of;
         }
-        // lists (ascending front index = postorder inside every executor)
+
+        // the lists of every executor (ascending front index = postorder inside every executor) -> wave_* / coop_*, and the top levels
+        // (height above the parts) -> top_*
+        std::vector<ivec> executor_lists(Symbolic& S, ivec const& exec_of, int K, int W)
         {
+            int const nf = S.nfronts;
             std::vector<ivec> lists(static_cast<size_t>(K) * (W + 1));
             for(int s = 0; s < nf; ++s)
                 if(exec_of[s] >= 0) lists[exec_of[s]].push_back(s);
@@ -1224,7 +1259,6 @@ namespace pe
                 S.coop_list.insert(S.coop_list.end(), cl.begin(), cl.end());
                 S.coop_ptr[q + 1] = static_cast<int>(S.coop_list.size());
             }
-            // top levels: height above the parts
             ivec h(nf, 0);
             int maxh = 0;
             for(int s = 0; s < nf; ++s)
@@ -1244,8 +1278,50 @@ namespace pe
                     if(S.f_kind[s] == 2 && h[s] == lev) S.top_list.push_back(s);
                 S.top_ptr[lev] = static_cast<int>(S.top_list.size());
             }
+            return lists;
+        }
 
-            // storage offsets: factor panels
+        struct Schedule
+        {
+            ivec exec_of;              // executor of a front (assign_executors), -1 for a top front
+            std::vector<ivec> lists;   // fronts of every executor, in postorder
+        };
+        Schedule schedule(Symbolic& S, SymbolicOptions const& opt)
+        {
+            int const nf = S.nfronts, W = std::max(1, opt.n_waves), K = std::max(1, opt.n_parts);
+            S.n_parts = K;
+            SubtreeCosts const c = subtree_costs(S, opt);
+            Parts const parts = cut_parts(S, opt, c, K);
+            // level 2
+            S.f_kind.assign(nf, 1);
+            for(int s = nf - 1; s >= 0; --s)
+            {
+                if(parts.part_of[s] < 0)
+                {
+                    S.f_kind[s] = 2;
+                    continue;
+                }
+                int const P = S.f_parent[s];
+                bool const parent_is_wave = P >= 0 && parts.part_of[P] == parts.part_of[s] && S.f_kind[P] == 0;
+                if(parent_is_wave) S.f_kind[s] = 0;  // inside a wave subtree
+                else
+                {
+                    double const limit2 = parts.part_total[parts.part_of[s]] / (opt.cut_factor * W);
+                    S.f_kind[s] = (c.fits[s] && c.sub[s] <= limit2) ? 0 : (c.fits_mid[s] ? 3 : 1);
+                }
+            }
+            S.f_quad.assign(nf, 0);
+            for(int s = 0; s < nf; ++s) S.f_quad[s] = (opt.quad && S.f_kind[s] == 0 && c.fits_quad[s]) ? 1 : 0;
+            Schedule sch;
+            sch.exec_of = assign_executors(S, parts.part_of, c, K, W);
+            sch.lists = executor_lists(S, sch.exec_of, K, W);
+            return sch;
+        }
+
+        // ---------------- phase 10: storage offsets: the factor panels, then the update-matrix arena
+        void place_storage(Symbolic& S, Schedule const& sch, ivec const& depth, SymbolicOptions const& opt)
+        {
+            int const nf = S.nfronts;
             S.f_lptr.resize(nf);
             S.f_uptr.resize(nf);
             S.f_sptr.assign(nf, 0);
@@ -1264,28 +1340,28 @@ namespace pe
             // matrix in a persistent slot; inside one executor the matrices live on TWO LIFO stacks chosen by the parity of
             // the tree depth: a front writes its Schur tiles while later tiles still gather from its children's, so a parent
             // must never overlap its children -- children always sit on the other stack.
-            long long base = 0;
-            auto on_stacks = [&](int s)
+            std::vector<char> persistent(nf);
+            S.static_root_doubles = 0;
+            for(int s = 0; s < nf; ++s)
             {
                 int const P = S.f_parent[s];
                 // (a MID front is factored by its own launch, before and in another order than the cooperative list it belongs to:
                 //  its update matrix cannot live on that executor's LIFO stacks; likewise a QUAD front under a wave front of the per-instance path)
-                return !(exec_of[s] < 0 || P < 0 || exec_of[P] != exec_of[s] || S.f_kind[s] == 3 || (S.f_quad[s] && !S.f_quad[P]));
-            };
-            // a static root of the lane-group kernel: the launches that skip the static fronts still assemble its update matrix + vector into
-            // the (dynamic) parent -- on the LIFO stacks a later front of the same launch would have overwritten them
-            auto static_quad_root = [&](int s) { return S.f_quad[s] && S.f_static[s] && S.f_parent[s] >= 0 && !S.f_static[S.f_parent[s]]; };
-            auto persistent = [&](int s) { return !on_stacks(s) || static_quad_root(s); };
-            S.static_root_doubles = 0;
+                bool const on_stacks = !(sch.exec_of[s] < 0 || P < 0 || sch.exec_of[P] != sch.exec_of[s] || S.f_kind[s] == 3 || (S.f_quad[s] && !S.f_quad[P]));
+                // a static root of the lane-group kernel: the launches that skip the static fronts still assemble its update matrix + vector into
+                // the (dynamic) parent -- on the LIFO stacks a later front of the same launch would have overwritten them
+                bool const static_quad_root = S.f_quad[s] && S.f_static[s] && P >= 0 && !S.f_static[P];
+                if(on_stacks && static_quad_root) S.static_root_doubles += slot_doubles(S.f_u[s]);
+                persistent[s] = !on_stacks || static_quad_root;
+            }
+            long long base = 0;
             for(int s = 0; s < nf; ++s)
-                if(on_stacks(s) && static_quad_root(s)) S.static_root_doubles += static_cast<long long>(S.f_u[s]) * (S.f_u[s] + 1);
-            for(int s = 0; s < nf; ++s)
-                if(persistent(s))
+                if(persistent[s])
                 {
                     S.f_sptr[s] = base;
-                    base += static_cast<long long>(S.f_u[s]) * (S.f_u[s] + 1);
+                    base += slot_doubles(S.f_u[s]);
                 }
-            for(auto const& lst: lists)
+            for(auto const& lst: sch.lists)
             {
                 long long sp[2] = {0, 0}, peak[2] = {0, 0};
                 std::vector<long long> rel_off(lst.size(), 0);
@@ -1295,27 +1371,26 @@ namespace pe
                     for(int a = S.f_child_ptr[s]; a < S.f_child_ptr[s + 1]; ++a)
                     {
                         int const c = S.f_child[a];
-                        if(!persistent(c)) sp[depth[c] & 1] -= static_cast<long long>(S.f_u[c]) * (S.f_u[c] + 1);
+                        if(!persistent[c]) sp[depth[c] & 1] -= slot_doubles(S.f_u[c]);
                     }
-                    if(persistent(s)) continue;
+                    if(persistent[s]) continue;
                     int const q = depth[s] & 1;
                     rel_off[qi] = sp[q];
-                    sp[q] += static_cast<long long>(S.f_u[s]) * (S.f_u[s] + 1);
+                    sp[q] += slot_doubles(S.f_u[s]);
                     peak[q] = std::max(peak[q], sp[q]);
                 }
                 if(sp[0] != 0 || sp[1] != 0)
                 {
                     S.error = "internal: executor stacks not empty at the end";
-                    return false;
+                    return;
                 }
                 for(size_t qi = 0; qi < lst.size(); ++qi)
                 {
                     int const s = lst[qi];
-                    if(!persistent(s)) S.f_sptr[s] = base + ((depth[s] & 1) ? peak[0] : 0) + rel_off[qi];
+                    if(!persistent[s]) S.f_sptr[s] = base + ((depth[s] & 1) ? peak[0] : 0) + rel_off[qi];
                 }
                 base += peak[0] + peak[1];
             }
-            S.work_doubles = 0;
             if(opt.quad)
             {
                 S.q_zero_off = base;  // never written: lanes of the lane-group kernel without a contribution read their zeros here
@@ -1323,33 +1398,77 @@ namespace pe
             }
             S.arena_doubles = base;
         }
-        // inverse relative maps of every parent front
-        S.f_inv_off.assign(S.f_child.size(), -1);
-        S.f_cnp.assign(S.f_child.size(), 0);
-        S.f_bmask.assign(S.f_child.size(), 0u);
-        S.f_inv.clear();
-        S.wave_panel_doubles = 1;
-        for(int s = 0; s < nf; ++s)
+
+        // ---------------- phase 11: inverse relative maps of every parent front (per child edge), the largest panel need of a wave front
+        void child_maps(Symbolic& S)
         {
-            int const m = S.f_p[s] + S.f_u[s];
-            if(S.f_kind[s] == 0) S.wave_panel_doubles = std::max<long long>(S.wave_panel_doubles, static_cast<long long>(pe_ld(m)) * S.f_p[s] + static_cast<long long>(pe_ld(S.f_p[s])) * S.f_u[s]);
-            for(int a = S.f_child_ptr[s]; a < S.f_child_ptr[s + 1]; ++a)
+            S.f_inv_off.assign(S.f_child.size(), -1);
+            S.f_cnp.assign(S.f_child.size(), 0);
+            S.f_bmask.assign(S.f_child.size(), 0u);
+            S.f_inv.clear();
+            S.wave_panel_doubles = 1;
+            for(int s = 0; s < S.nfronts; ++s)
             {
-                int const c = S.f_child[a];
-                S.f_inv_off[a] = static_cast<long long>(S.f_inv.size());
-                S.f_inv.resize(S.f_inv.size() + m, -1);
-                int* inv = S.f_inv.data() + S.f_inv_off[a];
-                for(int i = 0; i < S.f_u[c]; ++i)
+                int const m = S.f_p[s] + S.f_u[s];
+                if(S.f_kind[s] == 0) S.wave_panel_doubles = std::max<long long>(S.wave_panel_doubles, static_cast<long long>(pe_ld(m)) * S.f_p[s] + static_cast<long long>(pe_ld(S.f_p[s])) * S.f_u[s]);
+                for(int a = S.f_child_ptr[s]; a < S.f_child_ptr[s + 1]; ++a)
                 {
-                    int const l = S.f_rel[S.f_rows_ptr[c] + i];
-                    inv[l] = i;
-                    if(l >= S.f_p[s]) S.f_bmask[a] |= 1u << std::min((l - S.f_p[s]) >> 4, 31);
+                    int const c = S.f_child[a];
+                    S.f_inv_off[a] = static_cast<long long>(S.f_inv.size());
+                    S.f_inv.resize(S.f_inv.size() + m, -1);
+                    int* inv = S.f_inv.data() + S.f_inv_off[a];
+                    for(int i = 0; i < S.f_u[c]; ++i)
+                    {
+                        int const l = S.f_rel[S.f_rows_ptr[c] + i];
+                        inv[l] = i;
+                        if(l >= S.f_p[s]) S.f_bmask[a] |= 1u << std::min((l - S.f_p[s]) >> 4, 31);
+                    }
+                    int np = 0;
+                    while(np < S.f_u[c] && S.f_rel[S.f_rows_ptr[c] + np] < S.f_p[s]) ++np;
+                    S.f_cnp[a] = np;
                 }
-                int np = 0;
-                while(np < S.f_u[c] && S.f_rel[S.f_rows_ptr[c] + np] < S.f_p[s]) ++np;
-                S.f_cnp[a] = np;
             }
         }
+    }  // namespace
+
+    void build_quad_plan(Symbolic& S, int lds_doubles);  // phase 12, below
+
+    bool analyze(int n, int const* rp, int const* ci, double const* vals, SymbolicOptions const& opt, Symbolic& S)
+    {
+        S = Symbolic{};
+        S.n = n;
+        S.nnzA = rp[n];
+        if(n == 0) return true;
+
+        Ordering ord = fill_reducing_order(n, rp, ci, vals, opt, S.error);
+        S.structurally_singular = ord.singular;
+        S.n_row_swaps = ord.swaps;
+        if(!S.error.empty()) return false;
+        ivec& q = ord.q;  // re-permuted twice on the way down: by the postorder of its tree, and by the absorption
+
+        Tree tree = column_tree(ord.gp, ord.gi, q, true);
+        for(int j = 0; j < n; ++j) S.nnz_LU += 2LL * static_cast<long long>(tree.st[j].size()) + 1;
+        std::vector<SN> const sn = supernodes(tree, q, opt);
+        Groups const groups = absorb_children(tree, sn, q, opt, S.error);
+        if(!S.error.empty()) return false;
+        tree = column_tree(ord.gp, ord.gi, q, false);  // (of the final order)
+
+        std::vector<FR> const fronts = split_into_fronts(tree, groups, q, opt, S.error);
+        if(!S.error.empty()) return false;
+        FrontMaps const maps = fill_front_tables(S, tree, fronts);
+        if(!S.error.empty()) return false;
+
+        S.col_src = q;
+        S.row_src.resize(n);
+        for(int k = 0; k < n; ++k) S.row_src[k] = ord.rmatch[q[k]];
+        own_entries(S, rp, ci, maps.col2front);
+        if(!S.error.empty()) return false;
+        classify_static(S, opt, rp[n]);
+
+        Schedule const sch = schedule(S, opt);
+        place_storage(S, sch, maps.depth, opt);
+        if(!S.error.empty()) return false;
+        child_maps(S);
         if(opt.quad) build_quad_plan(S, opt.quad_lds_doubles);
         return true;
     }
@@ -1549,8 +1668,7 @@ namespace pe
                 int const P = S.f_parent[s];
                 root_of[s] = (P >= 0 && S.f_kind[P] == 3) ? root_of[P] : s;
                 if(root_of[s] == s) roots.push_back(s);
-                double const m = S.f_p[s] + S.f_u[s];
-                cost[root_of[s]] += 400.0 + m * m * (2.0 + S.f_p[s]);
+                cost[root_of[s]] += front_cost(S.f_p[s], S.f_u[s]);
             }
             std::sort(roots.begin(), roots.end(), [&](int a, int b) { return cost[a] != cost[b] ? cost[a] > cost[b] : a < b; });
             std::vector<double> load(W, 0.0);

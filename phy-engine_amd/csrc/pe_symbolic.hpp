@@ -2,11 +2,22 @@
 //
 // Replaces the per-call `solver.compute(A)` analysis of the reference (Eigen SparseLU analyzePattern:
 // COLAMD + etree + supernodes, circuits/circuit.h:1516) with a ONE-TIME analysis whose output is a static
-// assembly tree of dense fronts.  The numeric work (pe_kernels.hip) then runs with no pivot search:
-//   1. row matching   -> zero-free, large diagonal (MNA branch rows of V-sources have D == 0)
-//   2. nested dissection (BFS level-set bisection) + minimum degree on the leaves, on pattern(PA + (PA)^T)
-//   3. elimination tree, postorder, column structures, relaxed supernodes  -> fronts
-//   4. assembly maps (A slot -> front cell, child update rows -> parent rows), storage offsets
+// assembly tree of dense fronts.  The numeric work (pe_kernels.hip) then runs with no pivot search.
+// The phases of analyze(), one function each in pe_symbolic.cpp:
+//    1. fill_reducing_order  row matching -> zero-free, large diagonal (MNA branch rows of V-sources have D == 0); pattern(PA + (PA)^T);
+//                            nested dissection (BFS level-set bisection) + minimum degree on the leaves.  The seam for another ordering
+//    2. column_tree          elimination tree and column structures, the ordering re-postordered
+//    3. supernodes           fundamental runs, relaxed merging of last children
+//    4. absorb_children      a parent swallows any child while the merged front fits a wavefront; re-permutes, then the tree again
+//    5. split_into_fronts    groups cut against the wave, LDS-panel and top budgets -> fronts
+//    6. fill_front_tables    pivots, update rows, parents, children, child update rows -> parent rows, depth, statistics
+//    7. own_entries          A slot -> front cell
+//    8. classify_static      fronts no x-dependent entry reaches
+//    9. schedule             parts, wave subtrees, cooperative and top fronts, lane-group fronts; executors and their lists, top levels
+//   10. place_storage        factor offsets; the update-matrix arena: persistent slots and two LIFO stacks per executor
+//   11. child_maps           parent rows -> child update rows, per child edge
+//   12. build_quad_plan      the index program of the lane-group kernel (opt.quad)
+// build_assembly_lists() follows once the launch geometry fixed the LDS caps.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -70,8 +81,8 @@ namespace pe
         // the later Newton iterations of a solve point gathers again.  Null (or of another size): nothing is known, every front is dynamic.
         std::vector<char> const* dyn_slots{nullptr};
         std::vector<char> const* dyn_rows{nullptr};
-    long long panel_reserve{384};    // LDS doubles kept free behind the panels of a large front (right-hand-side column, staged child maps)
-    long long panel_doubles{18000};  // LDS doubles available for the L (m x p) and U (p x u) panels of a cooperative front
+        long long panel_reserve{384};    // LDS doubles kept free behind the panels of a large front (right-hand-side column, staged child maps)
+        long long panel_doubles{18000};  // LDS doubles available for the L (m x p) and U (p x u) panels of a cooperative front
     };
 
     struct Symbolic
@@ -100,7 +111,6 @@ namespace pe
         std::vector<long long> f_sptr;          // offset of the u x u update matrix (followed by the u update vector) in the stack arena
         long long factor_doubles{};
         long long arena_doubles{};
-        long long work_doubles{};               // (unused)
         long long wave_panel_doubles{};         // largest p*(m+u) of a wave front (LDS doubles of one wavefront's slot)
         std::vector<int> f_kind;                // 0: wave front, 1: cooperative front of a part, 2: top front, 3: MID front (quad mode: a front of a
                                                 // part's cooperative list of order <= 64 whose whole subtree the lane-group kernels can run; factored by
